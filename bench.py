@@ -9,7 +9,8 @@ rank per GPU) rank 0 builds the index, its row table is broadcast once over
 RCCL/xGMI, every rank queries its own shard of reads, no data-path collective
 ("scaling": "weak").
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps (and with --dump-outputs writes what the
+last one computed); --full adds the legs after the timed region: baselines, other queries, layouts and sizes, parity samples.
 """
 import argparse
 import ctypes as C
@@ -111,6 +112,19 @@ def ensure_pangenome(wl, world, rank, barrier):
             os.rename(reads_file + ".tmp", reads_file)
     barrier()
     return idx_dir, reads_file
+
+
+def prepare_inputs(workload="c2"):
+    """Build ahead of any run what `workload` reads from the cache (a .bench_cache/ beside this file unless $MOVI_BENCH_CACHE is
+    set): __graft_entry__.build() calls it on a machine with a GPU, because the c2 pangenome takes minutes of single-threaded
+    construction that a plain run must not spend before its first step."""
+    global CACHE
+    if not os.environ.get("MOVI_BENCH_CACHE"):
+        CACHE = os.path.join(ROOT, ".bench_cache")
+    wl = dict(WORKLOADS[workload])
+    if wl["kind"] == "pangenome":
+        return ensure_pangenome(wl, 1, 0, lambda: None)
+    return None
 
 
 def served_from(table_bytes):
@@ -729,6 +743,37 @@ def usable_cores():
 SEED = 20260529
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 INFINITY_CACHE_BYTES = 256 << 20   # MI355X_MICROARCH.md: 256 MiB Infinity Cache (MALL) in front of HBM
+DUMP_MAX_BASES = 1 << 23   # --dump-outputs: per-base values written at most (32 MB as float32) ...
+DUMP_MAX_READS = 1 << 19   # ... and reads (<= 5 per-read arrays of float64: 21 MB)
+
+
+def dump_outputs(out_dir, offs, per_base, per_read):
+    """--dump-outputs: one step's device arrays -> out_dir/<name>.npy.  8- and 16-bit values (the u16 PML / ZML vectors, the error
+    flags) go as float32, wider ones as float64: both exact.  A batch beyond DUMP_MAX_BASES bases or DUMP_MAX_READS reads is
+    sampled by whole reads in a fixed seeded order, so runs with the same arguments write the same reads (read_ids.npy)."""
+    n_reads = len(offs) - 1
+    lens = (offs[1:] - offs[:-1]).astype(np.int64)
+    if int(offs[-1]) <= DUMP_MAX_BASES and n_reads <= DUMP_MAX_READS:
+        ids = np.arange(n_reads, dtype=np.int64)
+    else:
+        perm = np.random.default_rng(SEED + 5).permutation(n_reads)
+        k = min(int(np.searchsorted(np.cumsum(lens[perm]), DUMP_MAX_BASES, side="right")), DUMP_MAX_READS)
+        ids = np.sort(perm[:k])
+    ln = lens[ids]
+    pos = np.repeat(offs[:-1][ids].astype(np.int64) - (np.cumsum(ln) - ln), ln) + np.arange(int(ln.sum()), dtype=np.int64)
+
+    def host(t, idx):
+        a = t.cpu().numpy()
+        if a.dtype == np.int16:
+            a = a.view(np.uint16)                    # PML / ZML lengths: u16 in int16 tensors
+        return a[idx].astype(np.float32 if a.itemsize <= 2 else np.float64)
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in per_base.items():
+        np.save(os.path.join(out_dir, name + ".npy"), host(t, pos))
+    for name, t in per_read.items():
+        np.save(os.path.join(out_dir, name + ".npy"), host(t, ids))
+    np.save(os.path.join(out_dir, "read_ids.npy"), ids.astype(np.float64))
 
 
 # ---- `--dry-run`: the whole N-rank flow of this file on the CPU, over gloo, WITHOUT a GPU call (round 6) -------------------------
@@ -859,15 +904,26 @@ def main():
     ap.add_argument("--big-rows", type=int, default=1_000_000_000, help="rows of the `big_table` leg's table (tests shrink it)")
     ap.add_argument("--long-reads", type=int, default=0, help="reads per GPU of the `long_reads` leg (default: c3's 100 000; tests shrink it)")
     ap.add_argument("--quick", action="store_true", help="the timed region only: no cpu_baseline, long_reads, host_path, sustained, big_table (A/B sweeps)")
-    ap.add_argument("--with-mask-leg", action="store_true", help="with --quick: keep the `mask_path` leg (the mask walk and the expand kernel timed on their own)")
+    ap.add_argument("--with-mask-leg", action="store_true", help="with --quick or without --full: keep the `mask_path` leg (the mask walk and the expand kernel timed on their own)")
     ap.add_argument("--dry-run", action="store_true", help="the N-rank flow on the CPU over gloo with a stand-in engine: no GPU call, no result (value null); "
                     "spawn, rank 0's synthesis, the broadcast, the read hand-over, timing and JSON assembly are real (tests/test_dist_cpu.py)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline as well: sustained, mask_path, zml, count, cpu_baseline "
+                    "(+ parity_sample_ok), long_reads, host_path, cli_path, big_table.  Without it a run sets up, warms up, times --steps "
+                    "steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's shard) as DIR/<name>.npy, float32 / float64; "
+                         "batches above %d bases: a fixed, seeded sample of whole reads (DIR/read_ids.npy)" % DUMP_MAX_BASES)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs: a dry run computes nothing")
     t_wall0 = time.time()
     if args.dry_run:
         args.no_cpu_baseline = args.no_sustained = True
-    args.quick_only_walk = bool(args.quick)
-    if args.quick:
+    # a run without --full (and any --quick run) is the timed region only: no leg, no baseline, no parity sample
+    args.quick_only_walk = bool(args.quick) or not args.full
+    if args.quick_only_walk:
         args.no_cpu_baseline = args.no_long_reads = args.no_big_table = args.no_sustained = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
@@ -1066,6 +1122,17 @@ def main():
 
     # ---- timed region: exactly K steps, barrier + synchronize on both sides, max over ranks
     elapsed, rank_seconds, avg_kern_s = timed_steps(torch, dist, world, dev, stream, step, args.steps)
+    if args.dump_outputs and rank == 0:
+        # what a caller of step() receives, as the last timed step left it (before any leg below reuses the buffers)
+        if args.query == "count":
+            per_base, per_read = {}, {"matched": d_matched, "count": d_count}
+        elif args.classify and args.query == "pml":
+            per_base = {"pml": d_out} if args.classify == 1 else {}
+            per_read = {"bins_above": d_above, "bins_below": d_below, "bins_sum_max": d_summax}
+        else:
+            per_base, per_read = {args.query: d_out}, {}
+        per_read["errors"] = d_err
+        dump_outputs(args.dump_outputs, offs, per_base, per_read)
     total_bases_per_step = sum_over_ranks(torch, dist, world, dev, n_bases)
 
     # which kernel the library's launch policy picked for this batch, and with which shape: asked, not assumed

@@ -22,8 +22,8 @@ def _line(out):
 
 
 def test_bench_single_gpu_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1"],
-                       capture_output=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
+                        "--full"], capture_output=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
     for k in REQUIRED:
@@ -35,6 +35,37 @@ def test_bench_single_gpu_contract():
     assert d["roofline"]["lane_iterations_per_s"] > 0 and d["roofline"]["rows_read_per_s"] > 0
     assert d["roofline"]["kernel"].startswith("pml_kernel_flatp<6, unsigned int, 0, 0, 0, 1, ") and d["rccl_ranks"] == 0
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0 and d["parity_sample_ok"] is True
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A run without --full prints the headline alone (no leg, baseline or parity sample), and --dump-outputs writes what its last
+    timed step computed: twice the same files, and PML vectors equal to the oracle's on the same seeded table and reads."""
+    import numpy as np
+    import bench
+    from oracle.oracle import Oracle
+    from tools import synth
+    got = []
+    for i in range(2):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "4", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / str(i))], capture_output=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _line(r.stdout)
+        assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0 and d["unit"] == "Gbases/s"
+        for k in ("sustained", "mask_path", "zml", "count", "cpu_baseline", "parity_sample_ok", "long_reads", "host_path",
+                  "cli_path", "big_table"):
+            assert k not in d, k
+        got.append({p.stem: np.load(p) for p in (tmp_path / str(i)).glob("*.npy")})
+    assert set(got[0]) == {"pml", "errors", "read_ids"}
+    for k, v in got[0].items():
+        assert v.dtype in (np.float32, np.float64) and np.array_equal(v, got[1][k]), k
+    wl = bench.WORKLOADS["tiny"]
+    n, L = wl["reads"], wl["read_len"]
+    assert got[0]["pml"].size == n * L and not got[0]["errors"].any()       # 3 M bases: written whole
+    six = synth.synth_index(wl["rows"], mode=wl["mode"], seed=bench.SEED)
+    bases, offs = synth.synth_reads(six, n, L, seed=bench.SEED + 1, sub_rate=wl["sub"], n_rate=0.001)
+    k = 500
+    exp, _, _ = Oracle(six.image()).pml_batch(bases[: int(offs[k])], offs[: k + 1], threads=4)
+    assert np.array_equal(got[0]["pml"][: exp.size], exp)
 
 
 @pytest.mark.parametrize("query", ["pml", "count"])
@@ -72,7 +103,7 @@ def test_bench_two_ranks_print_all_three_legs():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tinypg", "--steps", "3",
-                        "--warmup", "1", "--big-rows", "2000000", "--long-reads", "256", "--no-sustained"],
+                        "--warmup", "1", "--big-rows", "2000000", "--long-reads", "256", "--no-sustained", "--full"],
                        capture_output=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
@@ -94,7 +125,7 @@ def test_bench_default_line_legs_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tinypg", "--steps", "3", "--warmup", "1",
-                        "--big-rows", "2000000", "--long-reads", "256", "--no-sustained"], capture_output=True, timeout=1200, env=env)
+                        "--big-rows", "2000000", "--long-reads", "256", "--no-sustained", "--full"], capture_output=True, timeout=1200, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _line(r.stdout)
     assert d["parity_sample_ok"] is True and d["cpu_baseline"]["value"] > 0

@@ -98,7 +98,7 @@ def test_bench_dry_run_eight_ranks(built_lib):
     import time
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--dry-run", "--workload", "tinypg", "--big-rows", "300000",
-                        "--long-reads", "64", "--steps", "3", "--warmup", "1"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
+                        "--long-reads", "64", "--steps", "3", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=1500, cwd=ROOT)
     wall = time.time() - t0
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

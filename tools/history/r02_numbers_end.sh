@@ -2,7 +2,7 @@
 # End-of-round-2 result table: one bench.py line per workload (the 1 B-row workloads but c4 PML left out: minutes each).
 OUT=${1:-gpurun_out/r02_numbers_end.txt}
 mkdir -p "$(dirname "$OUT")"
-run() { echo "== $1"; timeout 900 python bench.py --steps 10 --warmup 2 $2 2>/dev/null | python -c "
+run() { echo "== $1"; timeout 900 python bench.py --full --steps 10 --warmup 2 $2 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); c=d['config']; r=d['roofline']
 print('%s | %s | rows=%d reads=%d len=%d | f=%.2f s=%.2f B=%.1f | %.2f Gbases/s | %.3f ms | frac=%.4f | segs=%s | cpu=%s | long=%s | few=%s | host=%s' % (d['metric'], r['kernel'], c['rows'], c['reads_per_gpu'], c['read_len'], c['fast_forwards_per_base'], c['scans_per_base'], c['algorithmic_bytes_per_base'], d['value'], r['kernel_ms_avg'], r['frac'], c.get('segments'), (d.get('cpu_baseline') or {}).get('value'), (d.get('long_reads') or {}).get('value'), (d.get('few_long_reads') or {}).get('segment_parallel'), (d.get('host_path') or {}).get('page_locked')))"; }

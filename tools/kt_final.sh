@@ -4,7 +4,7 @@ OUT=$1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
 run() {  # name, bench args
-  timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/$1" -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline $2 > "$OUT/$1.log" 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats -d "$OUT/$1" -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline $2 > "$OUT/$1.log" 2>&1
 }
 run c2_pml ""
 run c3_pml "--workload c3 --steps 5"

@@ -5,12 +5,12 @@
 OUT=$1; ARGS=$2
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
-timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline $ARGS > "$OUT/kt.log" 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats -d "$OUT/kt" -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline $ARGS > "$OUT/kt.log" 2>&1
 i=0
 while read -r grp; do
   [ -z "$grp" ] && continue
   i=$((i+1))
-  timeout 300 rocprofv3 --pmc $grp -d "$OUT/pmc$i" -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline $ARGS > "$OUT/pmc$i.log" 2>&1
+  timeout 300 rocprofv3 --pmc $grp -d "$OUT/pmc$i" -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline $ARGS > "$OUT/pmc$i.log" 2>&1
 done <<'GROUPS'
 FETCH_SIZE
 WRITE_SIZE

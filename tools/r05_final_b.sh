@@ -2,12 +2,12 @@
 # round 5, final tree: the default bench line (as the driver runs it), two ranks sharing the box's GPU, and the kernel trace of the default command
 cd "$(dirname "$0")/.." || exit 1
 O=gpurun_out/r05_final_b; mkdir -p $O
-( time python3 bench.py ) > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$?" >> $O/bench_default.err
+( time python3 bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$?" >> $O/bench_default.err
 tail -3 $O/bench_default.err
-( time MOVI_BENCH_SHARE_GPU=1 python3 bench.py --gpus 2 --no-sustained ) > $O/bench_n2_shared.json 2> $O/bench_n2_shared.err; echo "rc=$?" >> $O/bench_n2_shared.err
+( time MOVI_BENCH_SHARE_GPU=1 python3 bench.py --full --gpus 2 --no-sustained ) > $O/bench_n2_shared.json 2> $O/bench_n2_shared.err; echo "rc=$?" >> $O/bench_n2_shared.err
 tail -3 $O/bench_n2_shared.err
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-timeout 1200 rocprofv3 --kernel-trace --stats -d $O/kt -- python3 bench.py --no-cpu-baseline > $O/kt.log 2>&1
+timeout 1200 rocprofv3 --kernel-trace --stats -d $O/kt -- python3 bench.py --full --no-cpu-baseline > $O/kt.log 2>&1
 python3 tools/prof_summary.py $O/kt > $O/kt_summary.txt 2>&1; find $O -name "*.db" -delete
 head -14 $O/kt_summary.txt | cut -c1-200
 python3 - $O/bench_default.json <<'PY'

@@ -6,7 +6,7 @@ O=gpurun_out/r06_a; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
 timeout 1500 python3 -m pytest tests/test_mask_gpu.py tests/test_kernel_coverage_gpu.py -x -q > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest.log
 tail -5 $O/pytest.log
-( time timeout 900 python3 bench.py --no-big-table --no-long-reads ) > $O/bench_c2.json 2> $O/bench_c2.err; echo "rc=$?" >> $O/bench_c2.err
+( time timeout 900 python3 bench.py --full --no-big-table --no-long-reads ) > $O/bench_c2.json 2> $O/bench_c2.err; echo "rc=$?" >> $O/bench_c2.err
 for wl in c2 c3; do for via in 0 1; do
   timeout 400 python3 bench.py --quick --workload $wl --opt pml_via_mask=$via > $O/${wl}_via$via.json 2> $O/${wl}_via$via.err
 done; done

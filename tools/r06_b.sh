@@ -20,7 +20,7 @@ done; done
 python3 tools/prof_summary.py $O > $O/pmc_summary.txt 2>&1; find $O -name "*.db" -delete
 grep -h "PMC.*flatp" $O/pmc_summary.txt | cut -c1-230 | sort | uniq > $O/pmc_walk.txt
 for nt in 1 0; do
-  ( MOVI_EXPAND_NT=$nt timeout 900 python3 bench.py --no-big-table --no-long-reads --opt deep_rows=0 ) > $O/bench_c2_nt$nt.json 2> $O/bench_c2_nt$nt.err
+  ( MOVI_EXPAND_NT=$nt timeout 900 python3 bench.py --full --no-big-table --no-long-reads --opt deep_rows=0 ) > $O/bench_c2_nt$nt.json 2> $O/bench_c2_nt$nt.err
 done
 python3 - $O <<'PY'
 import json,sys,glob,os

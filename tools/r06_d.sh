@@ -8,7 +8,7 @@ tail -3 $O/pytest.log
 timeout 400 python3 bench.py --quick --workload c2 --waves-per-cu 13 > $O/c2_default_cap13.json 2> $O/c2_default_cap13.err
 timeout 400 python3 bench.py --quick --workload c2 > $O/c2_default.json 2> $O/c2_default.err
 for th in 6 8 12 16 24; do
-  ( timeout 900 python3 bench.py --no-big-table --no-long-reads --opt host_threads=$th ) > $O/bench_c2_th$th.json 2> $O/bench_c2_th$th.err
+  ( timeout 900 python3 bench.py --full --no-big-table --no-long-reads --opt host_threads=$th ) > $O/bench_c2_th$th.json 2> $O/bench_c2_th$th.err
 done
 python3 - $O <<'PY'
 import json,sys,glob,os

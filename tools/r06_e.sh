@@ -7,8 +7,8 @@ timeout 1500 python3 -m pytest tests/test_zml_coverage_gpu.py tests/test_mask_gp
 tail -3 $O/pytest.log
 for wl in c2 c3; do timeout 400 python3 bench.py --quick --workload $wl > $O/${wl}_default.json 2> $O/${wl}_default.err; done
 timeout 400 python3 bench.py --quick --workload c2 --opt pml_via_mask=1 > $O/c2_via1.json 2> $O/c2_via1.err
-( timeout 900 python3 bench.py --no-big-table --no-long-reads ) > $O/bench_c2.json 2> $O/bench_c2.err
-( timeout 900 python3 bench.py --no-big-table --no-long-reads ) > $O/bench_c2_again.json 2> $O/bench_c2_again.err
+( timeout 900 python3 bench.py --full --no-big-table --no-long-reads ) > $O/bench_c2.json 2> $O/bench_c2.err
+( timeout 900 python3 bench.py --full --no-big-table --no-long-reads ) > $O/bench_c2_again.json 2> $O/bench_c2_again.err
 python3 - $O <<'PY'
 import json,sys,glob,os
 O=sys.argv[1]

@@ -6,12 +6,12 @@ O=gpurun_out/r06_final; mkdir -p $O
 ( time timeout 2400 python3 -m pytest tests -q -m gpu -p no:cacheprovider --durations=15 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest.log
 tail -25 $O/pytest.log | cut -c1-200
 ( time python3 -c "import __graft_entry__ as g; g.smoke()" ) > $O/smoke.log 2>&1; echo "smoke rc=$?" | tee -a $O/smoke.log
-( time python3 bench.py ) > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$?" >> $O/bench_default.err
+( time python3 bench.py --full ) > $O/bench_default.json 2> $O/bench_default.err; echo "rc=$?" >> $O/bench_default.err
 tail -3 $O/bench_default.err
-( time MOVI_BENCH_SHARE_GPU=1 python3 bench.py --gpus 2 --no-sustained ) > $O/bench_n2_shared.json 2> $O/bench_n2_shared.err; echo "rc=$?" >> $O/bench_n2_shared.err
+( time MOVI_BENCH_SHARE_GPU=1 python3 bench.py --full --gpus 2 --no-sustained ) > $O/bench_n2_shared.json 2> $O/bench_n2_shared.err; echo "rc=$?" >> $O/bench_n2_shared.err
 tail -3 $O/bench_n2_shared.err
 cd /tmp && export TMPDIR=/tmp && cd - >/dev/null
-timeout 1200 rocprofv3 --kernel-trace --stats -d $O/kt -- python3 bench.py --no-cpu-baseline > $O/kt.log 2>&1
+timeout 1200 rocprofv3 --kernel-trace --stats -d $O/kt -- python3 bench.py --full --no-cpu-baseline > $O/kt.log 2>&1
 python3 tools/prof_summary.py $O/kt > $O/kt_summary.txt 2>&1; find $O -name "*.db" -delete
 head -30 $O/kt_summary.txt | cut -c1-200
 python3 - $O/bench_default.json <<'PY'

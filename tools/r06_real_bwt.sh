@@ -9,7 +9,7 @@ WLS=${1:-c4real c4real2}
 K=$(echo $WLS | sed 's/ / or /g')
 ( time MOVI_SLOW_TESTS=1 timeout 3000 python3 -m pytest tests/test_real_bwt_gpu.py -q -m gpu -x -k "$K" ) > $O/pytest.txt 2>&1; tail -5 $O/pytest.txt
 for w in $WLS; do
-  ( time timeout 1500 python3 bench.py --workload $w --no-big-table --no-long-reads --no-sustained ) > $O/bench_$w.json 2> $O/bench_$w.err
+  ( time timeout 1500 python3 bench.py --full --workload $w --no-big-table --no-long-reads --no-sustained ) > $O/bench_$w.json 2> $O/bench_$w.err
   python3 - $O/bench_$w.json $w <<'PY'
 import json,sys
 try:
