@@ -163,10 +163,16 @@ int movi_index_load_replicated(const char *index_dir_or_file, const int *devices
  * are built for it only under "count_variant" 0, the base-synchronous kernel of rounds 1 - 4, and then where a sample of the table
  * says the search will use them) | MOVI_PREPARE_ZML (nothing: accepted for symmetry).  Honours the options set before it ("kmer_k", "ftab_k", "ahead_rows": a table the caller built or switched
  * off is left alone).  Waits for the builders; *derived_bytes (optional) = bytes of device memory the handle's derived tables
- * hold afterwards (movi_index_info "derived_bytes").  After it the *_device entry points of those queries allocate nothing
- * and build nothing on this handle (batches of long reads still grow the segment workspace on their first call): they can be
- * captured into a HIP graph without a warm-up call -- a look-ahead copy that was declined for lack of device memory is asked for
- * again by the next movi_index_prepare call only, never from inside a query.  Not calling it is fine: the first query does the
+ * hold afterwards (movi_index_info "derived_bytes").  MOVI_PREPARE_PML also reserves the reset-mask words of movi_pml_device's
+ * default route ("pml_via_mask") for a batch of up to 2^28 bases in up to 2^22 reads (50 MB; 1 M reads of 150 bp take 23 MB of
+ * them; a bigger "reserve_device_masks", before or after, stays).  After it the *_device entry points of those queries allocate
+ * nothing and build nothing on this handle (batches of long reads still grow the segment workspace on their first call; an
+ * uncaptured movi_pml_device call on a batch whose mask words outgrow the reservation grows it): they can be captured into a HIP
+ * graph without a warm-up call.  A movi_pml_device call made under a stream capture never allocates: a batch whose mask words do
+ * not fit takes the route without masks (same answers).  A later growth keeps a mask buffer that a captured call used (movi_index_info
+ * "device_scratch_bytes" counts it) until "release_scratch" or movi_index_destroy, so such graphs stay valid until then -- and
+ * "release_scratch" invalidates every graph captured on the handle.  A look-ahead copy that was declined for lack of device memory is
+ * asked for again by the next movi_index_prepare call only, never from inside a query.  Not calling it is fine: the first query does the
  * same, lazily (and then retries a declined copy every 64 calls). */
 #define MOVI_PREPARE_PML 1u
 #define MOVI_PREPARE_COUNT 2u
@@ -267,7 +273,10 @@ int movi_launch_log(char *buf, size_t cap, size_t *needed);
  * caller sees their cost).  Keys: "rows_bytes" (the resident row table), "kmer_bytes", "ftab_bytes", "ahead_rows_bytes",
  * "ckpt_bytes" (0 = not built), "derived_bytes" (their sum), "ahead_no_ff" (share of the table's BWT
  * positions that reach their LF target without a fast-forward, tallied when the look-ahead rows are built: 0.83 on the
- * pangenome BWT, 0.51 on a uniformly random run sequence; -1 = not tallied yet).  Unknown key: MOVI_ERR_ARG. */
+ * pangenome BWT, 0.51 on a uniformly random run sequence; -1 = not tallied yet), "device_scratch_bytes" (device scratch the
+ * *_device calls hold: movi_pml_device's mask words -- retired buffers that captured graphs may still use included --, the u16 vector
+ * of a movi_pml_mask_device call whose path has no mask output, the segment workspace), "host_staging_bytes" (the *_host calls'
+ * device staging).  Unknown key: MOVI_ERR_ARG. */
 int movi_index_info(const movi_index_t *ix, const char *key, double *value);
 
 /* ---- PML as reset masks (round 6) ----------------------------------------------- */
@@ -375,7 +384,8 @@ int movi_host_unregister(void *p);
  * "block_threads" (0 = auto, 64, 128, 192 or 256: the kernels' launch bound), "waves_per_cu"
  * (0 = the launch policy's cap, else at most this many wavefronts resident per CU), "idx64" (1 = run the kernel instantiations for
  * tables of 2^32 rows and more, whatever the size: a test hook), "release_scratch" (any value: frees the
- * device staging buffers that the *_host entry points keep, grow-only, across calls), "host_overlap" (0: a *_host call is never cut into overlapped pieces, whatever memory
+ * device staging buffers that the *_host entry points keep, grow-only, across calls, and the scratch of the *_device calls -- graphs
+ * captured on the handle are invalid afterwards), "host_overlap" (0: a *_host call is never cut into overlapped pieces, whatever memory
  * its buffers are in -- one upload, the walk, one download; for a caller that pipelines chunk-sized calls itself and keeps its reads in page-locked
  * memory for the direct upload, as `movi query` does; default 1), "reserve_host_bases" / "reserve_host_results" /
  * "reserve_host_reads" (that staging reserved up front instead of inside the first big call: the reads of a synchronous *_host call of
@@ -440,7 +450,8 @@ int movi_host_unregister(void *p);
  * (default 70) of the bases as masks, the rest as the vector itself by DMA into a page-locked vector; 0 = never masks: a caller whose
  * own threads are busy, like `movi query`),
  * "fused_expand" (1, the default; 0 = the expansion by kernels of their own behind the walk: A/B), "reserve_device_masks" (device scratch
- * for the mask words of movi_pml_device calls of up to this many bases, reserved now instead of inside the first such call),
+ * for the mask words of movi_pml_device calls of up to this many bases, reserved now instead of inside the first such call; grow-only,
+ * beside what movi_index_prepare reserves),
  * "host_threads" (worker threads of the host-side expansion, 0 = three quarters of the CPUs the process may use -- affinity mask capped by the cgroup's quota --, at most 24),
  * "deep_rows" (round 6: a third layout of the table for the PML walk of short reads -- 21.33 bytes per row, windows of three rows, every
  * row with what the walk reads at its LF target AND at that row's target: up to three bases per gather.  Left alone, the first PML query

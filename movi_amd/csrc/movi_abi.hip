@@ -156,10 +156,41 @@ struct movi_index {
     int host_mask_share = 70;        // "host_mask_share": percent of a mixed call's bases that come down as masks (the rest as the vector itself)
     int host_masks = -1;             // "host_masks": movi_pml_host brings reset masks down and expands them on host worker threads (-1: calls of >= 2^22 bases into a pageable vector)
     int host_threads = 0;            // "host_threads": workers of the host-side expansion (0 = host_threads_default())
+    // movi_pml_device's reset-mask words (its default route for batches of short reads), apart from the *_host staging: reserved by
+    // movi_index_prepare(MOVI_PREPARE_PML) for kPrepareMaskBases bases in kPrepareMaskReads reads, by "reserve_device_masks", and grown
+    // by a bigger call outside a stream capture.  A graph captured over a call keeps the buffer's address, so a buffer a captured call
+    // has used is never freed by a growth: it is retired and kept until release_scratch / movi_index_destroy.
+    void *dmask = nullptr;
+    size_t dmask_cap = 0;
+    bool dmask_in_graph = false;
+    std::vector<std::pair<void *, size_t>> dmask_retired;
 };
 
 static void release_scratch(movi_index *ix);
 namespace { hipError_t grow(void **p, size_t *cap, size_t bytes); }
+constexpr uint64_t kPrepareMaskBases = 1ull << 28;   // movi_index_prepare's reservation of movi_pml_device's mask words (1 M x 150 bp fits)
+constexpr uint64_t kPrepareMaskReads = 1ull << 22;
+// movi_pml_device's mask words for `bytes`: grow-only; a buffer that a captured call used is retired, not freed
+static hipError_t grow_dmask(movi_index *ix, size_t bytes) {
+    if (ix->dmask_cap >= std::max<size_t>(bytes, 8)) return hipSuccess;
+    if (ix->dmask && ix->dmask_in_graph) {
+        ix->dmask_retired.emplace_back(ix->dmask, ix->dmask_cap);
+        ix->dmask = nullptr;
+        ix->dmask_cap = 0;
+    }
+    ix->dmask_in_graph = false;
+    return grow(&ix->dmask, &ix->dmask_cap, bytes);
+}
+// Is `s` being captured into a graph?  A query that cannot tell (hipErrorStreamCaptureImplicit: the null stream while another stream
+// captures in global mode) answers yes: the callers then take the route that allocates nothing.
+static bool stream_capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) {
+        (void)hipGetLastError();
+        return true;
+    }
+    return st != hipStreamCaptureStatusNone;
+}
 // The upload stream of the overlapped host paths.  Streams of one priority share a handful of hardware queues, and a chunk's stream that
 // landed on the upload stream's queue had its walk queued behind the copies' completion packets (every sixth chunk waited for uploads that
 // were not its own: 0.1 ms of a dry upload stream each time, profiles/r06_host_path.txt).  A stream of another priority gets a queue of
@@ -1103,7 +1134,7 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
     if (!strcmp(key, "reserve_device_masks")) {              // device scratch for the mask words of movi_pml_device calls of up to `value` bases (and as many reads / 16)
         if (value < 0 || (uint64_t)value > (1ull << 40)) return fail(MOVI_ERR_ARG, "reserve_device_masks out of range");
         HIP_TRY(hipSetDevice(ix->device));
-        HIP_TRY(grow(&ix->scratch[movi_index::kMask], &ix->scratch_cap[movi_index::kMask], (size_t)pml_mask_words((uint64_t)value / 16 + 1, (uint64_t)value, 0) * 4));
+        HIP_TRY(grow_dmask(ix, (size_t)pml_mask_words((uint64_t)value / 16 + 1, (uint64_t)value, 0) * 4));
         return MOVI_OK;
     }
     if (!strcmp(key, "host_threads")) {                      // workers of the host-side mask expansion (0 = as many as the process may run on)
@@ -1205,7 +1236,7 @@ static int ml_device(bool zml, movi_index_t *ix, const uint8_t *d_bases, const u
                      uint64_t n_bases, uint16_t *d_out, uint8_t *d_read_err, const uint32_t *d_read_order, void *stream,
                      const ClsArgs &cls = ClsArgs(), DevStats *d_stats = nullptr, SegWorkspace *seg_ws = nullptr,
                      int ragged_hint = -1, int *seg_verdict = nullptr, const MaskArgs *mask = nullptr, void **tmp_p = nullptr,
-                     size_t *tmp_cap = nullptr) {
+                     size_t *tmp_cap = nullptr, bool tables_ready = false) {
     if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
     if (!d_stats) d_stats = ix->d_stats;                     // (the pipelined host path counts per chunk in flight ...
     if (!seg_ws) seg_ws = &ix->seg_ws;                       //  ... and keeps a segment workspace per chunk in flight)
@@ -1223,8 +1254,8 @@ static int ml_device(bool zml, movi_index_t *ix, const uint8_t *d_bases, const u
     HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(DevStats), s));
     if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
     // the first PML query on a handle builds its derived tables -- unless movi_index_prepare did (--logs runs on the first
-    // kernel, which uses none of them)
-    if (!zml && cls.log_ff == nullptr) ensure_pml_tables(ix, s);
+    // kernel, which uses none of them; tables_ready: the caller has asked already, once per call)
+    if (!zml && cls.log_ff == nullptr && !tables_ready) ensure_pml_tables(ix, s);
     if (zml)
         HIP_TRY(launch_zml(ix->kmode, ix->dev, d_bases, d_offsets, n_reads, n_bases, d_out, d_read_err, d_stats,
                            d_read_order, ix->cfg, s, seg_ws, ragged_hint, seg_verdict, &ix->last_launch));
@@ -1266,20 +1297,30 @@ int movi_pml_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_
         // pml_expand_* kernels behind the walk).  "pml_via_mask" 1: always; -1, the default: where the walk runs on the deep rows -- three
         // emissions per iteration: c2 78.4 -> 86.7 Gbases/s; the 1 B-row table 42.3 -> 46.0 --, i.e. batches of short reads; long reads keep
         // the ring in LDS, which is as good there (c3: 16.76 against 16.66 ms).  The mask words live in device scratch of the handle
-        // (grow-only: "reserve_device_masks" reserves it, and movi_index_prepare's promise of no allocation inside a query holds from the
-        // first call of each size on).
+        // (ix->dmask, grow-only): movi_index_prepare reserves them for kPrepareMaskBases bases, "reserve_device_masks" for more.  A bigger
+        // batch grows them -- but never under a stream capture: a captured call whose words do not fit takes the packer route, which
+        // needs no scratch, and a buffer a captured call has used is retired on growth, not freed (grow_dmask).
+        // The vector of a fused expansion leaves in aligned 16-byte stores: launch_pml fuses it only into a 16-byte aligned d_out_pml
+        // and hands any other to launch_pml_expand behind the walk.
         HIP_TRY(hipSetDevice(ix->device));
         hipStream_t s = static_cast<hipStream_t>(stream);
-        ensure_pml_tables(ix, s);
+        ensure_pml_tables(ix, s);                            // (once per call: ml_device is told so)
         if (ix->pml_via_mask > 0 || pml_vector_via_masks(ix->dev, ix->cfg, n_reads, n_bases, true, d_read_order != nullptr)) {
-            HIP_TRY(grow(&ix->scratch[movi_index::kMask], &ix->scratch_cap[movi_index::kMask], (size_t)pml_mask_words(n_reads, n_bases, 0) * 4));
-            MaskArgs m;
-            m.words = static_cast<uint32_t *>(ix->scratch[movi_index::kMask]);
-            m.phase = 0;
-            m.expand_out = d_out_pml;
-            return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, nullptr, d_read_err, d_read_order, stream, ClsArgs(), nullptr, nullptr,
-                             -1, nullptr, &m);
+            const size_t need = (size_t)pml_mask_words(n_reads, n_bases, 0) * 4;
+            const bool capturing = stream_capturing(s);
+            if (!capturing || need <= ix->dmask_cap) {
+                HIP_TRY(grow_dmask(ix, need));
+                if (capturing) ix->dmask_in_graph = true;
+                MaskArgs m;
+                m.words = static_cast<uint32_t *>(ix->dmask);
+                m.phase = 0;
+                m.expand_out = d_out_pml;
+                return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, nullptr, d_read_err, d_read_order, stream, ClsArgs(), nullptr,
+                                 nullptr, -1, nullptr, &m, nullptr, nullptr, true);
+            }
         }
+        return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, d_out_pml, d_read_err, d_read_order, stream, ClsArgs(), nullptr,
+                         nullptr, -1, nullptr, nullptr, nullptr, nullptr, true);
     }
     return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, d_out_pml, d_read_err, d_read_order, stream);
 }
@@ -1355,6 +1396,11 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     else if (!strcmp(key, "ckpt_bytes")) *value = ckpt;
     else if (!strcmp(key, "derived_bytes")) *value = kmer + ftab + ahead + deep + ckpt;
     else if (!strcmp(key, "ahead_no_ff")) *value = ix->ahead_tallied ? ix->ahead_no_ff : -1.0;
+    else if (!strcmp(key, "device_scratch_bytes")) {         // device scratch the *_device calls hold: mask words (retired ones too), vector, segment workspace
+        double b = (double)ix->dmask_cap + (double)ix->scratch_cap[movi_index::kTmp] + (double)ix->seg_ws.cap;
+        for (const auto &r : ix->dmask_retired) b += (double)r.second;
+        *value = b;
+    }
     else if (!strcmp(key, "host_staging_bytes")) {           // device staging the synchronous *_host calls hold at the moment
         double b = 0.0;
         for (int k = 0; k < movi_index::kScratchSlots; k++) b += (double)ix->scratch_cap[k];
@@ -1480,6 +1526,12 @@ static void release_scratch(movi_index *ix) {
     ix->pipe_ev.clear();
     if (ix->seg_ws.buf) (void)hipFree(ix->seg_ws.buf);
     ix->seg_ws = SegWorkspace();
+    if (ix->dmask) (void)hipFree(ix->dmask);               // (graphs captured over movi_pml_device on this handle are invalid from here on)
+    ix->dmask = nullptr;
+    ix->dmask_cap = 0;
+    ix->dmask_in_graph = false;
+    for (const auto &r : ix->dmask_retired) (void)hipFree(r.first);
+    ix->dmask_retired.clear();
     if (ix->h_rel) (void)hipHostFree(ix->h_rel);
     ix->h_rel = nullptr;
     ix->h_rel_cap = 0;
@@ -2340,6 +2392,9 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
         (void)(ix->dev.idx32 ? preload_walk_u32() : preload_walk_u64());
         (void)(ix->dev.idx32 ? preload_walkseg_u32() : preload_walkseg_u64());
         (void)hipGetLastError();
+        // movi_pml_device's mask words for a default batch (a bigger "reserve_device_masks" stays): its first call allocates nothing.
+        // No room is no failure -- an uncaptured call grows them, a captured one takes the packer route
+        if (grow_dmask(ix, (size_t)pml_mask_words(kPrepareMaskReads, kPrepareMaskBases, 0) * 4) != hipSuccess) (void)hipGetLastError();
     }
     if (what & MOVI_PREPARE_COUNT) {
         const int rc = ensure_count_tables(ix, s, true);

@@ -141,7 +141,7 @@ void expand_reads(const ExpandJob &j) {
 }
 
 // Worker threads of the expansion by default: three quarters of the CPUs the process may really use -- its affinity mask capped by the
-// cgroup's CPU quota (the GPU boxes show 256 logical CPUs and grant 16) --, at most 32.  Not all of them: the calling thread drives the
+// cgroup's CPU quota (the GPU boxes show 256 logical CPUs and grant 16) --, at most 24.  Not all of them: the calling thread drives the
 // GPU pipeline beside the workers, and a cgroup that runs over its quota is throttled as a whole (16 workers on a quota of 16:
 // movi_pml_host 17.8 - 25 Gbases/s from run to run, 12 workers: 27; profiles/r06_mask_path.txt).
 int host_threads_default() {
