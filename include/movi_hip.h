@@ -16,6 +16,7 @@
  *   ReadProcessor::backward_search + compute_match_count  src/read_processor.cpp:610-620,1096-1175   movi_count_host / movi_count_device
  *   Classifier::classify (bins)     src/classifier.cpp:99-143           movi_classify_device / movi_pml_classify_device / movi_pml_classify_host
  *   MoveStructure::query_zml        src/move_structure_query.cpp:690-785  movi_zml_host / movi_zml_device
+ *   MoveStructure::query_mems  src/mem_finder.cpp:7-145  movi_mem_host / movi_mem_device
  *   MoveQuery::add_ml / matching_lens  include/move_query.hpp:26-38 (filled by process_char, src/read_processor.cpp:193-215)
  *                                                                       movi_pml_mask_device / movi_pml_mask_host (one reset bit per base)
  *                                                                       + movi_pml_expand_device / movi_pml_expand_host (bits -> u16 vector)
@@ -359,6 +360,64 @@ int movi_count_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *
 int movi_count_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets,
                     uint64_t n_reads, uint64_t *h_matched, uint64_t *h_count, uint8_t *h_read_err,
                     movi_query_stats_t *stats);
+
+/* ---- MEM finding (maximal exact matches) --------------------------------------- */
+
+/* `movi query --mem`: MoveStructure::query_mems (src/mem_finder.cpp:7-145).
+ *
+ * Terms.  Read P of length m; minimum length L (-l / --min-mem-length), L' = max(L, 1).  A base is illegal when
+ * desc.code_of[byte] == 0xFF (N, lower case, the separator '%', bytes >= 128: check_alphabet, move_structure.cpp:383-397).
+ * occ(X) = occurrences of X in the indexed text T (= MoveInterval::count); rc(X) = reverse complement (A<->T, C<->G).
+ *   bw[e] = the largest l such that P[e-l+1 .. e] has no illegal base and occ > 0 (a plain backward search);
+ *   fw[s] = the largest l such that P[s .. s+l) has no illegal base and occ(rc(P[s .. s+l))) > 0, cnt[s] = that occ
+ *           (a backward search over comp(P[s]), comp(P[s+1]), ...: forward_search_step, move_structure_search.cpp:336-338).
+ * The search (query_mem_bml, mem_finder.cpp:27-103, over those arrays; for L <= 1 the reference runs query_all_mems,
+ * :105-145, whose output on legal reads is this loop with L' = 1):
+ *     pos = 0
+ *     while pos + L' <= m:
+ *         w = pos + L' - 1
+ *         if bw[w] < L':  pos = w - bw[w] + 1; continue      # window absent: skip past the failing base
+ *         if fw[pos] < L': pos += 1; continue                # cannot happen on a text closed under rc
+ *         e = pos + fw[pos]
+ *         emit (start = pos, end = e, count = cnt[pos])      # end exclusive, as MoveQuery::add_mem
+ *         if e == m: break
+ *         pos = max(pos + 1, e - bw[e] + 1)                  # next left end (mem_finder.cpp:83-101)
+ * Closed texts: every index `movi build --separators` makes is closed under rc, and so is every single-record index.
+ * There the output is exactly the MEMs of length >= L', by increasing start:
+ *     { (s, s + fw[s], cnt[s]) : fw[s] >= L', s == 0 or fw[s-1] <= fw[s] }.
+ *
+ * Where this deviates from the reference:
+ *   1. Illegal bases are barriers in both directions: a MEM never contains one.  The reference is not well defined there
+ *      (forward_search_step('N') extends with complement('N') == 'A', utils.cpp:87-91; initialize_backward_search on an
+ *      illegal base indexes first_runs out of range).  On legal reads the two agree.
+ *   2. The reference checks --ftab-k against L (mem_finder.cpp:37-56), and with K > L its size_t / int32_t comparisons let
+ *      the left extension run past pos.  Here the answers depend neither on whether an interval table is used nor on its K.
+ *   3. On a text that is not closed under rc (a multi-record index built without --separators: its record junctions are
+ *      not rc-symmetric) the reference's bidirectional interval (extend_bidirectional, move_structure_search.cpp:66-120) is
+ *      meaningless and can throw "reverse complement might not be present" (:254-256).  The answer here is still the loop
+ *      above, each side computed by its own backward search.
+ *   4. count is the full 64-bit occ.  The reference's mem_t::count is uint16_t, filled by an implicit conversion
+ *      (move_query.hpp:42-49), so the reference prints count mod 2^16; the CLI prints that value (its output bytes match).
+ *
+ * Device layout: MEM j of read i is d_mems[offsets[i] + j] for j < d_n_mems[i] (a read has at most max(0, len - L' + 1)
+ * MEMs, so the buffer of offsets[n] entries holds them all; no prefix sum, no atomics, deterministic).  Slots past
+ * d_n_mems[i] are unspecified.  Buffers, offsets, d_read_err, d_read_order and the stream as for movi_count_device; a read
+ * that hits one of the reference's throws gets d_n_mems[i] = 0 and its error code.  The call uses the count query's derived
+ * tables (row-start checkpoints, interval table): after movi_index_prepare(MOVI_PREPARE_COUNT) it allocates and builds
+ * nothing and may be captured into a graph without a warm-up call.  movi_last_stats / movi_last_launch report on it. */
+typedef struct movi_mem { uint32_t start, end; uint64_t count; } movi_mem_t;    /* 16 bytes, end exclusive */
+
+int movi_mem_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                    uint32_t min_len, movi_mem_t *d_mems, uint32_t *d_n_mems, uint8_t *d_read_err,
+                    const uint32_t *d_read_order, void *stream);
+
+/* Host form, compact: h_n_mems[i] per read, and the MEMs of read 0, then read 1, ... in h_mems; *n_mems_total = their sum.
+ * mems_cap = offsets[n] - offsets[0] always suffices.  With a smaller cap and more MEMs than fit the call returns
+ * MOVI_ERR_ARG and still fills h_n_mems and *n_mems_total (h_mems is then incomplete).  Runs chunk by chunk, synchronously;
+ * each chunk is compacted on the device, so only the MEMs found cross the link. */
+int movi_mem_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint32_t min_len,
+                  uint32_t *h_n_mems, movi_mem_t *h_mems, uint64_t mems_cap, uint64_t *n_mems_total,
+                  uint8_t *h_read_err, movi_query_stats_t *stats);
 
 /* ---- page-locked host memory --------------------------------------------------- */
 

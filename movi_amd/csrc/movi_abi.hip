@@ -2443,4 +2443,139 @@ int movi_count_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_
     return run_host(overlapped, ix, h_bases, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest, 16);
 }
 
+// -------------------------------------------------------------------------- MEM
+
+static_assert(sizeof(movi_mem_t) == sizeof(MemOut) && sizeof(movi_mem_t) == 16, "movi_mem_t and MemOut differ");
+
+}  // extern "C"
+
+namespace {
+
+// complement codes of the handle's alphabet: byte c = code_of[complement(alphabet[c])], 0xFF where that base is not in it
+uint64_t complement_codes(const movi_index_desc_t &d) {
+    uint64_t comp = ~0ull;
+    for (uint32_t c = 0; c < d.alphabet_size && c < 8; c++) {
+        const uint8_t ch = d.alphabet[c];
+        const uint8_t cc = ch == 'A' ? 'T' : ch == 'T' ? 'A' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : 0;
+        const uint64_t v = cc ? d.code_of[cc] : 0xFFu;
+        comp &= ~(0xFFull << (8 * c));
+        comp |= v << (8 * c);
+    }
+    return comp;
+}
+
+int mem_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+               uint32_t min_len, movi_mem_t *d_mems, uint32_t *d_n_mems, uint8_t *d_read_err, const uint32_t *d_read_order,
+               hipStream_t s) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (n_reads == 0) return MOVI_OK;
+    if (!d_offsets || !d_n_mems || (n_bases && (!d_bases || !d_mems))) return fail(MOVI_ERR_ARG, "NULL device buffer");
+    if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
+    HIP_TRY(hipSetDevice(ix->device));
+    int rc = ensure_count_tables(ix, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(ix->d_stats, 0, sizeof(DevStats), s));
+    MemArgs a{};
+    a.comp = complement_codes(ix->desc);
+    a.min_len = min_len > 1u ? min_len : 1u;
+    HIP_TRY(launch_mem(ix->kmode, ix->dev, a, d_bases, d_offsets, n_reads, reinterpret_cast<MemOut *>(d_mems), d_n_mems,
+                       d_read_err, ix->d_stats, d_read_order, s, &ix->last_launch));
+    return MOVI_OK;
+}
+
+// movi_mem_host cuts its reads into chunks of about this many bases (at least kMemChunkReads reads, at most kMemMaxChunkBases):
+// the device layout stages 16 bytes per base, twice (kernel output and compacted MEMs).
+constexpr uint64_t kMemChunkBases = 1ull << 25;
+constexpr uint64_t kMemChunkReads = 1ull << 18;
+constexpr uint64_t kMemMaxChunkBases = 1ull << 27;
+
+}  // namespace
+
+extern "C" {
+
+int movi_mem_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                    uint32_t min_len, movi_mem_t *d_mems, uint32_t *d_n_mems, uint8_t *d_read_err,
+                    const uint32_t *d_read_order, void *stream) {
+    return mem_device(ix, d_bases, d_offsets, n_reads, n_bases, min_len, d_mems, d_n_mems, d_read_err, d_read_order,
+                      static_cast<hipStream_t>(stream));
+}
+
+int movi_mem_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint32_t min_len,
+                  uint32_t *h_n_mems, movi_mem_t *h_mems, uint64_t mems_cap, uint64_t *n_mems_total,
+                  uint8_t *h_read_err, movi_query_stats_t *stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_mems_total) *n_mems_total = 0;
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (n_reads == 0) return MOVI_OK;
+    if (!h_offsets || !h_n_mems || (h_offsets[n_reads] != h_offsets[0] && !h_bases) || (mems_cap && !h_mems))
+        return fail(MOVI_ERR_ARG, "NULL host buffer");
+    if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
+    HIP_TRY(hipSetDevice(ix->device));
+    void **d = ix->scratch;
+    size_t *cap = ix->scratch_cap;
+    std::vector<uint64_t> rel;
+    uint64_t total = 0, errors = 0;
+    bool overflow = false;
+    uint64_t first = 0;
+    while (first < n_reads) {
+        uint64_t last = first + 1;
+        while (last < n_reads) {
+            const uint64_t nb_next = h_offsets[last + 1] - h_offsets[first];
+            if (nb_next <= kMemChunkBases || (last - first < kMemChunkReads && nb_next <= kMemMaxChunkBases)) ++last;
+            else break;
+        }
+        const uint64_t nr = last - first, b0 = h_offsets[first], nb = h_offsets[last] - b0;
+        HIP_TRY(grow(&d[movi_index::kBases], &cap[movi_index::kBases], nb));
+        HIP_TRY(grow(&d[movi_index::kOffs], &cap[movi_index::kOffs], (nr + 1) * 8));
+        HIP_TRY(grow(&d[movi_index::kErr], &cap[movi_index::kErr], nr));
+        HIP_TRY(grow(&d[movi_index::kOut], &cap[movi_index::kOut], nb * sizeof(movi_mem_t)));
+        HIP_TRY(grow(&d[movi_index::kA], &cap[movi_index::kA], nr * 4));
+        HIP_TRY(grow(&d[movi_index::kB], &cap[movi_index::kB], (nr + 1) * 8));
+        rel.resize(nr + 1);
+        for (uint64_t i = 0; i <= nr; i++) rel[i] = h_offsets[first + i] - b0;
+        if (nb) HIP_TRY(hipMemcpy(d[movi_index::kBases], h_bases + b0, nb, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d[movi_index::kOffs], rel.data(), (nr + 1) * 8, hipMemcpyHostToDevice));
+        const uint64_t *d_offs = static_cast<const uint64_t *>(d[movi_index::kOffs]);
+        MemOut *d_out = static_cast<MemOut *>(d[movi_index::kOut]);
+        uint32_t *d_n = static_cast<uint32_t *>(d[movi_index::kA]);
+        uint64_t *d_first = static_cast<uint64_t *>(d[movi_index::kB]);
+        int rc = mem_device(ix, static_cast<const uint8_t *>(d[movi_index::kBases]), d_offs, nr, nb, min_len,
+                            reinterpret_cast<movi_mem_t *>(d_out), d_n, static_cast<uint8_t *>(d[movi_index::kErr]), nullptr, nullptr);
+        if (rc) return rc;
+        // compaction on the device: the per-read counts' prefix, then only the MEMs found come down
+        HIP_TRY(launch_mem_compact(d_out, d_offs, d_n, nr, d_first, nullptr, nullptr, true));
+        movi_query_stats_t st{};
+        rc = movi_last_stats(ix, nullptr, &st);
+        if (rc) return rc;
+        uint64_t found = 0;
+        HIP_TRY(hipMemcpy(h_n_mems + first, d_n, nr * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&found, d_first + nr, 8, hipMemcpyDeviceToHost));
+        if (!overflow && total + found <= mems_cap) {
+            if (found) {
+                HIP_TRY(grow(&d[movi_index::kS], &cap[movi_index::kS], found * sizeof(movi_mem_t)));
+                MemOut *d_comp = static_cast<MemOut *>(d[movi_index::kS]);
+                HIP_TRY(launch_mem_compact(d_out, d_offs, d_n, nr, d_first, d_comp, nullptr, false));
+                HIP_TRY(hipMemcpy(h_mems + total, d_comp, found * sizeof(movi_mem_t), hipMemcpyDeviceToHost));
+            }
+        } else overflow = true;
+        if (h_read_err) HIP_TRY(hipMemcpy(h_read_err + first, d[movi_index::kErr], nr, hipMemcpyDeviceToHost));
+        total += found;
+        errors += st.errors;
+        if (stats) {
+            st.bases = nb;
+            DevStats h{};
+            h.fast_forwards = st.fast_forwards; h.scans = st.scans; h.repositions = st.repositions; h.errors = st.errors;
+            h.lane_steps = st.lane_steps; h.wave_steps = st.wave_steps; h.segments = st.segments; h.rewalked = st.rewalked;
+            add_stats(stats, nb, h);
+        }
+        first = last;
+    }
+    if (n_mems_total) *n_mems_total = total;
+    if (overflow)
+        return fail(MOVI_ERR_ARG, std::to_string(total) + " MEMs found, mems_cap is " + std::to_string(mems_cap));
+    if (errors)
+        return fail(MOVI_ERR_INVARIANT, std::to_string(errors) + " read(s) hit a move-structure invariant violation (corrupt index?)");
+    return MOVI_OK;
+}
+
 }  // extern "C"

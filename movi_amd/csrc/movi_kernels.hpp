@@ -345,6 +345,21 @@ hipError_t tally_no_ff_share(int kmode, const DevIndex &ix, uint64_t stride, uns
 // Fills the 4^K entries of the count query's interval table (DevIndex::ftab); mode = resident layout (6 or 3).
 hipError_t build_ftab(int mode, const DevIndex &ix, uint32_t K, uint4 *d_table, hipStream_t stream);
 
+// MEM finding (movi_walk_mem.hip; MoveStructure::query_mems, src/mem_finder.cpp:7-145).  MemOut is movi_mem_t.
+struct MemOut { uint32_t start, end; uint64_t count; };
+struct MemArgs {
+    uint64_t comp;       // byte c: code of the complement of the base of code c, 0xFF = not in the alphabet
+    uint32_t min_len;    // L' = max(L, 1)
+    uint32_t pad_;
+};
+hipError_t launch_mem(int mode, const DevIndex &ix, const MemArgs &a, const uint8_t *d_bases, const uint64_t *d_offsets,
+                      uint64_t n_reads, MemOut *d_mems, uint32_t *d_n_mems, uint8_t *d_err, DevStats *d_stats,
+                      const uint32_t *d_order, hipStream_t stream, LaunchInfo *info);
+// The host path's compaction: scan_only -> d_first[0..n] = exclusive prefix of d_n_mems (d_first[n] = total); else every read's
+// MEMs from d_mems[offs[i]..] to d_out[d_first[i]..].
+hipError_t launch_mem_compact(const MemOut *d_mems, const uint64_t *d_offsets, const uint32_t *d_n_mems, uint64_t n_reads,
+                              uint64_t *d_first, MemOut *d_out, hipStream_t stream, bool scan_only);
+
 // Fills ckpt[j] = BWT position of row (j << kPrefixShift), j = 0 .. ceil(r/32).
 hipError_t build_row_start_ckpt(int mode, const uint8_t *d_rows, uint64_t r, uint64_t *d_ckpt,
                                 hipStream_t stream);

@@ -5,6 +5,7 @@ Reference seam (file:line under /root/reference) -> here:
   MoveStructure::query_pml(MoveQuery&) src/move_structure_query.cpp:234   -> MoveIndex.query_pml
   ReadProcessor::process_latency_hiding src/read_processor.cpp:641        -> MoveIndex.query_pml (batched)
   MoveStructure::query_backward_search src/move_structure_search.cpp:340  -> MoveIndex.query_count
+  MoveStructure::query_mems           src/mem_finder.cpp:7-145           -> MoveIndex.query_mems
 
 All compute happens in libmovi_hip.so on the GPU; this file only marshals
 buffers.  Errors are MoviError (the reference throws std::runtime_error).
@@ -14,6 +15,10 @@ import ctypes as C
 import numpy as np
 
 from ._lib import IndexDescC, LaunchInfoC, QueryStatsC, check, lib
+
+
+# movi_mem_t: one maximal exact match, end exclusive; count = occurrences of the match's reverse complement (64 bits)
+MEM_DTYPE = np.dtype([("start", np.uint32), ("end", np.uint32), ("count", np.uint64)])
 
 
 class IndexDesc:
@@ -318,6 +323,37 @@ class MoveIndex:
         m, c, _ = self.query_count_packed(bases, offs)
         return [(int(m[i]), int(c[i])) for i in range(len(reads))]
 
+    def query_mems_packed(self, bases, offs, min_len, want_err=False):
+        """movi_mem_host -> (n_mems, mems, QueryStats[, per-read error bytes, return code]); mems is a structured array
+        (MEM_DTYPE: start, end, count), compact: the MEMs of read 0, then read 1, ..."""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        n = offs.size - 1
+        cap = int(offs[-1] - offs[0]) if n > 0 else 0
+        nm = np.zeros(max(n, 1), np.uint32)
+        mems = np.zeros(max(cap, 1), MEM_DTYPE)
+        err = np.zeros(max(n, 1), np.uint8)
+        total = C.c_uint64(0)
+        st = QueryStatsC()
+        rc = lib().movi_mem_host(self._h, bases.ctypes.data, offs.ctypes.data, n, int(min_len), nm.ctypes.data,
+                                 mems.ctypes.data, cap, C.byref(total), err.ctypes.data if want_err else None, C.byref(st))
+        out = mems[:total.value]
+        if want_err:
+            return nm[:n], out, QueryStats(st), err[:n], rc
+        check(rc)
+        return nm[:n], out, QueryStats(st)
+
+    def query_mems(self, reads, min_len):
+        """query_mems per read: list of [(start, end, count), ...] (end exclusive, count = full 64-bit occ)."""
+        bases, offs = _pack_reads(reads)
+        nm, mems, _ = self.query_mems_packed(bases, offs, min_len)
+        out, k = [], 0
+        for i in range(len(reads)):
+            c = int(nm[i])
+            out.append([(int(x["start"]), int(x["end"]), int(x["count"])) for x in mems[k:k + c]])
+            k += c
+        return out
+
     # -- device-pointer queries (bench / torch interop) ---------------------------
     def pml_device(self, d_bases, d_offs, n_reads, n_bases, d_out, d_err=0, stream=0, d_order=0):
         check(lib().movi_pml_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offs), n_reads, n_bases,
@@ -358,6 +394,14 @@ class MoveIndex:
                                       C.c_void_p(d_err) if d_err else None,
                                       C.c_void_p(d_order) if d_order else None,
                                       C.c_void_p(stream) if stream else None))
+
+    def mem_device(self, d_bases, d_offs, n_reads, n_bases, min_len, d_mems, d_n_mems, d_err=0, stream=0, d_order=0):
+        """movi_mem_device: MEM j of read i at d_mems[offs[i] + j] (16 bytes each), j < d_n_mems[i]."""
+        check(lib().movi_mem_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offs), n_reads, n_bases, int(min_len),
+                                    C.c_void_p(d_mems), C.c_void_p(d_n_mems),
+                                    C.c_void_p(d_err) if d_err else None,
+                                    C.c_void_p(d_order) if d_order else None,
+                                    C.c_void_p(stream) if stream else None))
 
     PREPARE_PML, PREPARE_COUNT, PREPARE_ZML = 1, 2, 4
 

@@ -204,6 +204,8 @@ struct Job {
     MlBuf pml;                                                        // PML / ZML values, emission order per read
     std::vector<uint16_t> log_ff, log_scan;                           // --logs: per-base fast-forwards / scan rows
     std::vector<uint64_t> matched, counts;                            // --count
+    std::vector<uint32_t> n_mems;                                     // --mem: MEMs per read ...
+    std::vector<movi_mem_t> mems;                                     // ... and all of them, read by read (file order)
     std::vector<uint8_t> err;                                         // per-read error byte
     RawBytes original;                                                // reads as given (--filter after --ignore-illegal-chars 1)
     std::vector<uint32_t> bins_above, bins_below;                     // verdict-only classification
@@ -360,6 +362,9 @@ int run_query(const Options &o) {
         std::cerr << "[movi] --ahead-rows 1 is ignored with --zml: the ZML parse walks on the plain rows (the engine's \"zml_ahead\" option is opt-in and no faster).\n";
     if (o.ahead_rows >= 0 && !(o.zml && o.ahead_rows == 1))
         for (auto *hd : handles) check(movi_set_option(hd, "ahead_rows", o.ahead_rows), "--ahead-rows");
+    // --ftab-k K: the engine's interval table at min(K, 12) -- speed only, never answers (an index outside its scope keeps none)
+    if (o.ftab_k >= 0)
+        for (auto *hd : handles) (void)movi_set_option(hd, "ftab_k", std::min<long>(o.ftab_k, 12));
     if (pin_chunks)
         for (auto *hd : handles) check(movi_set_option(hd, "host_overlap", 0), "host_overlap");
     // (the command's own pipeline keeps the host's cores busy -- parser pool, record order, BPF gather and write --: the PML vector comes
@@ -375,7 +380,7 @@ int run_query(const Options &o) {
     // 14 M-row index hides and a 1 B-row one does not (bench.py big_table.cli_path: 0.31 s of "processing" for 0.03 s of work).
     for (auto *hd : handles) {                                         // (errors here are not the query's: the real calls report)
         if (o.pml && o.logs) continue;                                 // --logs runs on the first kernel, which uses none of the derived tables
-        (void)movi_index_prepare(hd, o.pml ? MOVI_PREPARE_PML : (o.zml ? MOVI_PREPARE_ZML : MOVI_PREPARE_COUNT), nullptr, nullptr);
+        (void)movi_index_prepare(hd, o.pml ? MOVI_PREPARE_PML : (o.zml ? MOVI_PREPARE_ZML : MOVI_PREPARE_COUNT), nullptr, nullptr);   // (--mem: the count tables)
         // ... and so is the device staging of a chunk's host call (three hipMallocs: 1.2 ms of the first chunk's 3 ms call otherwise):
         // a chunk's bases with the slack of its last batch, its result vector when one comes back, reads down to 64 bases long
         const int64_t cb = (int64_t)std::min<uint64_t>(chunk_bases + (chunk_bases >> 3), 1ull << 31) / (o.gpus > 0 ? o.gpus : 1);
@@ -422,10 +427,14 @@ int run_query(const Options &o) {
     const bool open_files = (!o.write_stdout || o.classify) && o.write_output_allowed();
     if (open_files) {
         std::string prefix = !o.out_file.empty() ? o.out_file : o.read_file + "." + index_type;
-        prefix += "." + o.query_type();
-        if (o.ml()) {
+        if (o.mem) {                                                  // <out_file or reads.<index type>>.mems
+            matches_file.open(prefix + ".mems");
+            if (!matches_file.good()) throw std::runtime_error("Failed to open the output file: " + prefix + ".mems");
+        } else if (o.ml()) {
+            prefix += "." + o.query_type();
             mls_file.open(prefix + ".bpf", 16);
         } else {
+            prefix += "." + o.query_type();
             matches_file.open(prefix + ".matches");
             if (!matches_file.good()) throw std::runtime_error("Failed to open the output file: " + prefix + ".matches");
         }
@@ -573,6 +582,13 @@ int run_query(const Options &o) {
         }
         std::string count_txt;
         if (!o.ml() && o.write_output_allowed()) count_txt.reserve(n * 32);
+        if (o.mem) {                                                  // output_mems, src/utils.cpp:306-316 (file order: no prefetch)
+            std::vector<uint64_t> first(n + 1, 0);
+            for (size_t i = 0; i < n; i++) first[i + 1] = first[i] + job.n_mems[i];
+            for (uint32_t i : order)
+                for (uint64_t k = first[i]; k < first[i + 1]; k++) append_mem_line(count_txt, rs.id(i), job.mems[k]);
+            order.clear();
+        }
         for (uint32_t i : order) {
             const uint64_t len = rs.len(i);
             if (o.ml()) {
@@ -665,6 +681,12 @@ int run_query(const Options &o) {
                 (void)movi_pml_classify_host(hd, wb, wo, 1, (uint32_t)o.bin_width, classifier.max_value_thr, &wa, &wbl, &wsum, &we, nullptr);
             else if (o.pml) (void)movi_pml_host(hd, wb, wo, 1, wp, &we, nullptr);
             else if (o.zml) (void)movi_zml_host(hd, wb, wo, 1, wp, &we, nullptr);
+            else if (o.mem) {
+                uint32_t wn = 0;
+                uint64_t wt = 0;
+                movi_mem_t wmem[32];
+                (void)movi_mem_host(hd, wb, wo, 1, o.min_mem_length, &wn, wmem, 32, &wt, &we, nullptr);
+            }
             else (void)movi_count_host(hd, wb, wo, 1, &wm, &wc, &we, nullptr);
         }
     }
@@ -698,9 +720,11 @@ int run_query(const Options &o) {
         if (logs) { job.log_ff.resize(rs.bases.size()); job.log_scan.resize(rs.bases.size()); }
         job.matched.assign(o.count ? n : 0, 0);
         job.counts.assign(o.count ? n : 0, 0);
+        job.n_mems.assign(o.mem ? n : 0, 0);
         job.err.assign(n, 0);
         const std::vector<size_t> sb = shard_bounds(rs, o.gpus);
         std::vector<std::string> errors((size_t)o.gpus);
+        std::vector<std::vector<movi_mem_t>> mem_shard(o.mem ? (size_t)o.gpus : 0);
         auto tg = std::chrono::steady_clock::now();
         auto work = [&](int g) {
             const size_t a = sb[g], b = sb[g + 1];
@@ -719,6 +743,20 @@ int run_query(const Options &o) {
             else if (o.zml)
                 rc = movi_zml_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, walk_only ? nullptr : job.pml.data(),
                                    job.err.data() + a, nullptr);
+            else if (o.mem) {
+                // room for a few MEMs per read first; a shard that finds more is run again with room for exactly what it found
+                std::vector<movi_mem_t> &v = mem_shard[(size_t)g];
+                uint64_t cap = (b - a) * 8 + (rs.offsets[b] - rs.offsets[a]) / 16, total = 0;
+                v.resize(cap);
+                rc = movi_mem_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, o.min_mem_length, job.n_mems.data() + a,
+                                   v.data(), cap, &total, job.err.data() + a, nullptr);
+                if (rc == MOVI_ERR_ARG && total > cap) {
+                    v.resize(total);
+                    rc = movi_mem_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, o.min_mem_length,
+                                       job.n_mems.data() + a, v.data(), total, &total, job.err.data() + a, nullptr);
+                }
+                v.resize(rc == MOVI_OK ? total : 0);
+            }
             else
                 rc = movi_count_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, job.matched.data() + a,
                                      job.counts.data() + a, job.err.data() + a, nullptr);
@@ -734,6 +772,10 @@ int run_query(const Options &o) {
         { const double dtg = std::chrono::duration<double>(std::chrono::steady_clock::now() - tg).count(); gpu_seconds += dtg; if (chunk_gpu_s.size() < 64) chunk_gpu_s.push_back(dtg); }
         for (const auto &e : errors)
             if (!e.empty()) throw EngineError(e);
+        if (o.mem) {                                                  // the shards' MEMs in read order
+            job.mems.clear();
+            for (auto &v : mem_shard) job.mems.insert(job.mems.end(), v.begin(), v.end());
+        }
         reads_done += n;
         bases_done += rs.bases.size();
         done_q.push(jp);

@@ -58,8 +58,10 @@ long to_int(const std::string &name, const std::string &v) {
 
 std::string usage() {
     return "movi (MI355X engine): movi query -i DIR -r FILE|- [-o PREFIX] [--pml|--zml|--count] [--classify] [--filter [-v]]\n"
-           "                      [--stdout] [--no-output] [-s N] [-t N] [-n] [--reverse] [--bin-width N]\n"
+           "                      [--stdout] [--no-output] [-s N] [-t N] [-n] [--reverse] [--bin-width N] [--ftab-k K]\n"
            "                      [--ignore-illegal-chars 1] [--gpus N] [--device D] [--seg-len N] [--ahead-rows 0|1] [--verbose]\n"
+           "       movi query -i DIR -r FILE|- --mem --ftab-k K [-l MIN_MEM_LENGTH] [-o PREFIX] [--stdout] [--no-output]\n"
+           "                      [--reverse] [--ignore-illegal-chars 1] [--gpus N] [--device D]\n"
            "       movi view --bpf FILE\n"
            "       movi null -i DIR [--gen-reads -f REF.fasta] [--pml|--zml]\n"
            "       movi build -i DIR -f REF.fasta [--type regular-thresholds|blocked-thresholds|sampled-thresholds|regular|blocked|sampled]\n"
@@ -118,20 +120,30 @@ Options parse_args(int argc, char **argv) {
         o.index_dir = val("index");
         o.read_file = val("read");
         if (has("out-file")) o.out_file = val("out-file");
-        for (const char *bad : {"mem", "rpml", "kmer", "kmer-count", "sa-entries", "multi-classify", "ftab-k",
-                                "multi-ftab"})
+        for (const char *bad : {"rpml", "kmer", "kmer-count", "sa-entries", "multi-classify", "multi-ftab"})
             if (has(bad))
-                throw UsageError(std::string("--") + bad + " is not supported by the MI355X engine (PML, ZML and count queries "
-                                 "on regular-thresholds / blocked-thresholds indexes only)");
+                throw UsageError(std::string("--") + bad + " is not supported by the MI355X engine (PML, ZML, count and MEM "
+                                 "queries only)");
         // --mmap (src/movi_parser.cpp: "Use memory mapping to read the index") is accepted and implied: movi_index_load
         // always maps the file and uploads the rows straight from the page cache
                 if (has("bin-width")) o.bin_width = (size_t)to_int("bin-width", val("bin-width"));
         // movi_parser.cpp:353-355 applies set_count, set_zml, set_pml in this order and each setter
         // clears the other query types (movi_options.hpp:108-110), so the last one applied wins
         // (the "only specify count or pml" check at :407-410 can never fire)
-        if (has("count")) { o.count = true; o.pml = false; o.zml = false; }
-        if (has("zml")) { o.zml = true; o.pml = false; o.count = false; }
-        if (has("pml")) { o.pml = true; o.count = false; o.zml = false; }
+        // (set_mem comes first, :352: --mem followed by --count, --zml or --pml is that other query)
+        if (has("mem")) { o.mem = true; o.pml = false; o.count = false; o.zml = false; }
+        if (has("count")) { o.count = true; o.pml = false; o.zml = false; o.mem = false; }
+        if (has("zml")) { o.zml = true; o.pml = false; o.count = false; o.mem = false; }
+        if (has("pml")) { o.pml = true; o.count = false; o.zml = false; o.mem = false; }
+        if (has("min-mem-length")) {
+            const long v = to_int("min-mem-length", val("min-mem-length"));
+            if (v < 0 || v > 0xFFFFFFFFl) throw UsageError("Argument '" + val("min-mem-length") + "' failed to parse for option 'min-mem-length'");
+            o.min_mem_length = (uint32_t)v;
+        }
+        if (has("ftab-k")) {
+            o.ftab_k = to_int("ftab-k", val("ftab-k"));
+            if (o.ftab_k < 0) throw UsageError("Argument '" + val("ftab-k") + "' failed to parse for option 'ftab-k'");
+        }
         o.classify = has("classify");
         o.filter = has("filter");
         if (o.filter) o.classify = true;                          // set_filter(), movi_options.hpp:122-125
@@ -160,6 +172,13 @@ Options parse_args(int argc, char **argv) {
         }
         if (o.gpus < 1) throw UsageError("--gpus must be >= 1");
         if (o.classify && o.count) throw UsageError("--classify needs PML or ZML queries");
+        if (o.mem) {                                              // src/movi.cpp:235-247
+            if (o.classify || o.logs) throw UsageError("--mem cannot be combined with --classify, --filter or --logs");
+            if (o.ftab_k <= 0)
+                throw UsageError("MEM finding requires ftab. Please build the ftab using the ./movi ftab --ftab-k <k>, then pass "
+                                 "--ftab-k <k> to the query step. (MEM finding without --ftab-k is not supported.)");
+            o.prefetch = false;                                   // MEM finding does not support prefetching: file order
+        }
     } else if (o.command == "plan") {
         // host-only helper (no GPU): prints how the reads are batched and in which order
         // their records will be emitted, one `batch<TAB>id<TAB>length` line per read.

@@ -22,6 +22,9 @@ struct Options {
     bool pml = true;              // default query type (movi_options.hpp:243)
     bool count = false;
     bool zml = false;             // --zml: Ziv-Merhav cross parse lengths, same outputs as PML
+    bool mem = false;             // --mem: maximal exact matches (src/mem_finder.cpp), one line per MEM
+    uint32_t min_mem_length = 25; // -l / --min-mem-length (movi_options.hpp:255)
+    long ftab_k = -1;             // --ftab-k K: the engine's interval table at min(K, 12) ("ftab_k"); -1 = not given
     bool classify = false;
     bool filter = false;
     bool invert = false;
@@ -47,7 +50,7 @@ struct Options {
     bool write_output_allowed() const { return !no_output && !filter; }
     bool write_stdout_enabled() const { return write_stdout && !classify; }
     bool ml() const { return pml || zml; }                                // per-base matching lengths
-    std::string query_type() const { return count ? "count" : (zml ? "zml" : "pml"); }   // src/utils.cpp:47-67
+    std::string query_type() const { return mem ? "mem" : count ? "count" : (zml ? "zml" : "pml"); }   // src/utils.cpp:47-67
 };
 
 struct UsageError : std::runtime_error {

@@ -327,6 +327,24 @@ void write_count_line(std::ostream &out, std::string_view id, uint64_t query_len
     out << id << "\t" << matched << "/" << query_length << "\t" << count << "\n";
 }
 
+// output_mems, src/utils.cpp:306-316: `id<TAB>start<TAB>end<TAB>count` -- count as the reference's mem_t holds it, a uint16_t
+// (move_query.hpp:42-49: the 64-bit occurrence count modulo 2^16)
+void append_mem_line(std::string &txt, std::string_view id, const movi_mem_t &m) {
+    char num[24];
+    auto put = [&](uint64_t v) {
+        const auto r = std::to_chars(num, num + sizeof(num), v);
+        txt.append(num, (size_t)(r.ptr - num));
+    };
+    txt.append(id.data(), id.size());
+    txt.push_back('\t');
+    put(m.start);
+    txt.push_back('\t');
+    put(m.end);
+    txt.push_back('\t');
+    put((uint16_t)m.count);
+    txt.push_back('\n');
+}
+
 void append_count_line(std::string &txt, std::string_view id, uint64_t query_length, uint64_t matched, uint64_t count) {
     char num[24];
     auto put = [&](uint64_t v) {
