@@ -17,6 +17,7 @@
  *   Classifier::classify (bins)     src/classifier.cpp:99-143           movi_classify_device / movi_pml_classify_device / movi_pml_classify_host
  *   MoveStructure::query_zml        src/move_structure_query.cpp:690-785  movi_zml_host / movi_zml_device
  *   MoveStructure::query_mems  src/mem_finder.cpp:7-145  movi_mem_host / movi_mem_device
+ *   MoveStructure::query_all_kmers  src/sequitur.cpp:322-421  movi_kmer_host / movi_kmer_device
  *   MoveQuery::add_ml / matching_lens  include/move_query.hpp:26-38 (filled by process_char, src/read_processor.cpp:193-215)
  *                                                                       movi_pml_mask_device / movi_pml_mask_host (one reset bit per base)
  *                                                                       + movi_pml_expand_device / movi_pml_expand_host (bits -> u16 vector)
@@ -419,6 +420,59 @@ int movi_mem_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_of
                   uint32_t *h_n_mems, movi_mem_t *h_mems, uint64_t mems_cap, uint64_t *n_mems_total,
                   uint8_t *h_read_err, movi_query_stats_t *stats);
 
+/* ---- k-mer presence ------------------------------------------------------------- */
+
+/* `movi query --kmer [-k K]`: MoveStructure::query_all_kmers / query_kmers_from (src/sequitur.cpp:257-421, the non-count
+ * branch) over initialize_backward_search / try_ftab / backward_search (src/move_structure_search.cpp:169-293).
+ *
+ * Terms.  Read P of length m, k >= 1.  Illegal bases and bw[] as for MEM finding above: bw[e] = the largest l such that
+ * P[e-l+1 .. e] has no illegal base and occurs in the indexed text.  The k-mer starting at p (ending at e = p + k - 1) is
+ * *found* iff bw[e] >= k.  The reference's walk, with every skipping rule taken out (none of them changes the answer):
+ *     e = m - 1
+ *     while e >= k - 1:
+ *         if bw[e] < k:  e -= 1;  continue
+ *         L = e - bw[e] + 1
+ *         emit run (start = L, count = bw[e] - k + 1)        # the k-mers starting at L, L + 1, ..., L + count - 1
+ *         e = L + k - 2
+ *     found = sum of the counts = #{ p : the k-mer at p is found };   all = m - k + 1
+ * Runs come out by decreasing start (the order of the reference's "pos:count " string, MoveQuery::add_kmer,
+ * include/move_query.hpp:12-19).  A run is greedy, not maximal: it is the longest match ending at the first found end met
+ * from the right, and the k-mer ending at L + k - 2 may be found again and start the next run.  The runs of a read are
+ * disjoint and cover exactly the found k-mers.
+ *
+ * Where this deviates from the reference:
+ *   1. Illegal bases are barriers.  A read that is empty, all illegal, or whose cursor would run off its left end simply
+ *      ends with the runs found so far; the reference reads out of bounds there (query_seq[-1]; the int32_t against size_t
+ *      comparison in `while (pos_on_r >= k - 1)`).
+ *   2. --ftab-k >= k makes the reference's look-ahead step negative and its ftab skip wrong.  Here the answers depend
+ *      neither on whether an interval table is used, nor on its K, nor on which dead ends the kernel skips ("kmer_lookahead").
+ *   3. k = 1 follows the loop above (runs = the stretches of legal bases that occur).  The reference special-cases k = 1 and
+ *      emits nothing.
+ *   4. `all` is not returned: the caller computes m - k + 1 (the reference does so in 64-bit unsigned arithmetic, so a read
+ *      shorter than k prints the wrapped value; the CLI prints that).  k = 0 is MOVI_ERR_ARG.
+ *
+ * Device layout: run j of read i is d_runs[offsets[i] + j] for j < d_n_runs[i] (a read has at most max(0, len - k + 1) runs,
+ * so the buffer of offsets[n] entries holds them all; no prefix sum, no atomics, deterministic).  Slots past d_n_runs[i] are
+ * unspecified.  d_found[i] = the read's found k-mers (d_found may be NULL).  Buffers, offsets, d_read_err, d_read_order and
+ * the stream as for movi_mem_device; a read that hits one of the reference's throws gets d_n_runs[i] = d_found[i] = 0 and its
+ * error code.  The call uses the count query's derived tables: after movi_index_prepare(MOVI_PREPARE_COUNT) it allocates and
+ * builds nothing and may be captured into a graph without a warm-up call.  movi_last_stats / movi_last_launch report on it
+ * (lane_steps = backward-search steps taken, wave_steps = iterations of the wavefronts: what a skipping policy is judged by). */
+typedef struct movi_kmer_run { uint32_t start, count; } movi_kmer_run_t;      /* 8 bytes */
+
+int movi_kmer_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                     uint32_t k, movi_kmer_run_t *d_runs, uint32_t *d_n_runs, uint32_t *d_found, uint8_t *d_read_err,
+                     const uint32_t *d_read_order, void *stream);
+
+/* Host form, compact: h_n_runs[i] and h_found[i] (may be NULL) per read, and the runs of read 0, then read 1, ... in h_runs;
+ * *n_runs_total = their number.  runs_cap = offsets[n] - offsets[0] always suffices.  With a smaller cap and more runs than
+ * fit the call returns MOVI_ERR_ARG and still fills h_n_runs, h_found and *n_runs_total (h_runs is then incomplete).  Runs
+ * chunk by chunk, synchronously; each chunk is compacted on the device, so only the runs found cross the link.  A read that
+ * hits an invariant violation makes the call return MOVI_ERR_INVARIANT (its h_n_runs[i] is 0). */
+int movi_kmer_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint32_t k,
+                   uint32_t *h_n_runs, uint32_t *h_found, movi_kmer_run_t *h_runs, uint64_t runs_cap, uint64_t *n_runs_total,
+                   movi_query_stats_t *stats);
+
 /* ---- page-locked host memory --------------------------------------------------- */
 
 /* The reference keeps reads and results in std::string / std::vector of its MoveQuery objects
@@ -498,6 +552,12 @@ int movi_host_unregister(void *p);
  * "classify_fused" (movi_pml_classify_device with a PML vector: -1, the default: reads of mean length >= 1024 are walked
  * first and their bins reduced from the resident vectors by a wavefront per read -- faster than bins fused into the walk
  * there --, shorter ones fused; 1 = always fused, 0 = always two passes),
+ * "kmer_lookahead" (the k-mer query's skipping of dead ends.  Before an end whose window holds the base the last search died
+ * on, the window's left part is tried first, from at most `step` bases left of the end and never left of that base -- the
+ * reference's look-ahead, src/sequitur.cpp:339-370, taken only where it is likely to die.  -1, the default: step = min(k / 2,
+ * k - (log4(text length) + 2)), none when k is shorter than that -- a look shorter than log4(n) + 2 bases mostly passes and is
+ * wasted; n in [2, 16]: step = k / n (3 = the reference's); 0 = every end searched from its own base.  Never changes an
+ * answer: A/B, profiles/kmer_bench.txt),
  * "zml_ahead" (1: the ZML parse walks on the look-ahead rows where they exist -- a third fewer iterations, no faster: off
  * by default),
  * "pml_via_mask" (round 6; PML as reset masks.  movi_pml_device: the walk writes one bit per base and every wavefront expands its reads'

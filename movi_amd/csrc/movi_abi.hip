@@ -1220,6 +1220,11 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
         if (!ftab_eligible(ix)) return fail(MOVI_ERR_ARG, "the count query's interval table serves DNA (ACGT) indexes only");
         return build_ftab_table(ix, (uint32_t)value, nullptr);
     }
+    if (!strcmp(key, "kmer_lookahead")) {                    // k-mer query: -1 = by k and the text's length, 0 = no look-ahead, n in [2, 16] = split k / n
+        if (value != 0 && value != -1 && (value < 2 || value > 16)) return fail(MOVI_ERR_ARG, "kmer_lookahead must be -1, 0 or in [2, 16]");
+        ix->cfg.kmer_lookahead = (int)value;
+        return MOVI_OK;
+    }
     if (!strcmp(key, "waves_per_cu")) {
         if (value < 0 || value > 32) return fail(MOVI_ERR_ARG, "waves_per_cu must be in [0,32]");
         ix->cfg.waves_per_cu = (int)value;
@@ -2573,6 +2578,141 @@ int movi_mem_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_of
     if (n_mems_total) *n_mems_total = total;
     if (overflow)
         return fail(MOVI_ERR_ARG, std::to_string(total) + " MEMs found, mems_cap is " + std::to_string(mems_cap));
+    if (errors)
+        return fail(MOVI_ERR_INVARIANT, std::to_string(errors) + " read(s) hit a move-structure invariant violation (corrupt index?)");
+    return MOVI_OK;
+}
+
+// -------------------------------------------------------------------------- k-mers
+
+static_assert(sizeof(movi_kmer_run_t) == sizeof(KmerRun) && sizeof(movi_kmer_run_t) == 8, "movi_kmer_run_t and KmerRun differ");
+
+}  // extern "C"
+
+namespace {
+
+// The look-ahead's split for this k ("kmer_lookahead").  A look takes the k - step left bases of a window and pays only if it
+// dies; a window that holds a substituted base still occurs by chance with probability ~ n / 4^length, so a look shorter than
+// log4(n) + 2 bases (chance 1/16) mostly passes and is wasted: -1 picks step = min(k / 2, k - that length), none if k is too short
+// (measured, profiles/kmer_bench.txt: at k = 31 on a 640 Mbase text the split k / 2 beats k / 3 and no look-ahead by 1.6x and
+// 2.5x; at k = 15 any look-ahead is 1.9 - 2.2x slower than none).
+uint32_t kmer_look_step(uint32_t k, uint64_t n, int policy) {
+    if (policy == 0) return 0u;
+    if (policy > 0) return k / (uint32_t)policy;
+    uint32_t need = 2;                                   // ceil(log4(n)) + 2
+    for (uint64_t v = 1; v < n && need < 64; v <<= 2) need += 1;
+    if (k <= need) return 0u;
+    return std::min(k / 2u, k - need);
+}
+
+int kmer_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t k,
+                movi_kmer_run_t *d_runs, uint32_t *d_n_runs, uint32_t *d_found, uint8_t *d_read_err, const uint32_t *d_read_order,
+                hipStream_t s) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (k == 0) return fail(MOVI_ERR_ARG, "k must be at least 1");
+    if (n_reads == 0) return MOVI_OK;
+    if (!d_offsets || !d_n_runs || (n_bases && (!d_bases || !d_runs))) return fail(MOVI_ERR_ARG, "NULL device buffer");
+    if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
+    HIP_TRY(hipSetDevice(ix->device));
+    int rc = ensure_count_tables(ix, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(ix->d_stats, 0, sizeof(DevStats), s));
+    KmerArgs a{};
+    a.k = k;
+    a.step = kmer_look_step(k, ix->desc.length, ix->cfg.kmer_lookahead);
+    HIP_TRY(launch_kmer(ix->kmode, ix->dev, a, d_bases, d_offsets, n_reads, reinterpret_cast<KmerRun *>(d_runs), d_n_runs, d_found,
+                        d_read_err, ix->d_stats, d_read_order, s, &ix->last_launch));
+    return MOVI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int movi_kmer_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                     uint32_t k, movi_kmer_run_t *d_runs, uint32_t *d_n_runs, uint32_t *d_found, uint8_t *d_read_err,
+                     const uint32_t *d_read_order, void *stream) {
+    return kmer_device(ix, d_bases, d_offsets, n_reads, n_bases, k, d_runs, d_n_runs, d_found, d_read_err, d_read_order,
+                       static_cast<hipStream_t>(stream));
+}
+
+// (chunks as movi_mem_host cuts them: the device layout stages 8 bytes per base, twice)
+int movi_kmer_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint32_t k,
+                   uint32_t *h_n_runs, uint32_t *h_found, movi_kmer_run_t *h_runs, uint64_t runs_cap, uint64_t *n_runs_total,
+                   movi_query_stats_t *stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_runs_total) *n_runs_total = 0;
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (k == 0) return fail(MOVI_ERR_ARG, "k must be at least 1");
+    if (n_reads == 0) return MOVI_OK;
+    if (!h_offsets || !h_n_runs || (h_offsets[n_reads] != h_offsets[0] && !h_bases) || (runs_cap && !h_runs))
+        return fail(MOVI_ERR_ARG, "NULL host buffer");
+    if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
+    HIP_TRY(hipSetDevice(ix->device));
+    void **d = ix->scratch;
+    size_t *cap = ix->scratch_cap;
+    std::vector<uint64_t> rel;
+    uint64_t total = 0, errors = 0;
+    bool overflow = false;
+    uint64_t first = 0;
+    while (first < n_reads) {
+        uint64_t last = first + 1;
+        while (last < n_reads) {
+            const uint64_t nb_next = h_offsets[last + 1] - h_offsets[first];
+            if (nb_next <= kMemChunkBases || (last - first < kMemChunkReads && nb_next <= kMemMaxChunkBases)) ++last;
+            else break;
+        }
+        const uint64_t nr = last - first, b0 = h_offsets[first], nb = h_offsets[last] - b0;
+        HIP_TRY(grow(&d[movi_index::kBases], &cap[movi_index::kBases], nb));
+        HIP_TRY(grow(&d[movi_index::kOffs], &cap[movi_index::kOffs], (nr + 1) * 8));
+        HIP_TRY(grow(&d[movi_index::kErr], &cap[movi_index::kErr], nr));
+        HIP_TRY(grow(&d[movi_index::kOut], &cap[movi_index::kOut], nb * sizeof(movi_kmer_run_t)));
+        HIP_TRY(grow(&d[movi_index::kA], &cap[movi_index::kA], nr * 8));          // runs per read, then k-mers found per read
+        HIP_TRY(grow(&d[movi_index::kB], &cap[movi_index::kB], (nr + 1) * 8));
+        rel.resize(nr + 1);
+        for (uint64_t i = 0; i <= nr; i++) rel[i] = h_offsets[first + i] - b0;
+        if (nb) HIP_TRY(hipMemcpy(d[movi_index::kBases], h_bases + b0, nb, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d[movi_index::kOffs], rel.data(), (nr + 1) * 8, hipMemcpyHostToDevice));
+        const uint64_t *d_offs = static_cast<const uint64_t *>(d[movi_index::kOffs]);
+        KmerRun *d_out = static_cast<KmerRun *>(d[movi_index::kOut]);
+        uint32_t *d_n = static_cast<uint32_t *>(d[movi_index::kA]);
+        uint32_t *d_found = d_n + nr;
+        uint64_t *d_first = static_cast<uint64_t *>(d[movi_index::kB]);
+        int rc = kmer_device(ix, static_cast<const uint8_t *>(d[movi_index::kBases]), d_offs, nr, nb, k,
+                             reinterpret_cast<movi_kmer_run_t *>(d_out), d_n, d_found, static_cast<uint8_t *>(d[movi_index::kErr]),
+                             nullptr, nullptr);
+        if (rc) return rc;
+        // compaction on the device: the per-read counts' prefix, then only the runs found come down
+        HIP_TRY(launch_mem_compact(nullptr, d_offs, d_n, nr, d_first, nullptr, nullptr, true));
+        movi_query_stats_t st{};
+        rc = movi_last_stats(ix, nullptr, &st);
+        if (rc) return rc;
+        uint64_t got = 0;
+        HIP_TRY(hipMemcpy(h_n_runs + first, d_n, nr * 4, hipMemcpyDeviceToHost));
+        if (h_found) HIP_TRY(hipMemcpy(h_found + first, d_found, nr * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&got, d_first + nr, 8, hipMemcpyDeviceToHost));
+        if (!overflow && total + got <= runs_cap) {
+            if (got) {
+                HIP_TRY(grow(&d[movi_index::kS], &cap[movi_index::kS], got * sizeof(movi_kmer_run_t)));
+                KmerRun *d_comp = static_cast<KmerRun *>(d[movi_index::kS]);
+                HIP_TRY(launch_kmer_gather(d_out, d_offs, d_n, nr, d_first, d_comp, nullptr));
+                HIP_TRY(hipMemcpy(h_runs + total, d_comp, got * sizeof(movi_kmer_run_t), hipMemcpyDeviceToHost));
+            }
+        } else overflow = true;
+        total += got;
+        errors += st.errors;
+        if (stats) {
+            st.bases = nb;
+            DevStats h{};
+            h.fast_forwards = st.fast_forwards; h.scans = st.scans; h.repositions = st.repositions; h.errors = st.errors;
+            h.lane_steps = st.lane_steps; h.wave_steps = st.wave_steps; h.segments = st.segments; h.rewalked = st.rewalked;
+            add_stats(stats, nb, h);
+        }
+        first = last;
+    }
+    if (n_runs_total) *n_runs_total = total;
+    if (overflow)
+        return fail(MOVI_ERR_ARG, std::to_string(total) + " runs found, runs_cap is " + std::to_string(runs_cap));
     if (errors)
         return fail(MOVI_ERR_INVARIANT, std::to_string(errors) + " read(s) hit a move-structure invariant violation (corrupt index?)");
     return MOVI_OK;

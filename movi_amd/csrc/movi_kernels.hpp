@@ -155,6 +155,7 @@ struct LaunchCfg {
     int hints = 1;         // 1: mismatches whose scan leaves the row window jump by the reposition hints of the look-ahead rows (DevIndex::hints); 0 = off: A/B
     int zml_ahead = 0;     // 1: zml_kernel_flat<6, T, 0, 1> on the look-ahead rows where they exist (a third fewer iterations, no faster: opt-in)
     int fused_expand = 1;  // 1: a mask walk whose caller wants the vector expands its wavefronts' reads itself (DevIndex::expand_out); 0 = pml_expand_* kernels behind the walk: A/B
+    int kmer_lookahead = -1; // kmer_kernel: -1 = hinted look-ahead with a split chosen by k and the text's length (kmer_look_step), 0 = every end searched from its own base, n >= 2 = split k / n (A/B)
     int deep = -1;         // the PML walk on the deep rows (DevIndex::rows3) where the handle holds them: -1 = batches of short reads (mean length < kDeepReadLen), 0 never, 1 always
 };
 
@@ -359,6 +360,19 @@ hipError_t launch_mem(int mode, const DevIndex &ix, const MemArgs &a, const uint
 // MEMs from d_mems[offs[i]..] to d_out[d_first[i]..].
 hipError_t launch_mem_compact(const MemOut *d_mems, const uint64_t *d_offsets, const uint32_t *d_n_mems, uint64_t n_reads,
                               uint64_t *d_first, MemOut *d_out, hipStream_t stream, bool scan_only);
+
+// k-mer presence (movi_walk_kmer.hip; MoveStructure::query_all_kmers, src/sequitur.cpp:322-421).  KmerRun is movi_kmer_run_t.
+struct KmerRun { uint32_t start, count; };
+struct KmerArgs {
+    uint32_t k;          // >= 1
+    uint32_t step;       // the look-ahead's split: a look starts at most this far left of the end under test (0 = no look-ahead)
+};
+hipError_t launch_kmer(int mode, const DevIndex &ix, const KmerArgs &a, const uint8_t *d_bases, const uint64_t *d_offsets,
+                       uint64_t n_reads, KmerRun *d_runs, uint32_t *d_n_runs, uint32_t *d_found, uint8_t *d_err,
+                       DevStats *d_stats, const uint32_t *d_order, hipStream_t stream, LaunchInfo *info);
+// The host path's compaction, after launch_mem_compact's scan of d_n_runs: every read's runs from d_runs[offs[i]..] to d_out[d_first[i]..].
+hipError_t launch_kmer_gather(const KmerRun *d_runs, const uint64_t *d_offsets, const uint32_t *d_n_runs, uint64_t n_reads,
+                              const uint64_t *d_first, KmerRun *d_out, hipStream_t stream);
 
 // Fills ckpt[j] = BWT position of row (j << kPrefixShift), j = 0 .. ceil(r/32).
 hipError_t build_row_start_ckpt(int mode, const uint8_t *d_rows, uint64_t r, uint64_t *d_ckpt,

@@ -6,6 +6,7 @@ Reference seam (file:line under /root/reference) -> here:
   ReadProcessor::process_latency_hiding src/read_processor.cpp:641        -> MoveIndex.query_pml (batched)
   MoveStructure::query_backward_search src/move_structure_search.cpp:340  -> MoveIndex.query_count
   MoveStructure::query_mems           src/mem_finder.cpp:7-145           -> MoveIndex.query_mems
+  MoveStructure::query_all_kmers      src/sequitur.cpp:322-421           -> MoveIndex.query_kmers
 
 All compute happens in libmovi_hip.so on the GPU; this file only marshals
 buffers.  Errors are MoviError (the reference throws std::runtime_error).
@@ -19,6 +20,8 @@ from ._lib import IndexDescC, LaunchInfoC, QueryStatsC, check, lib
 
 # movi_mem_t: one maximal exact match, end exclusive; count = occurrences of the match's reverse complement (64 bits)
 MEM_DTYPE = np.dtype([("start", np.uint32), ("end", np.uint32), ("count", np.uint64)])
+# movi_kmer_run_t: the k-mers starting at start, start + 1, ..., start + count - 1 are found
+KMER_RUN_DTYPE = np.dtype([("start", np.uint32), ("count", np.uint32)])
 
 
 class IndexDesc:
@@ -354,6 +357,37 @@ class MoveIndex:
             k += c
         return out
 
+    def query_kmers_packed(self, bases, offs, k, want_rc=False):
+        """movi_kmer_host -> (n_runs, found, runs, QueryStats[, return code]); runs is a structured array (KMER_RUN_DTYPE:
+        start, count), compact: the runs of read 0 (by decreasing start), then read 1, ..."""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        n = offs.size - 1
+        cap = int(offs[-1] - offs[0]) if n > 0 else 0
+        nr = np.zeros(max(n, 1), np.uint32)
+        found = np.zeros(max(n, 1), np.uint32)
+        runs = np.zeros(max(cap, 1), KMER_RUN_DTYPE)
+        total = C.c_uint64(0)
+        st = QueryStatsC()
+        rc = lib().movi_kmer_host(self._h, bases.ctypes.data, offs.ctypes.data, n, int(k), nr.ctypes.data, found.ctypes.data,
+                                  runs.ctypes.data, cap, C.byref(total), C.byref(st))
+        out = runs[:total.value]
+        if want_rc:
+            return nr[:n], found[:n], out, QueryStats(st), rc
+        check(rc)
+        return nr[:n], found[:n], out, QueryStats(st)
+
+    def query_kmers(self, reads, k):
+        """query_all_kmers per read: (found, [(start, count), ...]) -- runs by decreasing start, found = sum of the counts."""
+        bases, offs = _pack_reads(reads)
+        nr, found, runs, _ = self.query_kmers_packed(bases, offs, k)
+        out, j = [], 0
+        for i in range(len(reads)):
+            c = int(nr[i])
+            out.append((int(found[i]), [(int(x["start"]), int(x["count"])) for x in runs[j:j + c]]))
+            j += c
+        return out
+
     # -- device-pointer queries (bench / torch interop) ---------------------------
     def pml_device(self, d_bases, d_offs, n_reads, n_bases, d_out, d_err=0, stream=0, d_order=0):
         check(lib().movi_pml_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offs), n_reads, n_bases,
@@ -402,6 +436,15 @@ class MoveIndex:
                                     C.c_void_p(d_err) if d_err else None,
                                     C.c_void_p(d_order) if d_order else None,
                                     C.c_void_p(stream) if stream else None))
+
+    def kmer_device(self, d_bases, d_offs, n_reads, n_bases, k, d_runs, d_n_runs, d_found=0, d_err=0, stream=0, d_order=0):
+        """movi_kmer_device: run j of read i at d_runs[offs[i] + j] (8 bytes each), j < d_n_runs[i]; d_found[i] = found k-mers."""
+        check(lib().movi_kmer_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offs), n_reads, n_bases, int(k),
+                                     C.c_void_p(d_runs), C.c_void_p(d_n_runs),
+                                     C.c_void_p(d_found) if d_found else None,
+                                     C.c_void_p(d_err) if d_err else None,
+                                     C.c_void_p(d_order) if d_order else None,
+                                     C.c_void_p(stream) if stream else None))
 
     PREPARE_PML, PREPARE_COUNT, PREPARE_ZML = 1, 2, 4
 

@@ -206,6 +206,8 @@ struct Job {
     std::vector<uint64_t> matched, counts;                            // --count
     std::vector<uint32_t> n_mems;                                     // --mem: MEMs per read ...
     std::vector<movi_mem_t> mems;                                     // ... and all of them, read by read (file order)
+    std::vector<uint32_t> n_runs, kmers_found;                        // --kmer: runs and found k-mers per read ...
+    std::vector<movi_kmer_run_t> runs;                                // ... and all the runs, read by read (file order)
     std::vector<uint8_t> err;                                         // per-read error byte
     RawBytes original;                                                // reads as given (--filter after --ignore-illegal-chars 1)
     std::vector<uint32_t> bins_above, bins_below;                     // verdict-only classification
@@ -427,7 +429,11 @@ int run_query(const Options &o) {
     const bool open_files = (!o.write_stdout || o.classify) && o.write_output_allowed();
     if (open_files) {
         std::string prefix = !o.out_file.empty() ? o.out_file : o.read_file + "." + index_type;
-        if (o.mem) {                                                  // <out_file or reads.<index type>>.mems
+        if (o.kmer) {                                                 // <out_file or reads.<index type>>.kmers.<k> (src/utils.cpp:348-366)
+            const std::string name = prefix + "." + o.query_type() + "." + std::to_string(o.k);
+            matches_file.open(name);
+            if (!matches_file.good()) throw std::runtime_error("Failed to open the output file: " + name);
+        } else if (o.mem) {                                           // <out_file or reads.<index type>>.mems
             matches_file.open(prefix + ".mems");
             if (!matches_file.good()) throw std::runtime_error("Failed to open the output file: " + prefix + ".mems");
         } else if (o.ml()) {
@@ -589,6 +595,15 @@ int run_query(const Options &o) {
                 for (uint64_t k = first[i]; k < first[i + 1]; k++) append_mem_line(count_txt, rs.id(i), job.mems[k]);
             order.clear();
         }
+        if (o.kmer) {                                                 // output_kmers, src/utils.cpp:258-266 (file order: no prefetch)
+            if (o.write_output_allowed()) {
+                std::vector<uint64_t> first(n + 1, 0);
+                for (size_t i = 0; i < n; i++) first[i + 1] = first[i] + job.n_runs[i];
+                for (uint32_t i : order)
+                    append_kmer_line(count_txt, rs.id(i), rs.len(i), o.k, job.kmers_found[i], job.runs.data() + first[i], job.n_runs[i]);
+            }
+            order.clear();
+        }
         for (uint32_t i : order) {
             const uint64_t len = rs.len(i);
             if (o.ml()) {
@@ -687,6 +702,12 @@ int run_query(const Options &o) {
                 movi_mem_t wmem[32];
                 (void)movi_mem_host(hd, wb, wo, 1, o.min_mem_length, &wn, wmem, 32, &wt, &we, nullptr);
             }
+            else if (o.kmer) {
+                uint32_t wn = 0, wf = 0;
+                uint64_t wt = 0;
+                movi_kmer_run_t wruns[32];
+                (void)movi_kmer_host(hd, wb, wo, 1, o.k, &wn, &wf, wruns, 32, &wt, nullptr);
+            }
             else (void)movi_count_host(hd, wb, wo, 1, &wm, &wc, &we, nullptr);
         }
     }
@@ -721,10 +742,13 @@ int run_query(const Options &o) {
         job.matched.assign(o.count ? n : 0, 0);
         job.counts.assign(o.count ? n : 0, 0);
         job.n_mems.assign(o.mem ? n : 0, 0);
+        job.n_runs.assign(o.kmer ? n : 0, 0);
+        job.kmers_found.assign(o.kmer ? n : 0, 0);
         job.err.assign(n, 0);
         const std::vector<size_t> sb = shard_bounds(rs, o.gpus);
         std::vector<std::string> errors((size_t)o.gpus);
         std::vector<std::vector<movi_mem_t>> mem_shard(o.mem ? (size_t)o.gpus : 0);
+        std::vector<std::vector<movi_kmer_run_t>> run_shard(o.kmer ? (size_t)o.gpus : 0);
         auto tg = std::chrono::steady_clock::now();
         auto work = [&](int g) {
             const size_t a = sb[g], b = sb[g + 1];
@@ -757,6 +781,20 @@ int run_query(const Options &o) {
                 }
                 v.resize(rc == MOVI_OK ? total : 0);
             }
+            else if (o.kmer) {
+                // room for a few runs per read first; a shard that finds more is run again with room for exactly what it found
+                std::vector<movi_kmer_run_t> &v = run_shard[(size_t)g];
+                uint64_t cap = (b - a) * 8 + (rs.offsets[b] - rs.offsets[a]) / 16, total = 0;
+                v.resize(cap);
+                rc = movi_kmer_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, o.k, job.n_runs.data() + a,
+                                    job.kmers_found.data() + a, v.data(), cap, &total, nullptr);
+                if (rc == MOVI_ERR_ARG && total > cap) {
+                    v.resize(total);
+                    rc = movi_kmer_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, o.k, job.n_runs.data() + a,
+                                        job.kmers_found.data() + a, v.data(), total, &total, nullptr);
+                }
+                v.resize(rc == MOVI_OK ? total : 0);
+            }
             else
                 rc = movi_count_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, job.matched.data() + a,
                                      job.counts.data() + a, job.err.data() + a, nullptr);
@@ -772,6 +810,10 @@ int run_query(const Options &o) {
         { const double dtg = std::chrono::duration<double>(std::chrono::steady_clock::now() - tg).count(); gpu_seconds += dtg; if (chunk_gpu_s.size() < 64) chunk_gpu_s.push_back(dtg); }
         for (const auto &e : errors)
             if (!e.empty()) throw EngineError(e);
+        if (o.kmer) {                                                 // the shards' runs in read order
+            job.runs.clear();
+            for (auto &v : run_shard) job.runs.insert(job.runs.end(), v.begin(), v.end());
+        }
         if (o.mem) {                                                  // the shards' MEMs in read order
             job.mems.clear();
             for (auto &v : mem_shard) job.mems.insert(job.mems.end(), v.begin(), v.end());

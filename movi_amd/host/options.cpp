@@ -62,6 +62,8 @@ std::string usage() {
            "                      [--ignore-illegal-chars 1] [--gpus N] [--device D] [--seg-len N] [--ahead-rows 0|1] [--verbose]\n"
            "       movi query -i DIR -r FILE|- --mem --ftab-k K [-l MIN_MEM_LENGTH] [-o PREFIX] [--stdout] [--no-output]\n"
            "                      [--reverse] [--ignore-illegal-chars 1] [--gpus N] [--device D]\n"
+           "       movi query -i DIR -r FILE|- --kmer [-k K] [--ftab-k K'] [-o PREFIX] [--stdout] [--no-output]\n"
+           "                      [--reverse] [--ignore-illegal-chars 1] [--gpus N] [--device D]   (--kmer-count, --rpml: not supported)\n"
            "       movi view --bpf FILE\n"
            "       movi null -i DIR [--gen-reads -f REF.fasta] [--pml|--zml]\n"
            "       movi build -i DIR -f REF.fasta [--type regular-thresholds|blocked-thresholds|sampled-thresholds|regular|blocked|sampled]\n"
@@ -120,21 +122,27 @@ Options parse_args(int argc, char **argv) {
         o.index_dir = val("index");
         o.read_file = val("read");
         if (has("out-file")) o.out_file = val("out-file");
-        for (const char *bad : {"rpml", "kmer", "kmer-count", "sa-entries", "multi-classify", "multi-ftab"})
+        for (const char *bad : {"rpml", "kmer-count", "sa-entries", "multi-classify", "multi-ftab"})
             if (has(bad))
-                throw UsageError(std::string("--") + bad + " is not supported by the MI355X engine (PML, ZML, count and MEM "
-                                 "queries only)");
+                throw UsageError(std::string("--") + bad + " is not supported by the MI355X engine (PML, ZML, count, MEM and "
+                                 "k-mer presence queries only)");
         // --mmap (src/movi_parser.cpp: "Use memory mapping to read the index") is accepted and implied: movi_index_load
         // always maps the file and uploads the rows straight from the page cache
                 if (has("bin-width")) o.bin_width = (size_t)to_int("bin-width", val("bin-width"));
         // movi_parser.cpp:353-355 applies set_count, set_zml, set_pml in this order and each setter
         // clears the other query types (movi_options.hpp:108-110), so the last one applied wins
         // (the "only specify count or pml" check at :407-410 can never fire)
-        // (set_mem comes first, :352: --mem followed by --count, --zml or --pml is that other query)
-        if (has("mem")) { o.mem = true; o.pml = false; o.count = false; o.zml = false; }
-        if (has("count")) { o.count = true; o.pml = false; o.zml = false; o.mem = false; }
-        if (has("zml")) { o.zml = true; o.pml = false; o.count = false; o.mem = false; }
-        if (has("pml")) { o.pml = true; o.count = false; o.zml = false; o.mem = false; }
+        // (set_kmer, :350, then set_mem, :352, come first: --kmer or --mem followed by a later one of the list is that other query)
+        if (has("kmer")) { o.kmer = true; o.pml = false; o.count = false; o.zml = false; o.mem = false; }
+        if (has("mem")) { o.mem = true; o.pml = false; o.count = false; o.zml = false; o.kmer = false; }
+        if (has("count")) { o.count = true; o.pml = false; o.zml = false; o.mem = false; o.kmer = false; }
+        if (has("zml")) { o.zml = true; o.pml = false; o.count = false; o.mem = false; o.kmer = false; }
+        if (has("pml")) { o.pml = true; o.count = false; o.zml = false; o.mem = false; o.kmer = false; }
+        if (has("k-length")) {
+            const long v = to_int("k-length", val("k-length"));
+            if (v < 0 || v > 0xFFFFFFFFl) throw UsageError("Argument '" + val("k-length") + "' failed to parse for option 'k-length'");
+            o.k = (uint32_t)v;
+        }
         if (has("min-mem-length")) {
             const long v = to_int("min-mem-length", val("min-mem-length"));
             if (v < 0 || v > 0xFFFFFFFFl) throw UsageError("Argument '" + val("min-mem-length") + "' failed to parse for option 'min-mem-length'");
@@ -172,6 +180,11 @@ Options parse_args(int argc, char **argv) {
         }
         if (o.gpus < 1) throw UsageError("--gpus must be >= 1");
         if (o.classify && o.count) throw UsageError("--classify needs PML or ZML queries");
+        if (o.kmer) {
+            if (o.classify || o.logs) throw UsageError("--kmer cannot be combined with --classify, --filter or --logs");
+            if (o.k == 0) throw UsageError("-k / --k-length must be at least 1");
+            o.prefetch = false;                                   // movi_parser.cpp:350: file order
+        }
         if (o.mem) {                                              // src/movi.cpp:235-247
             if (o.classify || o.logs) throw UsageError("--mem cannot be combined with --classify, --filter or --logs");
             if (o.ftab_k <= 0)

@@ -23,6 +23,8 @@ struct Options {
     bool count = false;
     bool zml = false;             // --zml: Ziv-Merhav cross parse lengths, same outputs as PML
     bool mem = false;             // --mem: maximal exact matches (src/mem_finder.cpp), one line per MEM
+    bool kmer = false;            // --kmer: k-mer presence (src/sequitur.cpp:322-421), one line per read
+    uint32_t k = 31;              // -k / --k-length (movi_options.hpp:254)
     uint32_t min_mem_length = 25; // -l / --min-mem-length (movi_options.hpp:255)
     long ftab_k = -1;             // --ftab-k K: the engine's interval table at min(K, 12) ("ftab_k"); -1 = not given
     bool classify = false;
@@ -50,7 +52,7 @@ struct Options {
     bool write_output_allowed() const { return !no_output && !filter; }
     bool write_stdout_enabled() const { return write_stdout && !classify; }
     bool ml() const { return pml || zml; }                                // per-base matching lengths
-    std::string query_type() const { return mem ? "mem" : count ? "count" : (zml ? "zml" : "pml"); }   // src/utils.cpp:47-67
+    std::string query_type() const { return kmer ? "kmers" : mem ? "mem" : count ? "count" : (zml ? "zml" : "pml"); }   // src/utils.cpp:47-67
 };
 
 struct UsageError : std::runtime_error {

@@ -345,6 +345,31 @@ void append_mem_line(std::string &txt, std::string_view id, const movi_mem_t &m)
     txt.push_back('\n');
 }
 
+// output_kmers, src/utils.cpp:258-266: `id<TAB>found/all<TAB>` and MoveQuery::add_kmer's string (move_query.hpp:12-19), every
+// `start:count` pair followed by a space.  all = query length - k + 1 as the reference computes it (src/movi.cpp:87): in
+// 64-bit unsigned arithmetic, so a read shorter than k prints the wrapped value.
+void append_kmer_line(std::string &txt, std::string_view id, uint64_t query_length, uint32_t k, uint64_t found,
+                      const movi_kmer_run_t *runs, uint64_t n_runs) {
+    char num[24];
+    auto put = [&](uint64_t v) {
+        const auto r = std::to_chars(num, num + sizeof(num), v);
+        txt.append(num, (size_t)(r.ptr - num));
+    };
+    txt.append(id.data(), id.size());
+    txt.push_back('\t');
+    put(found);
+    txt.push_back('/');
+    put(query_length - (uint64_t)k + 1ull);
+    txt.push_back('\t');
+    for (uint64_t j = 0; j < n_runs; j++) {
+        put(runs[j].start);
+        txt.push_back(':');
+        put(runs[j].count);
+        txt.push_back(' ');
+    }
+    txt.push_back('\n');
+}
+
 void append_count_line(std::string &txt, std::string_view id, uint64_t query_length, uint64_t matched, uint64_t count) {
     char num[24];
     auto put = [&](uint64_t v) {
