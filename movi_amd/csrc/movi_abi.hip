@@ -1686,6 +1686,88 @@ int run_chunked(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offset
     return MOVI_OK;
 }
 
+// One kind of query whose per-read results vary in length (MEMs, k-mer runs) behind a *_host entry point: the reads go through the
+// handle's staging in chunks of about kCompactChunkBases bases (at least kCompactChunkReads reads, at most kCompactMaxChunkBases:
+// the device stages elem_bytes per base, twice -- the kernel's output and its compacted copy), every chunk's results are compacted on
+// the device and come down behind those of the chunks before it.
+//   device(d_bases, d_offs, nr, nb, d_out, d_n, d_err)   enqueues the query on the null stream: read i's results from d_out + elem_bytes *
+//                                                        d_offs[i], their number in d_n[i], a second u32 per read in d_n[nr + i] if `second`.
+constexpr uint64_t kCompactChunkBases = 1ull << 25;
+constexpr uint64_t kCompactChunkReads = 1ull << 18;
+constexpr uint64_t kCompactMaxChunkBases = 1ull << 27;
+struct CompactOut {
+    size_t elem_bytes;         // of one result
+    void *h_out;               // the caller's array of `cap` results; *n_total = the number found (set even when they do not fit)
+    uint64_t cap, *n_total;
+    uint32_t *h_n;             // results per read
+    bool second;               // the kernel writes a second u32 per read ...
+    uint32_t *h_second;        // ... which comes down here (optional)
+    uint8_t *h_read_err;       // optional
+    const char *what;          // the overflow message between the two numbers
+};
+template <typename Device>
+int run_compact(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, const CompactOut &o,
+                movi_query_stats_t *stats, Device device) {
+    if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
+    HIP_TRY(hipSetDevice(ix->device));
+    void **d = ix->scratch;
+    size_t *cap = ix->scratch_cap;
+    std::vector<uint64_t> rel;
+    uint64_t total = 0, errors = 0;
+    bool overflow = false;
+    uint64_t first = 0;
+    while (first < n_reads) {
+        uint64_t last = first + 1;
+        while (last < n_reads) {
+            const uint64_t nb_next = h_offsets[last + 1] - h_offsets[first];
+            if (nb_next <= kCompactChunkBases || (last - first < kCompactChunkReads && nb_next <= kCompactMaxChunkBases)) ++last;
+            else break;
+        }
+        const uint64_t nr = last - first, b0 = h_offsets[first], nb = h_offsets[last] - b0;
+        HIP_TRY(grow(&d[movi_index::kBases], &cap[movi_index::kBases], nb));
+        HIP_TRY(grow(&d[movi_index::kOffs], &cap[movi_index::kOffs], (nr + 1) * 8));
+        HIP_TRY(grow(&d[movi_index::kErr], &cap[movi_index::kErr], nr));
+        HIP_TRY(grow(&d[movi_index::kOut], &cap[movi_index::kOut], nb * o.elem_bytes));
+        HIP_TRY(grow(&d[movi_index::kA], &cap[movi_index::kA], nr * (o.second ? 8 : 4)));
+        HIP_TRY(grow(&d[movi_index::kB], &cap[movi_index::kB], (nr + 1) * 8));
+        rel.resize(nr + 1);
+        for (uint64_t i = 0; i <= nr; i++) rel[i] = h_offsets[first + i] - b0;
+        if (nb) HIP_TRY(hipMemcpy(d[movi_index::kBases], h_bases + b0, nb, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d[movi_index::kOffs], rel.data(), (nr + 1) * 8, hipMemcpyHostToDevice));
+        const uint64_t *d_offs = static_cast<const uint64_t *>(d[movi_index::kOffs]);
+        uint32_t *d_n = static_cast<uint32_t *>(d[movi_index::kA]);
+        uint64_t *d_first = static_cast<uint64_t *>(d[movi_index::kB]);
+        int rc = device(static_cast<const uint8_t *>(d[movi_index::kBases]), d_offs, nr, nb, d[movi_index::kOut], d_n,
+                        static_cast<uint8_t *>(d[movi_index::kErr]));
+        if (rc) return rc;
+        // compaction on the device: the per-read counts' prefix, then only the results found come down
+        HIP_TRY(launch_count_scan(d_n, nr, d_first, nullptr));
+        DevStats h{};
+        HIP_TRY(hipMemcpy(&h, ix->d_stats, sizeof(h), hipMemcpyDeviceToHost));
+        uint64_t found = 0;
+        HIP_TRY(hipMemcpy(o.h_n + first, d_n, nr * 4, hipMemcpyDeviceToHost));
+        if (o.h_second) HIP_TRY(hipMemcpy(o.h_second + first, d_n + nr, nr * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&found, d_first + nr, 8, hipMemcpyDeviceToHost));
+        if (!overflow && total + found <= o.cap) {
+            if (found) {
+                HIP_TRY(grow(&d[movi_index::kS], &cap[movi_index::kS], found * o.elem_bytes));
+                HIP_TRY(launch_gather(d[movi_index::kOut], o.elem_bytes, d_offs, d_n, nr, d_first, d[movi_index::kS], nullptr));
+                HIP_TRY(hipMemcpy(static_cast<uint8_t *>(o.h_out) + total * o.elem_bytes, d[movi_index::kS], found * o.elem_bytes, hipMemcpyDeviceToHost));
+            }
+        } else overflow = true;
+        if (o.h_read_err) HIP_TRY(hipMemcpy(o.h_read_err + first, d[movi_index::kErr], nr, hipMemcpyDeviceToHost));
+        total += found;
+        errors += h.errors;
+        if (stats) add_stats(stats, nb, h);
+        first = last;
+    }
+    if (o.n_total) *o.n_total = total;
+    if (overflow) return fail(MOVI_ERR_ARG, std::to_string(total) + o.what + std::to_string(o.cap));
+    if (errors)
+        return fail(MOVI_ERR_INVARIANT, std::to_string(errors) + " read(s) hit a move-structure invariant violation (corrupt index?)");
+    return MOVI_OK;
+}
+
 // The same call with the caller's bases (and, for PML / ZML, result vector) in page-locked memory: kPipeSlots chunks in
 // flight, each on its own stream -- upload, walk, download -- so that the three overlap across chunks: the call then
 // costs about what its slowest leg does (2 B per base coming down: ~28 Gbases/s on a 56 GB/s link) instead of the
@@ -2488,12 +2570,6 @@ int mem_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_offsets
     return MOVI_OK;
 }
 
-// movi_mem_host cuts its reads into chunks of about this many bases (at least kMemChunkReads reads, at most kMemMaxChunkBases):
-// the device layout stages 16 bytes per base, twice (kernel output and compacted MEMs).
-constexpr uint64_t kMemChunkBases = 1ull << 25;
-constexpr uint64_t kMemChunkReads = 1ull << 18;
-constexpr uint64_t kMemMaxChunkBases = 1ull << 27;
-
 }  // namespace
 
 extern "C" {
@@ -2514,73 +2590,11 @@ int movi_mem_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_of
     if (n_reads == 0) return MOVI_OK;
     if (!h_offsets || !h_n_mems || (h_offsets[n_reads] != h_offsets[0] && !h_bases) || (mems_cap && !h_mems))
         return fail(MOVI_ERR_ARG, "NULL host buffer");
-    if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
-    HIP_TRY(hipSetDevice(ix->device));
-    void **d = ix->scratch;
-    size_t *cap = ix->scratch_cap;
-    std::vector<uint64_t> rel;
-    uint64_t total = 0, errors = 0;
-    bool overflow = false;
-    uint64_t first = 0;
-    while (first < n_reads) {
-        uint64_t last = first + 1;
-        while (last < n_reads) {
-            const uint64_t nb_next = h_offsets[last + 1] - h_offsets[first];
-            if (nb_next <= kMemChunkBases || (last - first < kMemChunkReads && nb_next <= kMemMaxChunkBases)) ++last;
-            else break;
-        }
-        const uint64_t nr = last - first, b0 = h_offsets[first], nb = h_offsets[last] - b0;
-        HIP_TRY(grow(&d[movi_index::kBases], &cap[movi_index::kBases], nb));
-        HIP_TRY(grow(&d[movi_index::kOffs], &cap[movi_index::kOffs], (nr + 1) * 8));
-        HIP_TRY(grow(&d[movi_index::kErr], &cap[movi_index::kErr], nr));
-        HIP_TRY(grow(&d[movi_index::kOut], &cap[movi_index::kOut], nb * sizeof(movi_mem_t)));
-        HIP_TRY(grow(&d[movi_index::kA], &cap[movi_index::kA], nr * 4));
-        HIP_TRY(grow(&d[movi_index::kB], &cap[movi_index::kB], (nr + 1) * 8));
-        rel.resize(nr + 1);
-        for (uint64_t i = 0; i <= nr; i++) rel[i] = h_offsets[first + i] - b0;
-        if (nb) HIP_TRY(hipMemcpy(d[movi_index::kBases], h_bases + b0, nb, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d[movi_index::kOffs], rel.data(), (nr + 1) * 8, hipMemcpyHostToDevice));
-        const uint64_t *d_offs = static_cast<const uint64_t *>(d[movi_index::kOffs]);
-        MemOut *d_out = static_cast<MemOut *>(d[movi_index::kOut]);
-        uint32_t *d_n = static_cast<uint32_t *>(d[movi_index::kA]);
-        uint64_t *d_first = static_cast<uint64_t *>(d[movi_index::kB]);
-        int rc = mem_device(ix, static_cast<const uint8_t *>(d[movi_index::kBases]), d_offs, nr, nb, min_len,
-                            reinterpret_cast<movi_mem_t *>(d_out), d_n, static_cast<uint8_t *>(d[movi_index::kErr]), nullptr, nullptr);
-        if (rc) return rc;
-        // compaction on the device: the per-read counts' prefix, then only the MEMs found come down
-        HIP_TRY(launch_mem_compact(d_out, d_offs, d_n, nr, d_first, nullptr, nullptr, true));
-        movi_query_stats_t st{};
-        rc = movi_last_stats(ix, nullptr, &st);
-        if (rc) return rc;
-        uint64_t found = 0;
-        HIP_TRY(hipMemcpy(h_n_mems + first, d_n, nr * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&found, d_first + nr, 8, hipMemcpyDeviceToHost));
-        if (!overflow && total + found <= mems_cap) {
-            if (found) {
-                HIP_TRY(grow(&d[movi_index::kS], &cap[movi_index::kS], found * sizeof(movi_mem_t)));
-                MemOut *d_comp = static_cast<MemOut *>(d[movi_index::kS]);
-                HIP_TRY(launch_mem_compact(d_out, d_offs, d_n, nr, d_first, d_comp, nullptr, false));
-                HIP_TRY(hipMemcpy(h_mems + total, d_comp, found * sizeof(movi_mem_t), hipMemcpyDeviceToHost));
-            }
-        } else overflow = true;
-        if (h_read_err) HIP_TRY(hipMemcpy(h_read_err + first, d[movi_index::kErr], nr, hipMemcpyDeviceToHost));
-        total += found;
-        errors += st.errors;
-        if (stats) {
-            st.bases = nb;
-            DevStats h{};
-            h.fast_forwards = st.fast_forwards; h.scans = st.scans; h.repositions = st.repositions; h.errors = st.errors;
-            h.lane_steps = st.lane_steps; h.wave_steps = st.wave_steps; h.segments = st.segments; h.rewalked = st.rewalked;
-            add_stats(stats, nb, h);
-        }
-        first = last;
-    }
-    if (n_mems_total) *n_mems_total = total;
-    if (overflow)
-        return fail(MOVI_ERR_ARG, std::to_string(total) + " MEMs found, mems_cap is " + std::to_string(mems_cap));
-    if (errors)
-        return fail(MOVI_ERR_INVARIANT, std::to_string(errors) + " read(s) hit a move-structure invariant violation (corrupt index?)");
-    return MOVI_OK;
+    const CompactOut out{sizeof(movi_mem_t), h_mems, mems_cap, n_mems_total, h_n_mems, false, nullptr, h_read_err, " MEMs found, mems_cap is "};
+    return run_compact(ix, h_bases, h_offsets, n_reads, out, stats,
+                       [&](const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, void *d_out, uint32_t *d_n, uint8_t *d_err) {
+                           return mem_device(ix, db, dof, nr, nb, min_len, static_cast<movi_mem_t *>(d_out), d_n, d_err, nullptr, nullptr);
+                       });
 }
 
 // -------------------------------------------------------------------------- k-mers
@@ -2636,7 +2650,6 @@ int movi_kmer_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d
                        static_cast<hipStream_t>(stream));
 }
 
-// (chunks as movi_mem_host cuts them: the device layout stages 8 bytes per base, twice)
 int movi_kmer_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint32_t k,
                    uint32_t *h_n_runs, uint32_t *h_found, movi_kmer_run_t *h_runs, uint64_t runs_cap, uint64_t *n_runs_total,
                    movi_query_stats_t *stats) {
@@ -2647,75 +2660,11 @@ int movi_kmer_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_o
     if (n_reads == 0) return MOVI_OK;
     if (!h_offsets || !h_n_runs || (h_offsets[n_reads] != h_offsets[0] && !h_bases) || (runs_cap && !h_runs))
         return fail(MOVI_ERR_ARG, "NULL host buffer");
-    if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
-    HIP_TRY(hipSetDevice(ix->device));
-    void **d = ix->scratch;
-    size_t *cap = ix->scratch_cap;
-    std::vector<uint64_t> rel;
-    uint64_t total = 0, errors = 0;
-    bool overflow = false;
-    uint64_t first = 0;
-    while (first < n_reads) {
-        uint64_t last = first + 1;
-        while (last < n_reads) {
-            const uint64_t nb_next = h_offsets[last + 1] - h_offsets[first];
-            if (nb_next <= kMemChunkBases || (last - first < kMemChunkReads && nb_next <= kMemMaxChunkBases)) ++last;
-            else break;
-        }
-        const uint64_t nr = last - first, b0 = h_offsets[first], nb = h_offsets[last] - b0;
-        HIP_TRY(grow(&d[movi_index::kBases], &cap[movi_index::kBases], nb));
-        HIP_TRY(grow(&d[movi_index::kOffs], &cap[movi_index::kOffs], (nr + 1) * 8));
-        HIP_TRY(grow(&d[movi_index::kErr], &cap[movi_index::kErr], nr));
-        HIP_TRY(grow(&d[movi_index::kOut], &cap[movi_index::kOut], nb * sizeof(movi_kmer_run_t)));
-        HIP_TRY(grow(&d[movi_index::kA], &cap[movi_index::kA], nr * 8));          // runs per read, then k-mers found per read
-        HIP_TRY(grow(&d[movi_index::kB], &cap[movi_index::kB], (nr + 1) * 8));
-        rel.resize(nr + 1);
-        for (uint64_t i = 0; i <= nr; i++) rel[i] = h_offsets[first + i] - b0;
-        if (nb) HIP_TRY(hipMemcpy(d[movi_index::kBases], h_bases + b0, nb, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d[movi_index::kOffs], rel.data(), (nr + 1) * 8, hipMemcpyHostToDevice));
-        const uint64_t *d_offs = static_cast<const uint64_t *>(d[movi_index::kOffs]);
-        KmerRun *d_out = static_cast<KmerRun *>(d[movi_index::kOut]);
-        uint32_t *d_n = static_cast<uint32_t *>(d[movi_index::kA]);
-        uint32_t *d_found = d_n + nr;
-        uint64_t *d_first = static_cast<uint64_t *>(d[movi_index::kB]);
-        int rc = kmer_device(ix, static_cast<const uint8_t *>(d[movi_index::kBases]), d_offs, nr, nb, k,
-                             reinterpret_cast<movi_kmer_run_t *>(d_out), d_n, d_found, static_cast<uint8_t *>(d[movi_index::kErr]),
-                             nullptr, nullptr);
-        if (rc) return rc;
-        // compaction on the device: the per-read counts' prefix, then only the runs found come down
-        HIP_TRY(launch_mem_compact(nullptr, d_offs, d_n, nr, d_first, nullptr, nullptr, true));
-        movi_query_stats_t st{};
-        rc = movi_last_stats(ix, nullptr, &st);
-        if (rc) return rc;
-        uint64_t got = 0;
-        HIP_TRY(hipMemcpy(h_n_runs + first, d_n, nr * 4, hipMemcpyDeviceToHost));
-        if (h_found) HIP_TRY(hipMemcpy(h_found + first, d_found, nr * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(&got, d_first + nr, 8, hipMemcpyDeviceToHost));
-        if (!overflow && total + got <= runs_cap) {
-            if (got) {
-                HIP_TRY(grow(&d[movi_index::kS], &cap[movi_index::kS], got * sizeof(movi_kmer_run_t)));
-                KmerRun *d_comp = static_cast<KmerRun *>(d[movi_index::kS]);
-                HIP_TRY(launch_kmer_gather(d_out, d_offs, d_n, nr, d_first, d_comp, nullptr));
-                HIP_TRY(hipMemcpy(h_runs + total, d_comp, got * sizeof(movi_kmer_run_t), hipMemcpyDeviceToHost));
-            }
-        } else overflow = true;
-        total += got;
-        errors += st.errors;
-        if (stats) {
-            st.bases = nb;
-            DevStats h{};
-            h.fast_forwards = st.fast_forwards; h.scans = st.scans; h.repositions = st.repositions; h.errors = st.errors;
-            h.lane_steps = st.lane_steps; h.wave_steps = st.wave_steps; h.segments = st.segments; h.rewalked = st.rewalked;
-            add_stats(stats, nb, h);
-        }
-        first = last;
-    }
-    if (n_runs_total) *n_runs_total = total;
-    if (overflow)
-        return fail(MOVI_ERR_ARG, std::to_string(total) + " runs found, runs_cap is " + std::to_string(runs_cap));
-    if (errors)
-        return fail(MOVI_ERR_INVARIANT, std::to_string(errors) + " read(s) hit a move-structure invariant violation (corrupt index?)");
-    return MOVI_OK;
+    const CompactOut out{sizeof(movi_kmer_run_t), h_runs, runs_cap, n_runs_total, h_n_runs, true, h_found, nullptr, " runs found, runs_cap is "};
+    return run_compact(ix, h_bases, h_offsets, n_reads, out, stats,
+                       [&](const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, void *d_out, uint32_t *d_n, uint8_t *d_err) {
+                           return kmer_device(ix, db, dof, nr, nb, k, static_cast<movi_kmer_run_t *>(d_out), d_n, d_n + nr, d_err, nullptr, nullptr);
+                       });
 }
 
 }  // extern "C"

@@ -925,6 +925,63 @@ hipError_t launch_copy_words(uint64_t *d_dst, const uint64_t *src, uint64_t n, h
     return hipGetLastError();
 }
 
+// ---- compaction of per-read results of variable length (the host path of the MEM and k-mer queries): the counts' exclusive
+// prefix (one block), then every read's elements to their place
+
+constexpr int kScanThreads = 1024;
+
+__global__ __launch_bounds__(kScanThreads) void count_scan_kernel(const uint32_t *__restrict__ n, uint64_t cnt, uint64_t *__restrict__ first) {
+    __shared__ uint64_t part[kScanThreads];
+    const uint64_t per = (cnt + kScanThreads - 1) / kScanThreads;
+    const uint64_t lo = (uint64_t)threadIdx.x * per, hi = lo + per < cnt ? lo + per : cnt;
+    uint64_t s = 0;
+    for (uint64_t i = lo; i < hi; ++i) s += n[i];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int d = 1; d < kScanThreads; d <<= 1) {        // inclusive Hillis-Steele scan of the per-thread sums
+        const uint64_t v = threadIdx.x >= (unsigned)d ? part[threadIdx.x - d] : 0ull;
+        __syncthreads();
+        part[threadIdx.x] += v;
+        __syncthreads();
+    }
+    uint64_t run = threadIdx.x ? part[threadIdx.x - 1] : 0ull;
+    for (uint64_t i = lo; i < hi; ++i) { first[i] = run; run += n[i]; }
+    if (threadIdx.x == kScanThreads - 1) first[cnt] = part[kScanThreads - 1];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void gather_kernel(const T *__restrict__ src, const uint64_t *__restrict__ offs,
+                                                     const uint32_t *__restrict__ n, const uint64_t *__restrict__ first,
+                                                     uint64_t n_reads, T *__restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_reads) return;
+    const T *s = src + offs[i];
+    T *d = out + first[i];
+    for (uint32_t k = 0; k < n[i]; ++k) d[k] = s[k];
+}
+
+hipError_t launch_count_scan(const uint32_t *d_n, uint64_t n_reads, uint64_t *d_first, hipStream_t stream) {
+    hipLaunchKernelGGL(count_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, d_n, n_reads, d_first);
+    return hipGetLastError();
+}
+
+hipError_t launch_gather(const void *d_src, size_t elem_bytes, const uint64_t *d_offsets, const uint32_t *d_n, uint64_t n_reads,
+                         const uint64_t *d_first, void *d_out, hipStream_t stream) {
+    struct Words2 { uint64_t a, b; };
+    const uint64_t blocks = (n_reads + 255) / 256;
+    if (blocks == 0) return hipSuccess;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), block(256);
+    if (elem_bytes == 8)
+        hipLaunchKernelGGL(gather_kernel<uint64_t>, grid, block, 0, stream, static_cast<const uint64_t *>(d_src), d_offsets, d_n, d_first, n_reads,
+                           static_cast<uint64_t *>(d_out));
+    else if (elem_bytes == 16)
+        hipLaunchKernelGGL(gather_kernel<Words2>, grid, block, 0, stream, static_cast<const Words2 *>(d_src), d_offsets, d_n, d_first, n_reads,
+                           static_cast<Words2 *>(d_out));
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
 // ---- launch log (diagnostic; movi_launch_log): the distinct walk kernels launched since it was switched on / last read
 static std::atomic<bool> g_launch_log_on{false};
 static std::mutex g_launch_log_m;
@@ -1151,7 +1208,7 @@ hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
 }
 
 // ----------------------------------------------------------------------- count
-// (the interval step -- shrink_interval, row_start -- lives in movi_search.hpp, shared with the MEM kernel)
+// (the interval step -- shrink_interval, row_start -- and the interval table's entry live in movi_search.hpp, shared with the MEM and k-mer kernels)
 
 // Interval table of the count query (DevIndex::ftab): lane t runs the backward search of the K-mer whose i-th consumed base
 // (i = 0: the read's last base) has code (t >> 2 i) & 3 (+ 1 on a separators index) -- exactly count_kernel_v0's steps -- and
@@ -1182,14 +1239,8 @@ __global__ __launch_bounds__(256) void ftab_kernel(DevIndex ix, uint32_t K, uint
         if (nonempty && !((rs < re) || (rs == re && os <= oe))) run = 0;
     }
     if (!valid) return;
-    const uint32_t ok = (uint32_t)(run != 0u && failed == 0u && ff_total < (1u << 15) && scan_total < (1u << 16) && os < 4096u && oe < 4096u);
     uint4 e4 = make_uint4(0, 0, 0, 0);
-    if (ok) {
-        e4.x = (uint32_t)rs;
-        e4.y = (uint32_t)re;
-        e4.z = (uint32_t)(rs >> 32) | ((uint32_t)(re >> 32) << 4) | (os << 8) | (oe << 20);
-        e4.w = ff_total | (scan_total << 15) | (1u << 31);
-    }
+    if (run != 0u && failed == 0u && ftab_fits(os, oe, ff_total, scan_total)) e4 = ftab_encode(FtabEntry{rs, re, os, oe, ff_total, scan_total});
     table[t] = e4;
 }
 
@@ -1294,13 +1345,11 @@ __global__ __launch_bounds__(256) void count_kernel_v0(DevIndex ix, const uint8_
         }
         uint4 e4 = make_uint4(0, 0, 0, 0);
         if (!bad) e4 = ix.ftab[kidx];
-        if (e4.w >> 31) {
-            rs = (uint64_t)e4.x | ((uint64_t)(e4.z & 15u) << 32);
-            re = (uint64_t)e4.y | ((uint64_t)((e4.z >> 4) & 15u) << 32);
-            os = (e4.z >> 8) & 0xFFFu;
-            oe = e4.z >> 20;
-            ff_total = e4.w & 0x7FFFu;
-            scan_total = (e4.w >> 15) & 0xFFFFu;
+        if (ftab_valid(e4)) {
+            const FtabEntry f = ftab_decode(e4);
+            rs = f.rs; re = f.re; os = f.os; oe = f.oe;
+            ff_total = f.ff;
+            scan_total = f.scans;
             pos = len - (int64_t)K;
             have = 1;
             run = 1;
@@ -1877,13 +1926,11 @@ __global__ __launch_bounds__(256) void zml_kernel_flat(DevIndex ix, const uint8_
         }
         uint4 e4 = make_uint4(0, 0, 0, 0);
         if (!bad) e4 = ix.ftab[kidx];
-        if (e4.w >> 31) {
-            rs = (IdxT)((uint64_t)e4.x | ((uint64_t)(e4.z & 15u) << 32));
-            re = (IdxT)((uint64_t)e4.y | ((uint64_t)((e4.z >> 4) & 15u) << 32));
-            os = (e4.z >> 8) & 0xFFFu;
-            oe = e4.z >> 20;
-            ff_total = e4.w & 0x7FFFu;
-            scan_total = (e4.w >> 15) & 0xFFFFu;
+        if (ftab_valid(e4)) {
+            const FtabEntry f = ftab_decode(e4);
+            rs = (IdxT)f.rs; re = (IdxT)f.re; os = f.os; oe = f.oe;
+            ff_total = f.ff;
+            scan_total = f.scans;
             prs = rs; pre = re; pos_ = os; poe = oe; have = 1;
             k = K;
             open = 1;

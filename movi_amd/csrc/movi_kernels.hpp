@@ -356,10 +356,6 @@ struct MemArgs {
 hipError_t launch_mem(int mode, const DevIndex &ix, const MemArgs &a, const uint8_t *d_bases, const uint64_t *d_offsets,
                       uint64_t n_reads, MemOut *d_mems, uint32_t *d_n_mems, uint8_t *d_err, DevStats *d_stats,
                       const uint32_t *d_order, hipStream_t stream, LaunchInfo *info);
-// The host path's compaction: scan_only -> d_first[0..n] = exclusive prefix of d_n_mems (d_first[n] = total); else every read's
-// MEMs from d_mems[offs[i]..] to d_out[d_first[i]..].
-hipError_t launch_mem_compact(const MemOut *d_mems, const uint64_t *d_offsets, const uint32_t *d_n_mems, uint64_t n_reads,
-                              uint64_t *d_first, MemOut *d_out, hipStream_t stream, bool scan_only);
 
 // k-mer presence (movi_walk_kmer.hip; MoveStructure::query_all_kmers, src/sequitur.cpp:322-421).  KmerRun is movi_kmer_run_t.
 struct KmerRun { uint32_t start, count; };
@@ -370,9 +366,12 @@ struct KmerArgs {
 hipError_t launch_kmer(int mode, const DevIndex &ix, const KmerArgs &a, const uint8_t *d_bases, const uint64_t *d_offsets,
                        uint64_t n_reads, KmerRun *d_runs, uint32_t *d_n_runs, uint32_t *d_found, uint8_t *d_err,
                        DevStats *d_stats, const uint32_t *d_order, hipStream_t stream, LaunchInfo *info);
-// The host path's compaction, after launch_mem_compact's scan of d_n_runs: every read's runs from d_runs[offs[i]..] to d_out[d_first[i]..].
-hipError_t launch_kmer_gather(const KmerRun *d_runs, const uint64_t *d_offsets, const uint32_t *d_n_runs, uint64_t n_reads,
-                              const uint64_t *d_first, KmerRun *d_out, hipStream_t stream);
+
+// Compaction of per-read results of variable length (the host path of both): d_first[0..n] = exclusive prefix of the counts d_n
+// (d_first[n] = their total); then read i's d_n[i] elements of elem_bytes (8 or 16) from d_src[d_offsets[i]..] to d_out[d_first[i]..].
+hipError_t launch_count_scan(const uint32_t *d_n, uint64_t n_reads, uint64_t *d_first, hipStream_t stream);
+hipError_t launch_gather(const void *d_src, size_t elem_bytes, const uint64_t *d_offsets, const uint32_t *d_n, uint64_t n_reads,
+                         const uint64_t *d_first, void *d_out, hipStream_t stream);
 
 // Fills ckpt[j] = BWT position of row (j << kPrefixShift), j = 0 .. ceil(r/32).
 hipError_t build_row_start_ckpt(int mode, const uint8_t *d_rows, uint64_t r, uint64_t *d_ckpt,

@@ -1,6 +1,10 @@
-// movi_search.hpp -- the backward-search interval step shared by the count kernels (movi_kernels.hip) and the MEM kernel
-// (movi_walk_mem.hip): the row / window / look-ahead entry readers, update_interval (shrink_interval, shrink_interval_rows) and
-// the row-start checkpoints behind MoveInterval::count (row_start).  Moved here unchanged from movi_kernels.hip.
+// movi_search.hpp -- backward search on intervals, shared by the count kernels and ftab_kernel (movi_kernels.hip), the MEM kernel
+// (movi_walk_mem.hip) and the k-mer kernel (movi_walk_kmer.hip):
+//   * the row / window / look-ahead entry readers, update_interval (shrink_interval, shrink_interval_rows) and the row-start
+//     checkpoints behind MoveInterval::count (row_start);
+//   * the entry of the interval table (DevIndex::ftab): FtabEntry, ftab_encode, ftab_decode -- its bit layout is stated there only;
+//   * for the lane-per-read queries (MEM, k-mers): the prologue (read_lane), the interval step (search_step), the counters' way
+//     out (flush_lane_stats) and the launch (launch_lane_per_read).
 #pragma once
 #include "movi_device.hpp"
 
@@ -130,6 +134,164 @@ __device__ __forceinline__ uint64_t row_start(const DevIndex &ix, uint64_t k) {
     uint64_t p = ix.row_start_ckpt[k >> kPrefixShift];
     for (; j < k; ++j) p += row_n<MODE>(load_row<MODE>(ix.rows, j));
     return p;
+}
+
+// ---- entry of the interval table (DevIndex::ftab): the interval after the K bases of its index, and what reaching it cost.
+//   x       rs[31:0]                      y       re[31:0]
+//   z[3:0]  rs[35:32]   z[7:4]  re[35:32]   z[19:8]  os (< 4096)   z[31:20]  oe (< 4096)
+//   w[14:0] fast-forwards   w[30:15] rows scanned   w[31] valid (a cleared entry: the K-mer is absent, or a field overflowed)
+struct FtabEntry {
+    uint64_t rs, re;
+    uint32_t os, oe, ff, scans;
+};
+__device__ __forceinline__ bool ftab_fits(uint32_t os, uint32_t oe, uint32_t ff, uint32_t scans) {
+    return ff < (1u << 15) && scans < (1u << 16) && os < 4096u && oe < 4096u;
+}
+__device__ __forceinline__ uint4 ftab_encode(const FtabEntry &f) {           // ftab_fits(...) holds
+    uint4 e4;
+    e4.x = (uint32_t)f.rs;
+    e4.y = (uint32_t)f.re;
+    e4.z = (uint32_t)(f.rs >> 32) | ((uint32_t)(f.re >> 32) << 4) | (f.os << 8) | (f.oe << 20);
+    e4.w = f.ff | (f.scans << 15) | (1u << 31);
+    return e4;
+}
+__device__ __forceinline__ bool ftab_valid(const uint4 &e4) { return (e4.w >> 31) != 0u; }
+__device__ __forceinline__ FtabEntry ftab_decode(const uint4 &e4) {          // ftab_valid(e4)
+    FtabEntry f;
+    f.rs = (uint64_t)e4.x | ((uint64_t)(e4.z & 15u) << 32);
+    f.re = (uint64_t)e4.y | ((uint64_t)((e4.z >> 4) & 15u) << 32);
+    f.os = (e4.z >> 8) & 0xFFFu;
+    f.oe = e4.z >> 20;
+    f.ff = e4.w & 0x7FFFu;
+    f.scans = (e4.w >> 15) & 0xFFFFu;
+    return f;
+}
+
+// ---- one lane per read (MEM, k-mers): prologue, step, epilogue, launch
+
+// The block's copy of DevIndex::code_of in LDS (s_code) and the lane's read: rid (through `order`, if given), its first base and length.
+struct ReadLane {
+    bool valid;
+    uint64_t rid, beg;
+    uint32_t m;
+};
+__device__ __forceinline__ ReadLane read_lane(const DevIndex &ix, uint8_t (&s_code)[256], const uint64_t *__restrict__ offs,
+                                              uint64_t n_reads, const uint32_t *__restrict__ order) {
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) s_code[i] = ix.code_of[i];
+    __syncthreads();
+    ReadLane r;
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    r.valid = t < n_reads;
+    r.rid = (r.valid && order) ? order[t] : t;
+    r.beg = r.valid ? offs[r.rid] : 0;
+    r.m = r.valid ? (uint32_t)(offs[r.rid + 1] - r.beg) : 0u;
+    return r;
+}
+
+// One backward-search step of a lane inside a phase -- a run of bases searched from an empty pattern, of which `l` are taken so far
+// (the interval is non-empty after each) and `lim` may be taken.  base_at(i) is the code of the i-th base from the phase's next one
+// (0xFF: illegal), direction and complement being the caller's; it is asked for i = 0, and for i < K at the phase's start.
+//   l == 0   the first K = DevIndex::ftab_k bases by one lookup in the interval table, when they are all legal, stay inside the
+//            phase's range and the entry is valid (a cleared entry is not "absent": counter overflow clears it too);
+//            else initialize_backward_search (src/move_structure_search.cpp:284-291) on the first base;
+//   l > 0    update_interval + two LF moves (:311-333); keep(rs, re, os, oe) sees the interval before them.
+// The interval lives in the caller's rs / os / rws (start: row, offset, the row's words) and re / oe / rwe (end) across the call only:
+// what it is kept in between iterations is the caller's choice.  The wave-uniform loops inside are entered by all lanes.
+struct SearchStep {
+    uint32_t b;        // the base the step was on (0xFF: illegal, or the lane is idle)
+    uint32_t taken;    // bases taken: K, 1, or 0 -- the phase died on b
+    bool ext;          // the step was an update_interval on a legal base
+    uint32_t err;      // kErr* of the LF moves: the read is over
+};
+template <int MODE, typename BaseAt, typename Keep>
+__device__ __forceinline__ SearchStep search_step(const DevIndex &ix, bool live, uint32_t lim, uint32_t &l, BaseAt base_at, Keep keep,
+                                                  uint64_t &rs, uint32_t &os, uint2 &rws, uint64_t &re, uint32_t &oe, uint2 &rwe,
+                                                  uint32_t &ff_total, uint32_t &scan_total) {
+    const uint32_t K = ix.ftab_k;
+    SearchStep r;
+    r.b = live ? base_at(0u) : 0xFFu;
+    r.taken = 0;
+    r.err = 0;
+    bool stepped = false;
+    if (K != 0u && live && l == 0 && K <= lim) {
+        uint32_t kidx = 0, bad = 0;
+        for (uint32_t i = 0; i < K; ++i) {              // K is wave-uniform
+            const uint32_t cc = base_at(i) - ix.sep;
+            bad |= (uint32_t)(cc > 3u);
+            kidx |= (cc & 3u) << (2u * i);
+        }
+        uint4 e4 = make_uint4(0, 0, 0, 0);
+        if (!bad) e4 = ix.ftab[kidx];
+        if (ftab_valid(e4)) {
+            const FtabEntry f = ftab_decode(e4);
+            rs = f.rs; re = f.re; os = f.os; oe = f.oe;
+            ff_total += f.ff;
+            scan_total += f.scans;
+            rws = load_row<MODE>(ix.rows, rs);
+            rwe = load_row<MODE>(ix.rows, re);
+            r.taken = K;
+            stepped = true;
+        }
+    }
+    const uint32_t b = r.b;
+    const bool init = live && !stepped && l == 0 && b != 0xFFu;
+    r.ext = live && !stepped && l > 0 && b != 0xFFu;
+    bool ne_init = false;
+    if (init) {
+        rs = ix.first_runs[b + 1]; re = ix.last_runs[b + 1];
+        os = (uint32_t)ix.first_offsets[b + 1]; oe = (uint32_t)ix.last_offsets[b + 1];
+        ne_init = (rs < re) || (rs == re && os <= oe);
+        if (ne_init) {
+            rws = load_row<MODE>(ix.rows, rs);
+            rwe = load_row<MODE>(ix.rows, re);
+        }
+    }
+    if (r.ext) keep(rs, re, os, oe);
+    if (ix.r >= 8) shrink_interval<MODE>(ix, r.ext && rs <= re, b, rs, os, rws, re, oe, rwe, scan_total);
+    else shrink_interval_rows<MODE>(ix, r.ext && rs <= re, b, rs, os, rws, re, oe, rwe, scan_total);
+    bool ne = r.ext && ((rs < re) || (rs == re && os <= oe));
+    r.err = lf_step2<MODE>(ix, ne, rs, os, rws, re, oe, rwe, ff_total);
+    if (r.err) ne = false;
+    if (ne && !((rs < re) || (rs == re && os <= oe))) ne = false;
+    if (ne || ne_init) r.taken = 1;
+    l += r.taken;
+    return r;
+}
+
+// The lane's counters to DevStats (may be null), one atomic per wavefront and counter.
+__device__ __forceinline__ void flush_lane_stats(DevStats *stats, uint32_t ff_total, uint32_t scan_total, uint32_t failed,
+                                                 uint32_t lane_steps, uint32_t wave_steps) {
+    const uint32_t ffw = wave_sum(ff_total), scw = wave_sum(scan_total), erw = wave_sum(failed ? 1u : 0u), lsw = wave_sum(lane_steps);
+    if ((threadIdx.x & 63) == 0 && stats) {
+        if (ffw) atomicAdd(&stats->fast_forwards, (unsigned long long)ffw);
+        if (scw) atomicAdd(&stats->scans, (unsigned long long)scw);
+        if (erw) atomicAdd(&stats->errors, (unsigned long long)erw);
+        atomicAdd(&stats->lane_steps, (unsigned long long)lsw);
+        atomicAdd(&stats->wave_steps, (unsigned long long)wave_steps);
+    }
+}
+
+// Launch of a kernel family F -- F::kernel<MODE, IdxT>() = the __global__ function (DevIndex, args...) -- one lane per read in blocks of
+// one wavefront, MODE in {6, 3} x IdxT in {uint32_t, uint64_t (DevIndex::idx32 == 0)}; noted and reported as "<name><MODE, IdxT>".
+template <typename F, typename... Args>
+hipError_t launch_lane_per_read(const char *name, int variant, int mode, const DevIndex &ix, uint64_t n_reads, hipStream_t stream,
+                                LaunchInfo *info, Args... args) {
+    if (n_reads == 0) return hipSuccess;
+    if (mode != 6 && mode != 3) return hipErrorInvalidValue;
+    const uint64_t blocks = (n_reads + 63) / 64;
+    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    char nm[96];
+    snprintf(nm, sizeof(nm), "%s<%d, %s>", name, mode, ix.idx32 ? "unsigned int" : "unsigned long");
+    note_walk_launch(nm);
+    if (info) {
+        *info = LaunchInfo();
+        snprintf(info->kernel, sizeof(info->kernel), "%s", nm);
+        info->variant = variant; info->block_threads = 64; info->idx64 = ix.idx32 ? 0 : 1;
+    }
+    auto kernel = mode == 6 ? (ix.idx32 ? F::template kernel<6, uint32_t>() : F::template kernel<6, uint64_t>())
+                            : (ix.idx32 ? F::template kernel<3, uint32_t>() : F::template kernel<3, uint64_t>());
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), 0, stream, ix, args...);
+    return hipGetLastError();
 }
 
 }  // namespace movi

@@ -305,6 +305,57 @@ def test_host_cap_too_small(texts, expected):
     gpu.close()
 
 
+@pytest.fixture(scope="module")
+def tile(texts):
+    """A small batch of short reads (mean length < 128, so that 2^25 bases hold more than 2^18 reads and the host loop cuts there), one
+    with an illegal base and one shorter than k among them, and its k-mers at k = 13 from the oracle."""
+    from oracle.oracle import Oracle
+    k, ref = 13, _ref()
+    reads = [r for r in _reads() if len(r) <= 120][:300] + [ref[2000:2050] + b"N" + ref[2051:2100], ref[300:300 + k - 1]]
+    o = Oracle(texts[False][6])
+    exp, _ = kmer_ref.restate(o, reads, (k,))
+    o.close()
+    return k, reads, exp[k]
+
+
+@pytest.mark.parametrize("K", [0, 12])
+def test_host_two_chunks(texts, tile, K):
+    """movi_kmer_host on just over 2^25 bases -- the tile repeated -- takes two chunks: the second chunk's runs follow the first's."""
+    import movi_amd
+    from movi_amd._lib import QueryStatsC, lib
+    from movi_amd.engine import KMER_RUN_DTYPE
+    k, reads, want = tile
+    tb, toffs = pack(reads)
+    tnb = int(toffs[-1])
+    copies = (1 << 25) // tnb + 2                             # past 2^25 + one copy
+    bases = np.tile(np.asarray(tb), copies)
+    offs = np.concatenate([(toffs[:-1].astype(np.uint64) + np.uint64(c * tnb)) for c in range(copies)] + [np.array([copies * tnb], np.uint64)])
+    n = len(reads) * copies
+    assert (1 << 25) + tnb < copies * tnb <= (1 << 25) + 2 * tnb
+    assert np.searchsorted(offs, 1 << 25, "right") - 1 >= 1 << 18          # the first chunk ends at 2^25 bases, not at 2^27
+    want_n = np.tile(np.array([len(runs) for _, runs in want], np.uint32), copies)
+    want_f = np.tile(np.array([f for f, _ in want], np.uint32), copies)
+    want_runs = np.tile(np.array([r for _, runs in want for r in runs], KMER_RUN_DTYPE), copies)
+    assert len(want_runs) > len(reads)
+    gpu = movi_amd.MoveIndex.from_image(texts[False][6])
+    gpu.set_option("ftab_k", K)
+    nr, found = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    runs = np.zeros(len(want_runs), KMER_RUN_DTYPE)
+    total, st = C.c_uint64(0), QueryStatsC()
+    rc = lib().movi_kmer_host(gpu._h, bases.ctypes.data, offs.ctypes.data, n, k, nr.ctypes.data, found.ctypes.data, runs.ctypes.data,
+                              len(runs), C.byref(total), C.byref(st))
+    assert rc == 0 and total.value == len(want_runs) and st.bases == copies * tnb
+    assert (nr == want_n).all() and (found == want_f).all()
+    assert (runs == want_runs).all()
+    nr[:] = 0
+    found[:] = 0
+    rc = lib().movi_kmer_host(gpu._h, bases.ctypes.data, offs.ctypes.data, n, k, nr.ctypes.data, found.ctypes.data, runs.ctypes.data,
+                              len(runs) - 1, C.byref(total), C.byref(st))
+    assert rc == -1 and total.value == len(want_runs) and (nr == want_n).all() and (found == want_f).all()
+    assert ("%d runs found, runs_cap is %d" % (len(want_runs), len(runs) - 1)).encode() in lib().movi_last_error()
+    gpu.close()
+
+
 def _kmer_lines(ids, reads, oracle, k):
     exp, _ = kmer_ref.restate(oracle, reads, (k,))
     return b"".join(kmer_ref.line(i, len(r), k, f, runs) for i, r, (f, runs) in zip(ids, reads, exp[k]))

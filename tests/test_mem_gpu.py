@@ -270,6 +270,58 @@ def test_host_cap_too_small(texts, expected):
     gpu.close()
 
 
+@pytest.fixture(scope="module")
+def tile(texts):
+    """A small batch of short reads (mean length < 128, so that 2^25 bases hold more than 2^18 reads and the host loop cuts there), one
+    with an illegal base and one shorter than L among them, and its MEMs at L = 25 from the oracle."""
+    from oracle.oracle import Oracle
+    import movi_amd
+    L, ref = 25, _ref()
+    reads = [r for r in _reads() if len(r) <= 120][:300] + [ref[2000:2050] + b"N" + ref[2051:2100], ref[300:300 + L - 1]]
+    desc, _, _, _ = movi_amd.parse_index_image(texts[False][6])
+    o = Oracle(texts[False][6])
+    exp, _ = mem_ref.restate(o, reads, desc.code_of, (L,))
+    o.close()
+    return L, reads, exp[L]
+
+
+@pytest.mark.parametrize("K", [0, 12])
+def test_host_two_chunks(texts, tile, K):
+    """movi_mem_host on just over 2^25 bases -- the tile repeated -- takes two chunks: the second chunk's MEMs follow the first's."""
+    import ctypes as C
+    import movi_amd
+    from movi_amd._lib import QueryStatsC, lib
+    from movi_amd.engine import MEM_DTYPE
+    L, reads, want = tile
+    tb, toffs = pack(reads)
+    tnb = int(toffs[-1])
+    copies = (1 << 25) // tnb + 2                             # past 2^25 + one copy
+    bases = np.tile(np.asarray(tb), copies)
+    offs = np.concatenate([(toffs[:-1].astype(np.uint64) + np.uint64(c * tnb)) for c in range(copies)] + [np.array([copies * tnb], np.uint64)])
+    n = len(reads) * copies
+    assert (1 << 25) + tnb < copies * tnb <= (1 << 25) + 2 * tnb
+    assert np.searchsorted(offs, 1 << 25, "right") - 1 >= 1 << 18          # the first chunk ends at 2^25 bases, not at 2^27
+    want_n = np.tile(np.array([len(x) for x in want], np.uint32), copies)
+    want_mems = np.tile(np.array([m for x in want for m in x], MEM_DTYPE), copies)
+    assert len(want_mems) > len(reads)
+    gpu = movi_amd.MoveIndex.from_image(texts[False][6])
+    gpu.set_option("ftab_k", K)
+    nm = np.zeros(n, np.uint32)
+    mems = np.zeros(len(want_mems), MEM_DTYPE)
+    total, st = C.c_uint64(0), QueryStatsC()
+    rc = lib().movi_mem_host(gpu._h, bases.ctypes.data, offs.ctypes.data, n, L, nm.ctypes.data, mems.ctypes.data, len(mems),
+                             C.byref(total), None, C.byref(st))
+    assert rc == 0 and total.value == len(want_mems) and st.bases == copies * tnb
+    assert (nm == want_n).all()
+    assert (mems == want_mems).all()
+    nm[:] = 0
+    rc = lib().movi_mem_host(gpu._h, bases.ctypes.data, offs.ctypes.data, n, L, nm.ctypes.data, mems.ctypes.data, len(mems) - 1,
+                             C.byref(total), None, C.byref(st))
+    assert rc == -1 and total.value == len(want_mems) and (nm == want_n).all()
+    assert ("%d MEMs found, mems_cap is %d" % (len(want_mems), len(mems) - 1)).encode() in lib().movi_last_error()
+    gpu.close()
+
+
 def _mem_lines(ids, reads, oracle, code_of, L):
     exp, _ = mem_ref.restate(oracle, reads, code_of, (L,))
     return b"".join(b"%s\t%d\t%d\t%d\n" % (i, s, e, c & 0xFFFF) for i, ms in zip(ids, exp[L]) for s, e, c in ms)
