@@ -18,6 +18,9 @@
  *   MoveStructure::query_zml        src/move_structure_query.cpp:690-785  movi_zml_host / movi_zml_device
  *   MoveStructure::query_mems  src/mem_finder.cpp:7-145  movi_mem_host / movi_mem_device
  *   MoveStructure::query_all_kmers  src/sequitur.cpp:322-421  movi_kmer_host / movi_kmer_device
+ *   MoveStructure::get_SA_entries  src/move_structure.cpp:35-48  movi_locate_device / movi_sa_entries_host / movi_sa_entries_device
+ *   MoveStructure::find_sampled_SA_entries  src/move_structure_build.cpp:1174-1212  movi_ssa_build
+ *   MoveStructure::serialize_sampled_SA / deserialize_sampled_SA  src/move_structure_io.cpp:710-744  movi_ssa_save / movi_ssa_load
  *   MoveQuery::add_ml / matching_lens  include/move_query.hpp:26-38 (filled by process_char, src/read_processor.cpp:193-215)
  *                                                                       movi_pml_mask_device / movi_pml_mask_host (one reset bit per base)
  *                                                                       + movi_pml_expand_device / movi_pml_expand_host (bits -> u16 vector)
@@ -179,6 +182,9 @@ int movi_index_load_replicated(const char *index_dir_or_file, const int *devices
 #define MOVI_PREPARE_PML 1u
 #define MOVI_PREPARE_COUNT 2u
 #define MOVI_PREPARE_ZML 4u
+#define MOVI_PREPARE_SA 8u     /* locate: loads the kernels of movi_sa_entries_device / movi_locate_device.  The sampled suffix array and the
+                                  locate rows are built when the array is attached (movi_ssa_build / movi_ssa_load), so a handle without
+                                  one is MOVI_ERR_ARG here */
 int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *derived_bytes);
 
 int movi_index_destroy(movi_index_t *ix);
@@ -273,7 +279,7 @@ int movi_launch_log(char *buf, size_t cap, size_t *needed);
 /* What the handle holds in HBM besides the row table, and what its builders measured (no reference counterpart; the
  * derived tables of "kmer_k" / "ahead_rows" / "ftab_k" are built by the first query that can use them, so this is how a
  * caller sees their cost).  Keys: "rows_bytes" (the resident row table), "kmer_bytes", "ftab_bytes", "ahead_rows_bytes",
- * "ckpt_bytes" (0 = not built), "derived_bytes" (their sum), "ahead_no_ff" (share of the table's BWT
+ * "ckpt_bytes" (0 = not built), "locate_bytes" (the locate rows and the samples of an attached sampled suffix array), "derived_bytes" (their sum), "ahead_no_ff" (share of the table's BWT
  * positions that reach their LF target without a fast-forward, tallied when the look-ahead rows are built: 0.83 on the
  * pangenome BWT, 0.51 on a uniformly random run sequence; -1 = not tallied yet), "device_scratch_bytes" (device scratch the
  * *_device calls hold: movi_pml_device's mask words -- retired buffers that captured graphs may still use included --, the u16 vector
@@ -472,6 +478,77 @@ int movi_kmer_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d
 int movi_kmer_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint32_t k,
                    uint32_t *h_n_runs, uint32_t *h_found, movi_kmer_run_t *h_runs, uint64_t runs_cap, uint64_t *n_runs_total,
                    movi_query_stats_t *stats);
+
+/* ---- locate: suffix-array entries from a sampled suffix array ------------------- */
+
+/* `movi build-SA` and `movi query --sa-entries`: where in the indexed text a match lies.
+ *
+ * Terms.  n = desc.length BWT positions; SA[p] = the text position of the suffix at BWT position p; an LF step goes from the
+ * position of text position t to that of t - 1, and from text position 0 to BWT position 0, whose entry is n - 1.  A sampled
+ * suffix array of rate R holds SA[0], SA[R], SA[2R], ...: n / R + 1 entries (find_sampled_SA_entries sizes it so; where R
+ * divides n the last entry addresses no position and is 0).
+ * The entry of a position p (get_SA_entries): d LF steps from p reach the first sampled position q; the answer is SA[q] + d.
+ * It is NOT reduced modulo n: with m = the smallest sampled entry, the answer is SA[p] for SA[p] >= m and SA[p] + n below --
+ * the walk passed text position 0 and stopped at BWT position 0.  The reference returns the same.
+ *
+ * A position is a (row, offset) pair packed into one u64 by MOVI_POS_PACK: rows are those of the resident table
+ * (movi_index_device_rows), offset < the row's length.  MOVI_POS_NONE is no position: movi_locate_device leaves it as it is.
+ *
+ * movi_ssa_build: the array for `rate` (1 .. 2^24, else MOVI_ERR_ARG), on the device, from the table alone -- every sampled
+ * position walks to the next sampled position down the text (the locate kernel, one LF step taken first), which links the
+ * samples into one list from sample 0; ranking that list by pointer jumping gives every entry.  MOVI_ERR_INVARIANT if the list
+ * does not visit every sample exactly once (a corrupt table).  Works on every index type.  The call also derives the LOCATE ROWS,
+ * 16 bytes per row: the row and the quotient / remainder by `rate` of the BWT position of its first character, so that a locate
+ * step is one gather.  Both are counted by movi_index_info "locate_bytes" / "derived_bytes"; failing to allocate them is an error.
+ * Attaching an array replaces the one before it and frees that one's samples and locate rows: a graph captured over
+ * movi_sa_entries_device / movi_locate_device still points at them and must be captured again, not replayed.  A table of 2^31 - 1
+ * rows or more cannot attach an array yet (MOVI_ERR_ARG): the prefix sum over the row lengths is one 32-bit-indexed device scan.
+ * Waits for its kernels.
+ * movi_ssa_save / movi_ssa_load: INDEX/ssa.movi, byte for byte serialize_sampled_SA's file: u64 rate, u64 count, the entries,
+ * u64 r, all_p[r] (the BWT position of every row's first character).  Loading takes the rate from the file, checks the count
+ * against the text's length, the trailing r against the index and the file's length against r (MOVI_ERR_FORMAT; all_p itself is
+ * recomputed from the table, not read) and derives the locate rows for that rate.  Saving writes PATH.tmp and renames it: a failed
+ * save leaves no partial ssa.movi;
+ * a missing file is MOVI_ERR_IO with the reference's hint to run build-SA.
+ * movi_ssa_get: rate and entry count (either pointer may be NULL), and the entries if h_samples is given (cap < count:
+ * MOVI_ERR_ARG). */
+#define MOVI_POS_OFFSET_BITS 12
+#define MOVI_POS_PACK(row, offset) (((uint64_t)(row) << MOVI_POS_OFFSET_BITS) | (uint64_t)(offset))
+#define MOVI_POS_ROW(pos) ((uint64_t)(pos) >> MOVI_POS_OFFSET_BITS)
+#define MOVI_POS_OFFSET(pos) ((uint64_t)(pos) & ((1u << MOVI_POS_OFFSET_BITS) - 1u))
+#define MOVI_POS_NONE (~(uint64_t)0)
+
+int movi_ssa_build(movi_index_t *ix, uint64_t rate, void *stream);
+int movi_ssa_save(movi_index_t *ix, const char *path);
+int movi_ssa_load(movi_index_t *ix, const char *path);
+int movi_ssa_get(const movi_index_t *ix, uint64_t *rate, uint64_t *h_samples, uint64_t cap, uint64_t *n_samples);
+
+/* In place: d_positions_inout[i] holds a packed position on entry and its suffix-array entry on return.  A lane owns the items
+ * lane, lane + stride, ... and takes up its next item when a walk ends, so walks of very different lengths keep the wavefronts
+ * full.  An item that is not a position of the table, or whose walk breaks one of the table's invariants (the reference's throws
+ * in LF_move; more than n steps), becomes MOVI_POS_NONE and is counted in movi_last_stats' `errors`: a corrupt table ends the
+ * call, it does not hang it.  Asynchronous on `stream`; allocates nothing; capturable.  Without an attached sampled suffix
+ * array: MOVI_ERR_ARG (the message names build-SA).  movi_last_stats: lane_steps = LF steps taken, wave_steps = iterations of
+ * the wavefronts (lane_steps / (64 * wave_steps) = the occupancy of the strided lists). */
+int movi_locate_device(movi_index_t *ix, uint64_t *d_positions_inout, uint64_t n_items, void *stream);
+
+/* The PML query that also says where: d_out_sa[offsets[i] + k] = the suffix-array entry of the position the walk stands at after
+ * base (len_i - 1 - k) of read i was processed and before the LF step to the next one -- what query_pml hands to get_SA_entries
+ * (src/move_structure_query.cpp:354-357), in emission order like the PMLs.  An illegal base leaves the state as it is and still
+ * records an entry.  d_out_pml (optional): the PML vector of movi_pml_device.  One lane per read walks the plain rows (no derived
+ * table of the PML walk is used) and writes the packed positions into d_out_sa; the locate kernel then turns them into entries
+ * in place.  A read that hits one of the reference's throws reports its code in d_read_err, all-zero PMLs and MOVI_POS_NONE in
+ * every slot.  *-thresholds indexes only.  Buffers, offsets, d_read_err, d_read_order and the stream as for movi_pml_device, except
+ * that n_bases must EQUAL offsets[n_reads]: the locate kernel takes every one of the n_bases slots for a position.
+ * With a sampled suffix array attached the call allocates and builds nothing: it may be captured into a graph without a warm-up
+ * call (movi_index_prepare(MOVI_PREPARE_SA) loads the kernels beforehand).  Without one: MOVI_ERR_ARG. */
+int movi_sa_entries_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                           uint16_t *d_out_pml, uint64_t *d_out_sa, uint8_t *d_read_err, const uint32_t *d_read_order, void *stream);
+
+/* Host buffers in and out (h_out_pml optional), chunk by chunk through the handle's staging, synchronously.  A read or a walk
+ * that breaks an invariant makes the call return MOVI_ERR_INVARIANT after everything else was answered. */
+int movi_sa_entries_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint16_t *h_out_pml,
+                         uint64_t *h_out_sa, uint8_t *h_read_err, movi_query_stats_t *stats);
 
 /* ---- page-locked host memory --------------------------------------------------- */
 

@@ -113,6 +113,10 @@ struct movi_index {
     uint4 *d_ftab = nullptr;         // the count query's interval table ("ftab_k" option), 16 << 2K bytes
     int ftab_auto = 12;              // K of the table the first count query builds by itself (0 = none)
     DevStats *d_stats = nullptr;
+    // locate: the attached sampled suffix array (movi_ssa_build / movi_ssa_load) and the locate rows derived from the table for its rate
+    uint4 *d_loc = nullptr;          // 16 bytes per row (movi_sa.hpp)
+    uint64_t *d_samples = nullptr;   // length / sa_rate + 1 entries
+    uint64_t sa_rate = 0;            // 0 = no sampled suffix array attached
     DevIndex dev{};
     int kmode = 0;                   // row layout the kernels run on: desc.mode, except 6 for sampled-thresholds (expanded)
     LaunchCfg cfg;
@@ -167,6 +171,8 @@ struct movi_index {
 };
 
 static void release_scratch(movi_index *ix);
+static const char *const kNoSsa = "no sampled suffix array is attached to this index: build one with movi_ssa_build (`movi build-SA`) or "
+                                  "load ssa.movi with movi_ssa_load";
 namespace { hipError_t grow(void **p, size_t *cap, size_t bytes); }
 constexpr uint64_t kPrepareMaskBases = 1ull << 28;   // movi_index_prepare's reservation of movi_pml_device's mask words (1 M x 150 bp fits)
 constexpr uint64_t kPrepareMaskReads = 1ull << 22;
@@ -809,6 +815,8 @@ int movi_index_destroy(movi_index_t *ix) {
     if (ix->d_rows2) (void)hipFree(ix->d_rows2);
     if (ix->d_rows3) (void)hipFree(ix->d_rows3);
     if (ix->d_stats) (void)hipFree(ix->d_stats);
+    if (ix->d_loc) (void)hipFree(ix->d_loc);
+    if (ix->d_samples) (void)hipFree(ix->d_samples);
     release_scratch(ix);
     delete ix;
     return MOVI_OK;
@@ -1393,13 +1401,15 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     const double ahead = ix->d_rows2 ? (double)ahead_rows_bytes(ix->desc.r) : 0.0;
     const double deep = ix->d_rows3 ? (double)deep_rows_bytes(ix->desc.r) : 0.0;
     const double ckpt = ix->d_ckpt ? (double)((ix->desc.r >> kPrefixShift) + 2) * 8.0 : 0.0;
+    const double locate = ix->sa_rate ? (double)locate_rows_bytes(ix->desc.r) + (double)(ix->desc.length / ix->sa_rate + 1) * 8.0 : 0.0;
     if (!strcmp(key, "rows_bytes")) *value = rows;
+    else if (!strcmp(key, "locate_bytes")) *value = locate;
     else if (!strcmp(key, "kmer_bytes")) *value = kmer;
     else if (!strcmp(key, "ftab_bytes")) *value = ftab;
     else if (!strcmp(key, "ahead_rows_bytes")) *value = ahead;
     else if (!strcmp(key, "deep_rows_bytes")) *value = deep;
     else if (!strcmp(key, "ckpt_bytes")) *value = ckpt;
-    else if (!strcmp(key, "derived_bytes")) *value = kmer + ftab + ahead + deep + ckpt;
+    else if (!strcmp(key, "derived_bytes")) *value = kmer + ftab + ahead + deep + ckpt + locate;
     else if (!strcmp(key, "ahead_no_ff")) *value = ix->ahead_tallied ? ix->ahead_no_ff : -1.0;
     else if (!strcmp(key, "device_scratch_bytes")) {         // device scratch the *_device calls hold: mask words (retired ones too), vector, segment workspace
         double b = (double)ix->dmask_cap + (double)ix->scratch_cap[movi_index::kTmp] + (double)ix->seg_ws.cap;
@@ -2469,7 +2479,8 @@ int movi_count_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *
 
 int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *derived_bytes) {
     if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
-    if (what & ~(uint32_t)(MOVI_PREPARE_PML | MOVI_PREPARE_COUNT | MOVI_PREPARE_ZML)) return fail(MOVI_ERR_ARG, "unknown MOVI_PREPARE_* bit");
+    if (what & ~(uint32_t)(MOVI_PREPARE_PML | MOVI_PREPARE_COUNT | MOVI_PREPARE_ZML | MOVI_PREPARE_SA)) return fail(MOVI_ERR_ARG, "unknown MOVI_PREPARE_* bit");
+    if ((what & MOVI_PREPARE_SA) && !ix->sa_rate) return fail(MOVI_ERR_ARG, kNoSsa);
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     ix->ahead_retry_in = 0;                                           // an explicit call asks the device now
@@ -2486,6 +2497,11 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
     if (what & MOVI_PREPARE_COUNT) {
         const int rc = ensure_count_tables(ix, s, true);
         if (rc) return rc;
+    }
+    if (what & MOVI_PREPARE_SA) {
+        // the sampled suffix array and the locate rows were built when it was attached: only the kernels' code object is loaded here
+        (void)preload_sa(ix->kmode, ix->dev.idx32 != 0);
+        (void)hipGetLastError();
     }
     ix->prepared = true;
     // (MOVI_PREPARE_ZML: the parse walks on the plain rows and derives nothing -- accepted so that callers need not know)
@@ -2665,6 +2681,216 @@ int movi_kmer_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_o
                        [&](const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, void *d_out, uint32_t *d_n, uint8_t *d_err) {
                            return kmer_device(ix, db, dof, nr, nb, k, static_cast<movi_kmer_run_t *>(d_out), d_n, d_n + nr, d_err, nullptr, nullptr);
                        });
+}
+
+}  // extern "C"
+
+// -------------------------------------------------------------------------- locate (sampled suffix array)
+
+namespace {
+
+void detach_ssa(movi_index *ix) {
+    if (ix->d_loc) (void)hipFree(ix->d_loc);
+    if (ix->d_samples) (void)hipFree(ix->d_samples);
+    ix->d_loc = nullptr;
+    ix->d_samples = nullptr;
+    ix->sa_rate = 0;
+}
+
+LocArgs loc_args(const movi_index *ix) {
+    LocArgs a;
+    a.rows = ix->d_loc;
+    a.samples = ix->d_samples;
+    a.n = ix->desc.length;
+    a.n_entries = ix->desc.length / ix->sa_rate + 1;
+    a.rate = (uint32_t)ix->sa_rate;
+    return a;
+}
+
+// The locate rows for `rate` and room for the samples; on success the array is attached (its entries still to be filled).
+int attach_ssa(movi_index *ix, uint64_t rate, hipStream_t s) {
+    if (rate == 0) return fail(MOVI_ERR_ARG, "the sample rate must be at least 1");
+    if (rate > (1ull << 24)) return fail(MOVI_ERR_ARG, "sample rates above 2^24 are not supported (the locate rows keep the remainder in 24 bits)");
+    if (ix->desc.r + 1 > 0x7FFFFFFFull)
+        return fail(MOVI_ERR_ARG, "a sampled suffix array cannot be attached to a table of 2^31 - 1 rows or more yet (the prefix sum over the row "
+                                  "lengths is one 32-bit-indexed device scan)");
+    detach_ssa(ix);
+    const uint64_t entries = ix->desc.length / rate + 1;
+    hipError_t e = hipMalloc(&ix->d_loc, locate_rows_bytes(ix->desc.r));
+    if (e == hipSuccess) e = hipMalloc(&ix->d_samples, entries * 8);
+    uint64_t n_total = 0;
+    if (e == hipSuccess) e = build_locate_rows(ix->kmode, ix->dev, rate, ix->d_loc, &n_total, s);
+    if (e != hipSuccess) { detach_ssa(ix); return fail_hip(e, "building the locate rows"); }    // an error, never a walk without them
+    if (n_total != ix->desc.length) {
+        detach_ssa(ix);
+        return fail(MOVI_ERR_INVARIANT, "the row lengths add up to " + std::to_string(n_total) + ", the index header says " + std::to_string(ix->desc.length));
+    }
+    ix->sa_rate = rate;
+    return MOVI_OK;
+}
+
+int locate_device(movi_index *ix, uint64_t *d_pos, uint64_t n_items, hipStream_t s, DevStats *d_stats, bool clear_stats) {
+    if (clear_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(DevStats), s));
+    HIP_TRY(launch_locate(ix->kmode, ix->dev, loc_args(ix), d_pos, n_items, d_stats, ix->cfg.num_cus, s, &ix->last_launch));
+    return MOVI_OK;
+}
+
+int sa_entries_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint16_t *d_pml,
+                      uint64_t *d_sa, uint8_t *d_err, const uint32_t *d_order, hipStream_t s, DevStats *d_stats) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (!mode_has_thresholds(ix->desc.mode))
+        return fail(MOVI_ERR_ARG, "--sa-entries rides on the PML walk, which needs thresholds: use a *-thresholds index");
+    if (!ix->sa_rate) return fail(MOVI_ERR_ARG, kNoSsa);
+    if (n_reads == 0) return MOVI_OK;
+    if (!d_offsets || (n_bases && (!d_bases || !d_sa))) return fail(MOVI_ERR_ARG, "NULL device buffer");
+    if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
+    HIP_TRY(hipSetDevice(ix->device));
+    if (!d_stats) d_stats = ix->d_stats;
+    HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(DevStats), s));
+    LaunchInfo pos_info;
+    HIP_TRY(launch_sa_pos(ix->dev, d_bases, d_offsets, n_reads, d_pml, d_sa, d_err, d_stats, d_order, s, &pos_info));
+    if (n_bases == 0) { ix->last_launch = pos_info; return MOVI_OK; }
+    return locate_device(ix, d_sa, n_bases, s, d_stats, false);
+}
+
+bool read_exact(FILE *f, void *dst, size_t bytes) { return bytes == 0 || fread(dst, 1, bytes, f) == bytes; }
+
+}  // namespace
+
+extern "C" {
+
+int movi_ssa_build(movi_index_t *ix, uint64_t rate, void *stream) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = attach_ssa(ix, rate, s)) return rc;
+    uint32_t bad = 0;
+    HIP_TRY(hipMemsetAsync(ix->d_stats, 0, sizeof(DevStats), s));
+    const hipError_t e = build_sampled_sa(ix->kmode, ix->dev, loc_args(ix), ix->d_samples, ix->d_stats, ix->cfg.num_cus, s, &bad, &ix->last_launch);
+    if (e != hipSuccess) { detach_ssa(ix); return fail_hip(e, "building the sampled suffix array"); }
+    if (bad) {
+        detach_ssa(ix);
+        return fail(MOVI_ERR_INVARIANT, "the sampled positions do not form one cycle under LF (" + std::to_string(bad) + " finding(s)): corrupt index?");
+    }
+    return MOVI_OK;
+}
+
+int movi_ssa_get(const movi_index_t *ix, uint64_t *rate, uint64_t *h_samples, uint64_t cap, uint64_t *n_samples) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (!ix->sa_rate) return fail(MOVI_ERR_ARG, kNoSsa);
+    const uint64_t entries = ix->desc.length / ix->sa_rate + 1;
+    if (rate) *rate = ix->sa_rate;
+    if (n_samples) *n_samples = entries;
+    if (!h_samples) return MOVI_OK;
+    if (cap < entries) return fail(MOVI_ERR_ARG, "the sampled suffix array has " + std::to_string(entries) + " entries, cap is " + std::to_string(cap));
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipMemcpy(h_samples, ix->d_samples, entries * 8, hipMemcpyDeviceToHost));
+    return MOVI_OK;
+}
+
+int movi_ssa_save(movi_index_t *ix, const char *path) {
+    if (!ix || !path) return fail(MOVI_ERR_ARG, "NULL argument");
+    if (!ix->sa_rate) return fail(MOVI_ERR_ARG, kNoSsa);
+    HIP_TRY(hipSetDevice(ix->device));
+    const uint64_t entries = ix->desc.length / ix->sa_rate + 1, r = ix->desc.r;
+    std::vector<uint64_t> buf(entries);
+    HIP_TRY(hipMemcpy(buf.data(), ix->d_samples, entries * 8, hipMemcpyDeviceToHost));
+    const std::string tmp = std::string(path) + ".tmp";                // renamed over `path` once complete: no partial ssa.movi
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) return fail(MOVI_ERR_IO, std::string("cannot write ") + tmp);
+    // serialize_sampled_SA, src/move_structure_io.cpp:710-722
+    bool ok = fwrite(&ix->sa_rate, 8, 1, f) == 1 && fwrite(&entries, 8, 1, f) == 1 && fwrite(buf.data(), 8, entries, f) == entries &&
+              fwrite(&r, 8, 1, f) == 1;
+    constexpr uint64_t kPiece = 1ull << 22;                            // all_p back out of the locate rows, piece by piece
+    void *d_piece = nullptr;
+    hipError_t e = ok ? hipMalloc(&d_piece, std::min(r, kPiece) * 8) : hipSuccess;
+    buf.resize(std::min(r, kPiece));
+    for (uint64_t first = 0; ok && e == hipSuccess && first < r; first += kPiece) {
+        const uint64_t cnt = std::min(kPiece, r - first);
+        e = locate_rows_all_p(ix->d_loc, first, cnt, ix->sa_rate, static_cast<uint64_t *>(d_piece), nullptr);
+        if (e == hipSuccess) e = hipMemcpy(buf.data(), d_piece, cnt * 8, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) ok = fwrite(buf.data(), 8, cnt, f) == cnt;
+    }
+    if (d_piece) (void)hipFree(d_piece);
+    ok = (fclose(f) == 0) && ok;
+    if (e == hipSuccess && ok) ok = std::rename(tmp.c_str(), path) == 0;
+    else (void)std::remove(tmp.c_str());
+    if (e != hipSuccess) return fail_hip(e, "reading the locate rows back");
+    if (!ok) return fail(MOVI_ERR_IO, std::string("writing ") + path + " failed");
+    return MOVI_OK;
+}
+
+int movi_ssa_load(movi_index_t *ix, const char *path) {
+    if (!ix || !path) return fail(MOVI_ERR_ARG, "NULL argument");
+    FILE *f = fopen(path, "rb");
+    if (!f)       // deserialize_sampled_SA, src/move_structure_io.cpp:724-730
+        return fail(MOVI_ERR_IO, std::string("Failed to open sampled SA entries file at ") + path + "\nBuild the sampled SA by running the build-SA command.");
+    uint64_t rate = 0, entries = 0, r = 0;
+    std::vector<uint64_t> samples;
+    bool ok = read_exact(f, &rate, 8) && read_exact(f, &entries, 8);
+    const bool shape = ok && rate != 0 && entries == ix->desc.length / rate + 1;
+    if (shape) {
+        samples.resize(entries);
+        ok = read_exact(f, samples.data(), entries * 8) && read_exact(f, &r, 8);
+        if (ok && r == ix->desc.r) {                                   // all_p[r] follows and ends the file (its values are not read)
+            const long at = ftell(f);
+            ok = at >= 0 && fseek(f, 0, SEEK_END) == 0 && (uint64_t)ftell(f) == (uint64_t)at + r * 8;
+        }
+    }
+    fclose(f);
+    if (!ok) return fail(MOVI_ERR_FORMAT, std::string(path) + " is truncated");
+    if (!shape) return fail(MOVI_ERR_FORMAT, std::string(path) + ": rate " + std::to_string(rate) + " with " + std::to_string(entries) +
+                                                 " entries does not fit a text of " + std::to_string(ix->desc.length) + " positions");
+    if (r != ix->desc.r) return fail(MOVI_ERR_FORMAT, std::string(path) + " was built for an index of " + std::to_string(r) + " rows, this one has " + std::to_string(ix->desc.r));
+    HIP_TRY(hipSetDevice(ix->device));
+    // (the file's all_p is not read: the locate rows hold the same prefix sums, recomputed from the table on the device)
+    if (int rc = attach_ssa(ix, rate, nullptr)) return rc;
+    const hipError_t e = hipMemcpy(ix->d_samples, samples.data(), entries * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { detach_ssa(ix); return fail_hip(e, "uploading the sampled suffix array"); }
+    return MOVI_OK;
+}
+
+int movi_locate_device(movi_index_t *ix, uint64_t *d_positions_inout, uint64_t n_items, void *stream) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (!ix->sa_rate) return fail(MOVI_ERR_ARG, kNoSsa);
+    if (n_items == 0) return MOVI_OK;
+    if (!d_positions_inout) return fail(MOVI_ERR_ARG, "NULL device buffer");
+    HIP_TRY(hipSetDevice(ix->device));
+    return locate_device(ix, d_positions_inout, n_items, static_cast<hipStream_t>(stream), ix->d_stats, true);
+}
+
+int movi_sa_entries_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                           uint16_t *d_out_pml, uint64_t *d_out_sa, uint8_t *d_read_err, const uint32_t *d_read_order, void *stream) {
+    return sa_entries_device(ix, d_bases, d_offsets, n_reads, n_bases, d_out_pml, d_out_sa, d_read_err, d_read_order,
+                             static_cast<hipStream_t>(stream), nullptr);
+}
+
+int movi_sa_entries_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint16_t *h_out_pml,
+                         uint64_t *h_out_sa, uint8_t *h_read_err, movi_query_stats_t *stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (!mode_has_thresholds(ix->desc.mode))
+        return fail(MOVI_ERR_ARG, "--sa-entries rides on the PML walk, which needs thresholds: use a *-thresholds index");
+    if (!ix->sa_rate) return fail(MOVI_ERR_ARG, kNoSsa);
+    if (n_reads == 0) return MOVI_OK;
+    if (!h_offsets || (h_offsets[n_reads] != h_offsets[0] && (!h_bases || !h_out_sa))) return fail(MOVI_ERR_ARG, "NULL host buffer");
+    if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
+    HIP_TRY(hipSetDevice(ix->device));
+    struct { void *p; } d_pml{}, d_sa{};
+    auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
+        if (h_out_pml) HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_pml.p));
+        HIP_TRY(c.alloc(movi_index::kS, nb * 8, &d_sa.p));
+        return sa_entries_device(ix, db, dof, nr, nb, h_out_pml ? static_cast<uint16_t *>(d_pml.p) : nullptr, static_cast<uint64_t *>(d_sa.p),
+                                 derr, nullptr, c.s, c.d_stats);
+    };
+    auto fetch = [&](ChunkCtx &c, uint64_t, uint64_t, uint64_t b0, uint64_t nb) -> int {
+        if (h_out_pml) HIP_TRY(c.down(h_out_pml + b0, d_pml.p, nb * 2));
+        HIP_TRY(c.down(h_out_sa + b0, d_sa.p, nb * 8));
+        return MOVI_OK;
+    };
+    auto harvest = [](const uint8_t *, uint64_t, uint64_t, HostPool::Group *) {};
+    // (chunk by chunk, synchronously: 8 bytes per base come down, the locate walk is ~100 gathers per base -- nothing to overlap)
+    return run_host(false, ix, h_bases, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest, 0);
 }
 
 }  // extern "C"

@@ -367,6 +367,33 @@ hipError_t launch_kmer(int mode, const DevIndex &ix, const KmerArgs &a, const ui
                        uint64_t n_reads, KmerRun *d_runs, uint32_t *d_n_runs, uint32_t *d_found, uint8_t *d_err,
                        DevStats *d_stats, const uint32_t *d_order, hipStream_t stream, LaunchInfo *info);
 
+// Locate (movi_walk_sa.hip; MoveStructure::get_SA_entries, src/move_structure.cpp:35-48; the layouts are stated in movi_sa.hpp).
+constexpr int kLocateWaves = 16;     // locate_kernel: one-wavefront blocks per CU a launch fills at most (a lane then owns a list of items)
+struct LocArgs {
+    const uint4 *rows = nullptr;        // the locate rows: 16 bytes per row
+    const uint64_t *samples = nullptr;  // n / rate + 1 entries (not read in successor mode)
+    uint64_t n = 0;                     // BWT length: no walk is longer
+    uint64_t n_entries = 0;             // sample indexes are below this
+    uint32_t rate = 0;
+    uint32_t succ = 0;                  // 1 = successor mode: one LF step first; out = the sample's index, aux = the distance
+    uint64_t *aux = nullptr;
+};
+uint64_t locate_rows_bytes(uint64_t r);
+// d_loc: locate_rows_bytes(r) bytes; *n_total (host, optional) = the sum of the row lengths.  Allocates its scan's scratch and waits.
+hipError_t build_locate_rows(int mode, const DevIndex &ix, uint64_t rate, uint4 *d_loc, uint64_t *n_total, hipStream_t stream);
+hipError_t locate_rows_all_p(const uint4 *d_loc, uint64_t first, uint64_t cnt, uint64_t rate, uint64_t *d_all_p, hipStream_t stream);
+// In place: d_pos[i] = a packed position in, its suffix-array entry out (successor mode: see LocArgs).
+hipError_t launch_locate(int mode, const DevIndex &ix, const LocArgs &a, uint64_t *d_pos, uint64_t n_items, DevStats *d_stats,
+                         int num_cus, hipStream_t stream, LaunchInfo *info);
+// The PML walk that records its positions (mode-6 rows): d_pml optional, d_pos[offsets[i] + k] = position after base len - 1 - k.
+hipError_t launch_sa_pos(const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint16_t *d_pml,
+                         uint64_t *d_pos, uint8_t *d_err, DevStats *d_stats, const uint32_t *d_order, hipStream_t stream, LaunchInfo *info);
+// d_samples: loc.n / loc.rate + 1 entries.  *bad (host) = findings that one cycle over all samples cannot produce (0 = the array is
+// complete).  Allocates its scratch and waits.
+hipError_t build_sampled_sa(int mode, const DevIndex &ix, const LocArgs &loc, uint64_t *d_samples, DevStats *d_stats, int num_cus,
+                            hipStream_t stream, uint32_t *bad, LaunchInfo *info);
+hipError_t preload_sa(int mode, bool idx32);   // load the translation unit's code object now (movi_index_prepare)
+
 // Compaction of per-read results of variable length (the host path of both): d_first[0..n] = exclusive prefix of the counts d_n
 // (d_first[n] = their total); then read i's d_n[i] elements of elem_bytes (8 or 16) from d_src[d_offsets[i]..] to d_out[d_first[i]..].
 hipError_t launch_count_scan(const uint32_t *d_n, uint64_t n_reads, uint64_t *d_first, hipStream_t stream);

@@ -7,6 +7,8 @@ Reference seam (file:line under /root/reference) -> here:
   MoveStructure::query_backward_search src/move_structure_search.cpp:340  -> MoveIndex.query_count
   MoveStructure::query_mems           src/mem_finder.cpp:7-145           -> MoveIndex.query_mems
   MoveStructure::query_all_kmers      src/sequitur.cpp:322-421           -> MoveIndex.query_kmers
+  MoveStructure::get_SA_entries       src/move_structure.cpp:35-48       -> MoveIndex.locate / query_sa_entries
+  MoveStructure::find_sampled_SA_entries src/move_structure_build.cpp:1174 -> MoveIndex.build_ssa (save_ssa / load_ssa: ssa.movi)
 
 All compute happens in libmovi_hip.so on the GPU; this file only marshals
 buffers.  Errors are MoviError (the reference throws std::runtime_error).
@@ -148,9 +150,10 @@ class QueryStats:
 class MoveIndex:
     """A move-structure index resident on one GPU."""
 
-    def __init__(self, handle, keepalive=None):
+    def __init__(self, handle, keepalive=None, device=0):
         self._h = handle
         self._keep = keepalive
+        self.device = int(device)
         c = IndexDescC()
         check(lib().movi_index_get_desc(self._h, C.byref(c)))
         self.desc = IndexDesc(c)
@@ -160,7 +163,7 @@ class MoveIndex:
     def load(cls, index_dir_or_file, device=0):
         h = C.c_void_p()
         check(lib().movi_index_load(device, str(index_dir_or_file).encode(), C.byref(h)))
-        return cls(h)
+        return cls(h, device=device)
 
     @classmethod
     def from_image(cls, image, device=0):
@@ -168,14 +171,14 @@ class MoveIndex:
         _, c, off, _ = parse_index_image(buf)
         h = C.c_void_p()
         check(lib().movi_index_create(device, C.byref(c), buf.ctypes.data + off, C.byref(h)))
-        return cls(h)
+        return cls(h, device=device)
 
     @classmethod
     def from_device_rows(cls, cdesc, d_rows_ptr, device=0, keepalive=None):
         """Adopt a device-resident row table (e.g. an RCCL-broadcast torch tensor)."""
         h = C.c_void_p()
         check(lib().movi_index_create_from_device_rows(device, C.byref(cdesc), C.c_void_p(d_rows_ptr), C.byref(h)))
-        return cls(h, keepalive=keepalive)
+        return cls(h, keepalive=keepalive, device=device)
 
     @classmethod
     def load_replicated(cls, index_dir_or_file, devices):
@@ -185,7 +188,7 @@ class MoveIndex:
         devs = (C.c_int * n)(*[int(d) for d in devices])
         hs = (C.c_void_p * n)()
         check(lib().movi_index_load_replicated(str(index_dir_or_file).encode(), devs, n, hs))
-        return [cls(C.c_void_p(hs[i])) for i in range(n)]
+        return [cls(C.c_void_p(hs[i]), device=devices[i]) for i in range(n)]
 
     @classmethod
     def replicate_image(cls, image, devices):
@@ -196,7 +199,7 @@ class MoveIndex:
         devs = (C.c_int * n)(*[int(d) for d in devices])
         hs = (C.c_void_p * n)()
         check(lib().movi_index_replicate(C.byref(c), buf.ctypes.data + off, devs, n, hs))
-        return [cls(C.c_void_p(hs[i])) for i in range(n)]
+        return [cls(C.c_void_p(hs[i]), device=devices[i]) for i in range(n)]
 
     def close(self):
         if getattr(self, "_h", None):
@@ -388,6 +391,69 @@ class MoveIndex:
             j += c
         return out
 
+    # -- locate: sampled suffix array ---------------------------------------------
+    POS_OFFSET_BITS = 12          # MOVI_POS_PACK
+    POS_NONE = 0xFFFFFFFFFFFFFFFF
+
+    def build_ssa(self, rate=100, stream=0):
+        """movi_ssa_build: the sampled suffix array of `rate` (and the locate rows), built on the device and attached."""
+        check(lib().movi_ssa_build(self._h, int(rate), C.c_void_p(stream) if stream else None))
+
+    def save_ssa(self, path):
+        """movi_ssa_save: the attached array as the reference's ssa.movi."""
+        check(lib().movi_ssa_save(self._h, str(path).encode()))
+
+    def load_ssa(self, path):
+        check(lib().movi_ssa_load(self._h, str(path).encode()))
+
+    def ssa(self):
+        """(rate, the n / rate + 1 entries as uint64)."""
+        rate, n = C.c_uint64(0), C.c_uint64(0)
+        check(lib().movi_ssa_get(self._h, C.byref(rate), None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint64)
+        check(lib().movi_ssa_get(self._h, None, out.ctypes.data, out.size, None))
+        return int(rate.value), out
+
+    def locate(self, rows, offs):
+        """Suffix-array entries (uint64, not reduced modulo n) of the BWT positions (rows[i], offs[i]) of the resident table."""
+        import torch
+        pos = (np.asarray(rows, np.uint64) << np.uint64(self.POS_OFFSET_BITS)) | np.asarray(offs, np.uint64)
+        if pos.size == 0:
+            check(lib().movi_locate_device(self._h, None, 0, None))
+            return pos
+        with torch.cuda.device(self.device):
+            d = torch.from_numpy(pos.view(np.int64)).cuda()
+            self.locate_device(d.data_ptr(), pos.size)
+            st = self.last_stats()
+            out = d.cpu().numpy().view(np.uint64)
+        if st.errors:
+            from ._lib import MoviError
+            raise MoviError(-6, "%d position(s) are not positions of the table or hit a move-structure invariant violation "
+                                "(corrupt index?)" % st.errors)
+        return out
+
+    def query_sa_entries_packed(self, bases, offs, want_err=False, want_pml=True):
+        """movi_sa_entries_host -> (u64 entries in emission order, u16 PMLs or None, QueryStats[, err, rc])."""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        n = offs.size - 1
+        sa = np.zeros(bases.size, np.uint64)
+        pml = np.zeros(bases.size, np.uint16) if want_pml else None
+        err = np.zeros(max(n, 1), np.uint8)
+        st = QueryStatsC()
+        rc = lib().movi_sa_entries_host(self._h, bases.ctypes.data, offs.ctypes.data, n, pml.ctypes.data if want_pml else None,
+                                        sa.ctypes.data, err.ctypes.data, C.byref(st))
+        if want_err:
+            return sa, pml, QueryStats(st), err[:n], rc
+        check(rc)
+        return sa, pml, QueryStats(st)
+
+    def query_sa_entries(self, reads):
+        """`movi query --sa-entries` per read: list of uint64 arrays, last base first like the PMLs."""
+        bases, offs = _pack_reads(reads)
+        sa, _, _ = self.query_sa_entries_packed(bases, offs, want_pml=False)
+        return [sa[int(offs[i]): int(offs[i + 1])] for i in range(len(reads))]
+
     # -- device-pointer queries (bench / torch interop) ---------------------------
     def pml_device(self, d_bases, d_offs, n_reads, n_bases, d_out, d_err=0, stream=0, d_order=0):
         check(lib().movi_pml_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offs), n_reads, n_bases,
@@ -446,7 +512,18 @@ class MoveIndex:
                                      C.c_void_p(d_order) if d_order else None,
                                      C.c_void_p(stream) if stream else None))
 
-    PREPARE_PML, PREPARE_COUNT, PREPARE_ZML = 1, 2, 4
+    def locate_device(self, d_pos, n_items, stream=0):
+        """movi_locate_device: packed positions in, suffix-array entries out, in place."""
+        check(lib().movi_locate_device(self._h, C.c_void_p(d_pos), n_items, C.c_void_p(stream) if stream else None))
+
+    def sa_entries_device(self, d_bases, d_offs, n_reads, n_bases, d_sa, d_pml=0, d_err=0, stream=0, d_order=0):
+        check(lib().movi_sa_entries_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offs), n_reads, n_bases,
+                                           C.c_void_p(d_pml) if d_pml else None, C.c_void_p(d_sa),
+                                           C.c_void_p(d_err) if d_err else None,
+                                           C.c_void_p(d_order) if d_order else None,
+                                           C.c_void_p(stream) if stream else None))
+
+    PREPARE_PML, PREPARE_COUNT, PREPARE_ZML, PREPARE_SA = 1, 2, 4, 8
 
     def prepare(self, what=1 | 2 | 4, stream=0):
         """movi_index_prepare: build the handle's derived tables now (not inside the first query); returns their bytes."""

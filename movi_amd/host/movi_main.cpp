@@ -208,6 +208,7 @@ struct Job {
     std::vector<movi_mem_t> mems;                                     // ... and all of them, read by read (file order)
     std::vector<uint32_t> n_runs, kmers_found;                        // --kmer: runs and found k-mers per read ...
     std::vector<movi_kmer_run_t> runs;                                // ... and all the runs, read by read (file order)
+    std::vector<uint64_t> sa;                                         // --sa-entries: one suffix-array entry per base, emission order like pml
     std::vector<uint8_t> err;                                         // per-read error byte
     RawBytes original;                                                // reads as given (--filter after --ignore-illegal-chars 1)
     std::vector<uint32_t> bins_above, bins_below;                     // verdict-only classification
@@ -272,6 +273,9 @@ std::unique_ptr<BatchReader> open_reader(const std::string &path, std::istream &
 }
 
 int run_query(const Options &o) {
+    if (o.sa_entries && !std::ifstream(o.index_dir + "/ssa.movi").good())      // deserialize_sampled_SA, src/move_structure_io.cpp:727-730
+        throw std::runtime_error("[deserialize sampled SA] Failed to open sampled SA entries file at " + o.index_dir + "/ssa.movi" +
+                                 "\nBuild the sampled SA by running the build-SA command.");
     int n_dev = 0;
     check(movi_device_count(&n_dev), "no usable GPU");
     if (n_dev < 1) throw EngineError("no usable GPU: the MI355X engine has no CPU fallback");
@@ -357,6 +361,8 @@ int run_query(const Options &o) {
         // serve as N ranks): N independent loads, so that the read sharding and the per-GPU host threads can be exercised
         for (int g = 0; g < o.gpus; g++) check(movi_index_load(dev_of(g), o.index_dir.c_str(), &handles[(size_t)g]), "loading the index");
     }
+    if (o.sa_entries)                                                  // deserialize_sampled_SA, src/move_structure_io.cpp:724-744 (every GPU holds the samples beside its table)
+        for (auto *hd : handles) check(movi_ssa_load(hd, (o.index_dir + "/ssa.movi").c_str()), "loading the sampled suffix array");
     if (o.seg_len >= 0)
         for (auto *hd : handles) check(movi_set_option(hd, "seg_len", o.seg_len), "--seg-len");
     // (the ZML parse does not walk on the look-ahead rows unless "zml_ahead" asks for it: `--zml --ahead-rows 1` builds nothing)
@@ -382,7 +388,7 @@ int run_query(const Options &o) {
     // 14 M-row index hides and a 1 B-row one does not (bench.py big_table.cli_path: 0.31 s of "processing" for 0.03 s of work).
     for (auto *hd : handles) {                                         // (errors here are not the query's: the real calls report)
         if (o.pml && o.logs) continue;                                 // --logs runs on the first kernel, which uses none of the derived tables
-        (void)movi_index_prepare(hd, o.pml ? MOVI_PREPARE_PML : (o.zml ? MOVI_PREPARE_ZML : MOVI_PREPARE_COUNT), nullptr, nullptr);   // (--mem: the count tables)
+        (void)movi_index_prepare(hd, o.sa_entries ? MOVI_PREPARE_SA : o.pml ? MOVI_PREPARE_PML : (o.zml ? MOVI_PREPARE_ZML : MOVI_PREPARE_COUNT), nullptr, nullptr);   // (--mem: the count tables; --sa-entries: its own walk, no table of the PML walk)
         // ... and so is the device staging of a chunk's host call (three hipMallocs: 1.2 ms of the first chunk's 3 ms call otherwise):
         // a chunk's bases with the slack of its last batch, its result vector when one comes back, reads down to 64 bases long
         const int64_t cb = (int64_t)std::min<uint64_t>(chunk_bases + (chunk_bases >> 3), 1ull << 31) / (o.gpus > 0 ? o.gpus : 1);
@@ -407,7 +413,7 @@ int run_query(const Options &o) {
     Classifier classifier;
     // stream buffers first: they must outlive the streams that flush through them on destruction
     std::vector<char> out_buf2(1u << 20);
-    std::ofstream report_file, matches_file;
+    std::ofstream report_file, matches_file, sa_file;
     std::unique_ptr<WorkerPool> bpf_pool;                             // the writer stage's helper threads (record order, BPF gather; built by the writer thread, outlives mls_file)
     BpfWriter mls_file;
     matches_file.rdbuf()->pubsetbuf(out_buf2.data(), (std::streamsize)out_buf2.size());
@@ -439,6 +445,10 @@ int run_query(const Options &o) {
         } else if (o.ml()) {
             prefix += "." + o.query_type();
             mls_file.open(prefix + ".bpf", 16);
+            if (o.sa_entries) {                                       // src/utils.cpp:371-375: opened with the PML file, no BPF header
+                sa_file.open(prefix + ".sa_entries.bpf", std::ios::out | std::ios::binary);
+                if (!sa_file.good()) throw std::runtime_error("Failed to open the output file: " + prefix + ".sa_entries.bpf");
+            }
         } else {
             prefix += "." + o.query_type();
             matches_file.open(prefix + ".matches");
@@ -552,6 +562,14 @@ int run_query(const Options &o) {
         } else {
             order.resize(n);
             for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+        }
+        if (sa_file.is_open()) {                                      // output_base_stats(DataType::sa_entry), src/utils.cpp:212-246: the PML records' order
+            std::string rec;
+            for (uint32_t i : order) {
+                rec.clear();
+                append_sa_record(rec, rs.id(i), job.sa.data() + rs.offsets[i], rs.len(i));
+                sa_file.write(rec.data(), (std::streamsize)rec.size());
+            }
         }
         std::vector<BpfWriter::Record> bpf;                           // the chunk's records, in emission order
         const bool to_bpf = o.ml() && o.write_output_allowed() && !o.write_stdout_enabled();
@@ -694,6 +712,7 @@ int run_query(const Options &o) {
             if (o.pml && o.logs) continue;                             // --logs runs on the first kernel, which uses none of the derived tables
             if (o.pml && o.classify && !o.write_output_allowed())
                 (void)movi_pml_classify_host(hd, wb, wo, 1, (uint32_t)o.bin_width, classifier.max_value_thr, &wa, &wbl, &wsum, &we, nullptr);
+            else if (o.sa_entries) { uint64_t wsa[32]; (void)movi_sa_entries_host(hd, wb, wo, 1, wp, wsa, &we, nullptr); }
             else if (o.pml) (void)movi_pml_host(hd, wb, wo, 1, wp, &we, nullptr);
             else if (o.zml) (void)movi_zml_host(hd, wb, wo, 1, wp, &we, nullptr);
             else if (o.mem) {
@@ -739,6 +758,7 @@ int run_query(const Options &o) {
         const bool walk_only = o.ml() && !o.classify && !o.write_output_allowed();
         job.pml.ensure(o.ml() && !verdict_only && !walk_only ? rs.bases.size() : 0, pin_this_chunk(rs.bases.size() * 2));
         if (logs) { job.log_ff.resize(rs.bases.size()); job.log_scan.resize(rs.bases.size()); }
+        if (o.sa_entries) job.sa.resize(rs.bases.size());
         job.matched.assign(o.count ? n : 0, 0);
         job.counts.assign(o.count ? n : 0, 0);
         job.n_mems.assign(o.mem ? n : 0, 0);
@@ -761,6 +781,9 @@ int run_query(const Options &o) {
             else if (o.pml && logs)
                 rc = movi_pml_logs_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, job.pml.data(), job.log_ff.data(),
                                         job.log_scan.data(), job.err.data() + a, nullptr);
+            else if (o.sa_entries)                                    // (--no-output: computed and discarded, as the reference does)
+                rc = movi_sa_entries_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, walk_only ? nullptr : job.pml.data(),
+                                          job.sa.data(), job.err.data() + a, nullptr);
             else if (o.pml)
                 rc = movi_pml_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, walk_only ? nullptr : job.pml.data(),
                                    job.err.data() + a, nullptr);
@@ -830,6 +853,7 @@ int run_query(const Options &o) {
     if (write_error) std::rethrow_exception(write_error);
     if (parse_error) std::rethrow_exception(parse_error);
     mls_file.close();
+    if (sa_file.is_open()) sa_file.close();
     // (the parser's warm-up touched the input before t1: its seconds count as read processing, although they ran beside the index load)
     const double total = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count() + warm_seconds;
     std::cerr << "[movi] " << reads_done << " reads are processed.\n";
@@ -899,6 +923,25 @@ int run_null(const Options &o) {
     return 0;
 }
 
+// `movi build-SA` (src/movi.cpp:640-..., find_sampled_SA_entries + serialize_sampled_SA): INDEX/ssa.movi from index.movi alone --
+// nothing is fetched from the text; the array is built on the GPU (movi_ssa_build).
+int run_build_sa(const Options &o) {
+    const auto t0 = std::chrono::steady_clock::now();
+    movi_index_t *h = nullptr;
+    check(movi_index_load(o.device, o.index_dir.c_str(), &h), "loading the index");
+    struct Closer { movi_index_t *h; ~Closer() { movi_index_destroy(h); } } closer{h};
+    const auto t1 = std::chrono::steady_clock::now();
+    check(movi_ssa_build(h, o.sample_rate, nullptr), "building the sampled suffix array");
+    const auto t2 = std::chrono::steady_clock::now();
+    const std::string name = o.index_dir + "/ssa.movi";
+    check(movi_ssa_save(h, name.c_str()), "writing ssa.movi");
+    uint64_t n_samples = 0;
+    check(movi_ssa_get(h, nullptr, nullptr, 0, &n_samples), "the sampled suffix array");
+    std::cerr << "[movi] " << n_samples << " sampled SA entries (sample rate " << o.sample_rate << ") written to " << name << " (index load "
+              << std::chrono::duration<double>(t1 - t0).count() << " s, build " << std::chrono::duration<double>(t2 - t1).count() << " s)\n";
+    return 0;
+}
+
 // `movi plan`: the host-side batching + record order, without any GPU work.
 int run_plan(const Options &o) {
     std::ifstream file_in;
@@ -941,6 +984,7 @@ int main(int argc, char **argv) {
         if (o.command == "plan") return run_plan(o);
         if (o.command == "null") return run_null(o);
         if (o.command == "build") return run_build(o);
+        if (o.command == "build-SA") return run_build_sa(o);
         return run_query(o);
     } catch (const UsageError &e) {
         std::cerr << "Error parsing command line options: " << e.what() << "\n" << usage();

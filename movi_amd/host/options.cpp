@@ -28,7 +28,7 @@ const Spec kSpecs[] = {
     {"device", 0, true},         {"type", 0, true},         {"debug", 'd', false},
     {"logs", 0, false},          {"mmap", 0, false},        {"gen-reads", 0, false},
     {"fasta", 'f', true},          {"separators", 0, false},  {"seg-len", 0, true},
-    {"ahead-rows", 0, true},
+    {"ahead-rows", 0, true},        {"sample-rate", 0, true},
     // recognised but unsupported query types / features
     {"zml", 0, false},           {"mem", 0, false},         {"rpml", 0, false},
     {"kmer", 0, false},          {"kmer-count", 0, false},  {"sa-entries", 0, false},
@@ -64,6 +64,8 @@ std::string usage() {
            "                      [--reverse] [--ignore-illegal-chars 1] [--gpus N] [--device D]\n"
            "       movi query -i DIR -r FILE|- --kmer [-k K] [--ftab-k K'] [-o PREFIX] [--stdout] [--no-output]\n"
            "                      [--reverse] [--ignore-illegal-chars 1] [--gpus N] [--device D]   (--kmer-count, --rpml: not supported)\n"
+           "       movi query -i DIR -r FILE|- --sa-entries [-o PREFIX] [--no-output] ...   (PML + <prefix>.sa_entries.bpf; after build-SA)\n"
+           "       movi build-SA -i DIR [--sample-rate N] [--device D]\n"
            "       movi view --bpf FILE\n"
            "       movi null -i DIR [--gen-reads -f REF.fasta] [--pml|--zml]\n"
            "       movi build -i DIR -f REF.fasta [--type regular-thresholds|blocked-thresholds|sampled-thresholds|regular|blocked|sampled]\n"
@@ -122,10 +124,10 @@ Options parse_args(int argc, char **argv) {
         o.index_dir = val("index");
         o.read_file = val("read");
         if (has("out-file")) o.out_file = val("out-file");
-        for (const char *bad : {"rpml", "kmer-count", "sa-entries", "multi-classify", "multi-ftab"})
+        for (const char *bad : {"rpml", "kmer-count", "multi-classify", "multi-ftab"})
             if (has(bad))
                 throw UsageError(std::string("--") + bad + " is not supported by the MI355X engine (PML, ZML, count, MEM and "
-                                 "k-mer presence queries only)");
+                                 "k-mer presence queries, and --sa-entries with PML, only)");
         // --mmap (src/movi_parser.cpp: "Use memory mapping to read the index") is accepted and implied: movi_index_load
         // always maps the file and uploads the rows straight from the page cache
                 if (has("bin-width")) o.bin_width = (size_t)to_int("bin-width", val("bin-width"));
@@ -180,6 +182,13 @@ Options parse_args(int argc, char **argv) {
         }
         if (o.gpus < 1) throw UsageError("--gpus must be >= 1");
         if (o.classify && o.count) throw UsageError("--classify needs PML or ZML queries");
+        if (has("sample-rate")) throw UsageError("--sample-rate belongs to build-SA: a query takes the rate from ssa.movi");
+        o.sa_entries = has("sa-entries");
+        if (o.sa_entries) {
+            // (the reference opens an empty .sa_entries.bpf beside the other query types' files: only query_pml records entries)
+            if (!o.pml) throw UsageError("--sa-entries reports the positions of the PML walk: it cannot be combined with --zml, --count, --mem or --kmer");
+            if (o.classify || o.logs) throw UsageError("--sa-entries cannot be combined with --classify, --filter or --logs");
+        }
         if (o.kmer) {
             if (o.classify || o.logs) throw UsageError("--kmer cannot be combined with --classify, --filter or --logs");
             if (o.k == 0) throw UsageError("-k / --k-length must be at least 1");
@@ -220,13 +229,26 @@ Options parse_args(int argc, char **argv) {
         o.ref_file = val("fasta");
         if (has("type")) o.index_type = val("type");
         o.separators = has("separators");
+    } else if (o.command == "build-SA") {
+        // src/movi_parser.cpp:308-317
+        if (seen["index"].size() != 1) throw UsageError("Please specify the index directory file.");
+        o.index_dir = val("index");
+        if (has("sample-rate")) {
+            const std::string v = val("sample-rate");
+            char *end = nullptr;
+            const unsigned long long x = std::strtoull(v.c_str(), &end, 10);
+            if (v.empty() || v[0] == '-' || (end && *end)) throw UsageError("Argument '" + v + "' failed to parse for option 'sample-rate'");
+            if (x == 0 || x > (1ull << 24)) throw UsageError("--sample-rate must be between 1 and 16777216");
+            o.sample_rate = x;
+        }
+        if (has("device")) o.device = (int)to_int("device", val("device"));
     } else if (o.command == "view") {
         if (seen["bpf"].size() != 1) throw UsageError("Please specify one mls file.");
         o.bpf_file = val("bpf");
         o.small_bpf = has("small-bpf");
         o.large_bpf = has("large-bpf");
     } else {
-        throw UsageError("The '" + o.command + "' action is not part of the MI355X engine (query, view, null and build only); use "
+        throw UsageError("The '" + o.command + "' action is not part of the MI355X engine (query, view, null, build and build-SA only); use "
                          "the reference movi for inspect / color / ftab.");
     }
     return o;

@@ -10,7 +10,7 @@
 namespace movi_host {
 
 struct Options {
-    std::string command;          // "query" | "view" | "null" | "plan"
+    std::string command;          // "query" | "view" | "null" | "plan" | "build" | "build-SA"
     std::string index_dir;        // -i / --index
     std::string read_file;        // -r / --read ("-" = stdin)
     std::string out_file;         // -o / --out-file
@@ -24,6 +24,8 @@ struct Options {
     bool zml = false;             // --zml: Ziv-Merhav cross parse lengths, same outputs as PML
     bool mem = false;             // --mem: maximal exact matches (src/mem_finder.cpp), one line per MEM
     bool kmer = false;            // --kmer: k-mer presence (src/sequitur.cpp:322-421), one line per read
+    bool sa_entries = false;      // --sa-entries: one suffix-array entry per base beside the PML file (needs INDEX/ssa.movi: build-SA)
+    uint64_t sample_rate = 100;   // build-SA --sample-rate (movi_options.hpp: SA_sample_rate)
     uint32_t k = 31;              // -k / --k-length (movi_options.hpp:254)
     uint32_t min_mem_length = 25; // -l / --min-mem-length (movi_options.hpp:255)
     long ftab_k = -1;             // --ftab-k K: the engine's interval table at min(K, 12) ("ftab_k"); -1 = not given

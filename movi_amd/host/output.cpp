@@ -345,6 +345,14 @@ void append_mem_line(std::string &txt, std::string_view id, const movi_mem_t &m)
     txt.push_back('\n');
 }
 
+void append_sa_record(std::string &out, std::string_view id, const uint64_t *entries, uint64_t count) {
+    const uint16_t st_length = (uint16_t)id.size();                   // (the reference's uint16_t conversion of the id's length)
+    out.append(reinterpret_cast<const char *>(&st_length), sizeof(st_length));
+    out.append(id.data(), st_length);
+    out.append(reinterpret_cast<const char *>(&count), sizeof(count));
+    if (count) out.append(reinterpret_cast<const char *>(entries), count * sizeof(uint64_t));
+}
+
 // output_kmers, src/utils.cpp:258-266: `id<TAB>found/all<TAB>` and MoveQuery::add_kmer's string (move_query.hpp:12-19), every
 // `start:count` pair followed by a space.  all = query length - k + 1 as the reference computes it (src/movi.cpp:87): in
 // 64-bit unsigned arithmetic, so a read shorter than k prints the wrapped value.

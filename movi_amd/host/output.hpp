@@ -64,6 +64,9 @@ void append_stdout_pmls(std::string &txt, std::string_view id, const uint16_t *p
 void write_count_line(std::ostream &out, std::string_view id, uint64_t query_length, uint64_t matched, uint64_t count);
 void append_count_line(std::string &txt, std::string_view id, uint64_t query_length, uint64_t matched, uint64_t count);
 // one k-mer line (output_kmers, src/utils.cpp:258-266): `id<TAB>found/all<TAB>start:count start:count <LF>`, all = len - k + 1 in u64
+// One record of <prefix>.sa_entries.bpf (output_base_stats with DataType::sa_entry, src/utils.cpp:212-246; the file has no BPF header):
+// u16 id length, the id, u64 count, count x u64 -- the entries in emission order, like the PML record of the same read.
+void append_sa_record(std::string &out, std::string_view id, const uint64_t *entries, uint64_t count);
 void append_kmer_line(std::string &txt, std::string_view id, uint64_t query_length, uint32_t k, uint64_t found,
                       const movi_kmer_run_t *runs, uint64_t n_runs);
 void append_mem_line(std::string &txt, std::string_view id, const movi_mem_t &m);   // one MEM line (output_mems, count as u16)   // the same line, appended
