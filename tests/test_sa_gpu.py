@@ -82,7 +82,8 @@ def test_exhaustive_locate(texts, tmp_path, sep, mode):
 
 
 def test_multi_genome_text(built_lib, tmp_path):
-    """The 8-genome text of test_mem_gpu.py::test_text_not_closed_under_rc."""
+    """The 8-genome text of test_mem_gpu.py::test_text_not_closed_under_rc.
+    (Independent genomes: repetitive texts -- a pangenome, long runs, tandem repeats -- are in tests/test_odd_texts_gpu.py.)"""
     import movi_amd
     from oracle import build_index as B
     rng = np.random.default_rng(8181)
