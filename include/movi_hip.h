@@ -21,6 +21,9 @@
  *   MoveStructure::get_SA_entries  src/move_structure.cpp:35-48  movi_locate_device / movi_sa_entries_host / movi_sa_entries_device
  *   MoveStructure::find_sampled_SA_entries  src/move_structure_build.cpp:1174-1212  movi_ssa_build
  *   MoveStructure::serialize_sampled_SA / deserialize_sampled_SA  src/move_structure_io.cpp:710-744  movi_ssa_save / movi_ssa_load
+ *   MoveStructure::build_doc_pats / build_doc_sets  src/move_structure_color.cpp:4-72  movi_color_build
+ *   MoveStructure::flat_and_serialize_colors_vectors / deserialize_doc_sets_flat  src/move_structure_io.cpp:513-548,587-607  movi_color_save / movi_color_load
+ *   ReadProcessor::process_char (multi-classify)  src/read_processor.cpp:122-186  movi_multi_classify_host / movi_multi_classify_device
  *   MoveQuery::add_ml / matching_lens  include/move_query.hpp:26-38 (filled by process_char, src/read_processor.cpp:193-215)
  *                                                                       movi_pml_mask_device / movi_pml_mask_host (one reset bit per base)
  *                                                                       + movi_pml_expand_device / movi_pml_expand_host (bits -> u16 vector)
@@ -279,7 +282,8 @@ int movi_launch_log(char *buf, size_t cap, size_t *needed);
 /* What the handle holds in HBM besides the row table, and what its builders measured (no reference counterpart; the
  * derived tables of "kmer_k" / "ahead_rows" / "ftab_k" are built by the first query that can use them, so this is how a
  * caller sees their cost).  Keys: "rows_bytes" (the resident row table), "kmer_bytes", "ftab_bytes", "ahead_rows_bytes",
- * "ckpt_bytes" (0 = not built), "locate_bytes" (the locate rows and the samples of an attached sampled suffix array), "derived_bytes" (their sum), "ahead_no_ff" (share of the table's BWT
+ * "ckpt_bytes" (0 = not built), "color_bytes" (attached colour tables), "color_taxa" (to_taxon_id entries held), "color_chunks" and
+ * "color_walk_seconds" / "color_sort_seconds" / "color_number_seconds" (the last movi_color_build), "locate_bytes" (the locate rows and the samples of an attached sampled suffix array), "derived_bytes" (their sum), "ahead_no_ff" (share of the table's BWT
  * positions that reach their LF target without a fast-forward, tallied when the look-ahead rows are built: 0.83 on the
  * pangenome BWT, 0.51 on a uniformly random run sequence; -1 = not tallied yet), "device_scratch_bytes" (device scratch the
  * *_device calls hold: movi_pml_device's mask words -- retired buffers that captured graphs may still use included --, the u16 vector
@@ -549,6 +553,67 @@ int movi_sa_entries_device(movi_index_t *ix, const uint8_t *d_bases, const uint6
  * that breaks an invariant makes the call return MOVI_ERR_INVARIANT after everything else was answered. */
 int movi_sa_entries_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint16_t *h_out_pml,
                          uint64_t *h_out_sa, uint8_t *h_read_err, movi_query_stats_t *stats);
+
+/* ---- Movi Color: multi-class classification, default colour mode ---------------- */
+
+/* `movi color`, `movi build --color` and `movi query --multi-classify`: which documents (species) a read comes from.
+ *
+ * Terms.  The indexed text is a concatenation of n_docs documents; doc_offsets[i] is the text position where document i ends
+ * (exclusive; DIR/ref.fa.doc_offsets, load_document_info, src/move_structure_io.cpp:643-657).  The document of text position t is the
+ * first i with t < doc_offsets[i]; what lies past the last end -- the terminator -- belongs to the last document
+ * (build_doc_pats, src/move_structure_color.cpp:4-24).  doc_ids[i] (DIR/ref.fa.doc_ids; NULL: i + 1) is the taxon of document i; the
+ * taxa in use, ascending, are numbered 0 .. num_species - 1 and to_taxon_id maps back (:659-687).  The set of a run is the set of
+ * numbers of the documents its BWT positions lie in (build_doc_sets, src/move_structure_color.cpp:27-72).
+ * The colour tables (flat_and_serialize_colors_vectors, src/move_structure_io.cpp:513-548): flat_colors, u16, every distinct set
+ * stored once as its size followed by its sorted members, sets in the order of the first run, in run order, that has them; and per run
+ * the offset of its set in flat_colors.  DIR/doc_sets_flat.bin is, byte for byte, u64 flat_colors_size | flat_colors | r offsets as
+ * 5-byte MoveTally (u32 low, u8 high: include/move_row.hpp:13-39; doc_set_flat_inds, include/move_structure.hpp:296).
+ *
+ * movi_color_build: the tables, from the index and the offsets alone.  The text position of every BWT position comes from the
+ * attached sampled suffix array; if none is attached one is built with movi_ssa_build at rate 100 and STAYS attached (replacing
+ * nothing; a later movi_ssa_build / movi_ssa_load replaces it as usual).  Every sample walks down the text to the previous one and
+ * writes the key (row << 16) | document of every position it passes; the keys are sorted and made unique on the device (hipCUB), in
+ * chunks of samples sized from hipMemGetInfo ("color_chunk_keys": at most this many positions per chunk); numbering equal sets in
+ * first-appearance order runs on the host.  Offsets must be strictly increasing and above 0 (MOVI_ERR_ARG: the reference's
+ * one-step-per-position rule and a search agree only then); at most 65535 distinct taxa.  MOVI_ERR_INVARIANT if the walks do not visit
+ * every BWT position exactly once, or a run is left without a document: never a wrong table.  A table of 2^31 - 1 rows or more is
+ * MOVI_ERR_ARG, as for the sampled suffix array.  Replaces attached tables.  Waits.
+ * movi_color_save / movi_color_load: DIR/doc_sets_flat.bin.  Loading checks the file's length against r and every run's set against
+ * the table and num_species (MOVI_ERR_FORMAT); a missing file is MOVI_ERR_IO with the reference's message naming the path.
+ * movi_color_get: the tables as held (any pointer may be NULL; a cap too small: MOVI_ERR_ARG); h_inds as u64; h_to_taxon_id is known
+ * after a build only (0 entries after a load). */
+#define MOVI_PREPARE_COLOR 16u  /* movi_index_prepare: reserves the counter scratch of movi_multi_classify_device ("color_scratch_bytes",
+                                   default 256 MB, at least one read's counters) and loads its kernel; without attached colour tables
+                                   MOVI_ERR_ARG */
+int movi_color_build(movi_index_t *ix, const uint64_t *doc_offsets, const uint32_t *doc_ids, uint64_t n_docs, void *stream);
+int movi_color_save(movi_index_t *ix, const char *path);
+int movi_color_load(movi_index_t *ix, const char *path, uint32_t num_species);
+int movi_color_get(const movi_index_t *ix, uint64_t *flat_size, uint16_t *h_flat, uint64_t flat_cap, uint64_t *h_inds, uint64_t inds_cap,
+                   uint32_t *num_species, uint32_t *h_to_taxon_id, uint64_t taxa_cap);
+
+/* The PML query with ReadProcessor::process_char's multi-class scoring (src/read_processor.cpp:122-186) fused into the walk.  For
+ * every base, last base first: the LF step (not at the read's first base); then, BEFORE the base is compared, if the match length
+ * carried over from the base before is >= min_len (0 .. 255): colors_count += 1, and for every member d of the set of the row the
+ * walk stands on, in stored order: counter[d] += 1, and if d is not the best document it becomes the best one (the old best
+ * becoming second) when there is none or its counter is STRICTLY greater than the best's, else the second when there is none or its
+ * counter is strictly greater than the second's.  (A flat offset >= flat_colors_size is skipped.)  Then the base is processed as in
+ * the PML walk and its match length added to sum_ml (uint32_t, as in the reference).  Ties are decided by the order of the bases
+ * and of the members, so one lane scores one read from end to end.
+ * d_out[i]: best / second (0xFFFF = none), colors_count, sum_ml, and the counters of best and second (0 where there is none).  d_counts (optional): num_species u32 per read, the counters; when
+ * NULL they live in the handle's scratch and the reads go through it in chunks of scratch / (4 * num_species) reads.  d_out_pml
+ * (optional) as movi_pml_device.  A read that hits one of the reference's throws reports its code in d_read_err, no document, zero
+ * counters and all-zero PMLs.  *-thresholds indexes with attached colour tables only (MOVI_ERR_ARG otherwise).  After
+ * movi_index_prepare(MOVI_PREPARE_COLOR) the call allocates and builds nothing and may be captured into a graph. */
+typedef struct movi_mc_read { uint16_t best, second; uint32_t colors_count, sum_ml, best_count, second_count, reserved_; } movi_mc_read_t;   /* 24 bytes */
+
+int movi_multi_classify_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                               uint32_t min_len, movi_mc_read_t *d_out, uint32_t *d_counts, uint16_t *d_out_pml, uint8_t *d_read_err,
+                               const uint32_t *d_read_order, void *stream);
+/* Host buffers in and out (h_counts, h_out_pml optional), chunk by chunk through the host loop like movi_count_host (overlapped where
+ * the reads are page-locked and no vector comes down).  Every chunk has counters of its own in its staging, so chunks in flight
+ * together do not meet: with h_counts its counter rows whole, without them scratch within "color_scratch_bytes". */
+int movi_multi_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint32_t min_len,
+                             movi_mc_read_t *h_out, uint32_t *h_counts, uint16_t *h_out_pml, uint8_t *h_read_err, movi_query_stats_t *stats);
 
 /* ---- page-locked host memory --------------------------------------------------- */
 

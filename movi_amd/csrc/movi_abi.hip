@@ -117,6 +117,19 @@ struct movi_index {
     uint4 *d_loc = nullptr;          // 16 bytes per row (movi_sa.hpp)
     uint64_t *d_samples = nullptr;   // length / sa_rate + 1 entries
     uint64_t sa_rate = 0;            // 0 = no sampled suffix array attached
+    // Movi Color: the attached colour tables (movi_color_build / movi_color_load), on the host as the file holds them and on the device
+    std::vector<uint16_t> color_flat;            // flat_colors
+    std::vector<uint64_t> color_inds;            // doc_set_flat_inds, r entries (empty = no tables attached)
+    std::vector<uint32_t> color_taxa;            // to_taxon_id of the build (empty after a load)
+    uint32_t color_species = 0;
+    uint16_t *d_color_flat = nullptr;
+    uint64_t *d_color_inds = nullptr;
+    uint32_t *d_color_scratch = nullptr;         // the counters of movi_multi_classify_device calls that ask for no counter rows
+    size_t color_scratch_cap = 0;
+    uint64_t color_scratch_bytes = 256ull << 20; // "color_scratch_bytes": what movi_index_prepare(MOVI_PREPARE_COLOR) reserves
+    uint64_t color_chunk_keys = 0;               // "color_chunk_keys": BWT positions per chunk of the builder (0 = by the device's free memory)
+    uint32_t color_chunks = 0;                   // what the last build took
+    double color_seconds[3] = {0, 0, 0};         // ... and its seconds: walks, sorts, numbering
     DevIndex dev{};
     int kmode = 0;                   // row layout the kernels run on: desc.mode, except 6 for sampled-thresholds (expanded)
     LaunchCfg cfg;
@@ -173,7 +186,18 @@ struct movi_index {
 static void release_scratch(movi_index *ix);
 static const char *const kNoSsa = "no sampled suffix array is attached to this index: build one with movi_ssa_build (`movi build-SA`) or "
                                   "load ssa.movi with movi_ssa_load";
+static const char *const kNoColor = "no colour tables are attached to this index: build them with movi_color_build (`movi color`) or load "
+                                    "doc_sets_flat.bin with movi_color_load";
 namespace { hipError_t grow(void **p, size_t *cap, size_t bytes); }
+// The counters of one chunk of reads of movi_multi_classify_device: at least one read's row
+static hipError_t grow_color_scratch(movi_index *ix) {
+    const size_t want = std::max<size_t>((size_t)ix->color_scratch_bytes, (size_t)ix->color_species * 4);
+    if (ix->color_scratch_cap >= want) return hipSuccess;
+    void *p = ix->d_color_scratch;
+    const hipError_t e = grow(&p, &ix->color_scratch_cap, want);
+    ix->d_color_scratch = static_cast<uint32_t *>(p);
+    return e;
+}
 constexpr uint64_t kPrepareMaskBases = 1ull << 28;   // movi_index_prepare's reservation of movi_pml_device's mask words (1 M x 150 bp fits)
 constexpr uint64_t kPrepareMaskReads = 1ull << 22;
 // movi_pml_device's mask words for `bytes`: grow-only; a buffer that a captured call used is retired, not freed
@@ -817,6 +841,8 @@ int movi_index_destroy(movi_index_t *ix) {
     if (ix->d_stats) (void)hipFree(ix->d_stats);
     if (ix->d_loc) (void)hipFree(ix->d_loc);
     if (ix->d_samples) (void)hipFree(ix->d_samples);
+    if (ix->d_color_flat) (void)hipFree(ix->d_color_flat);
+    if (ix->d_color_inds) (void)hipFree(ix->d_color_inds);
     release_scratch(ix);
     delete ix;
     return MOVI_OK;
@@ -1017,6 +1043,16 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
     if (!strcmp(key, "count_variant")) {                     // A/B: -1 = the launch policy, 0 = count_kernel_v0, 1 = the lane state machine
         if (value < -1 || value > 1) return fail(MOVI_ERR_ARG, "count_variant must be -1 (auto), 0 or 1");
         ix->cfg.count_variant = (int)value;
+        return MOVI_OK;
+    }
+    if (!strcmp(key, "color_chunk_keys")) {                  // the colour builder: BWT positions per chunk (0 = by the device's free memory; small: a test hook)
+        if (value < 0) return fail(MOVI_ERR_ARG, "color_chunk_keys must be >= 0");
+        ix->color_chunk_keys = (uint64_t)value;
+        return MOVI_OK;
+    }
+    if (!strcmp(key, "color_scratch_bytes")) {               // movi_multi_classify_device's counter scratch: reads go through it in chunks
+        if (value < 4) return fail(MOVI_ERR_ARG, "color_scratch_bytes must be at least 4");
+        ix->color_scratch_bytes = (uint64_t)value;
         return MOVI_OK;
     }
     if (!strcmp(key, "idx64")) {                             // test hook: run the 64-bit-index kernel instantiations
@@ -1402,6 +1438,7 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     const double deep = ix->d_rows3 ? (double)deep_rows_bytes(ix->desc.r) : 0.0;
     const double ckpt = ix->d_ckpt ? (double)((ix->desc.r >> kPrefixShift) + 2) * 8.0 : 0.0;
     const double locate = ix->sa_rate ? (double)locate_rows_bytes(ix->desc.r) + (double)(ix->desc.length / ix->sa_rate + 1) * 8.0 : 0.0;
+    const double color = ix->d_color_inds ? (double)ix->color_flat.size() * 2.0 + (double)ix->color_inds.size() * 8.0 : 0.0;
     if (!strcmp(key, "rows_bytes")) *value = rows;
     else if (!strcmp(key, "locate_bytes")) *value = locate;
     else if (!strcmp(key, "kmer_bytes")) *value = kmer;
@@ -1409,10 +1446,16 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     else if (!strcmp(key, "ahead_rows_bytes")) *value = ahead;
     else if (!strcmp(key, "deep_rows_bytes")) *value = deep;
     else if (!strcmp(key, "ckpt_bytes")) *value = ckpt;
-    else if (!strcmp(key, "derived_bytes")) *value = kmer + ftab + ahead + deep + ckpt + locate;
+    else if (!strcmp(key, "color_bytes")) *value = color;
+    else if (!strcmp(key, "color_taxa")) *value = (double)ix->color_taxa.size();      // to_taxon_id entries held (0 after a load)
+    else if (!strcmp(key, "color_chunks")) *value = (double)ix->color_chunks;
+    else if (!strcmp(key, "color_walk_seconds")) *value = ix->color_seconds[0];
+    else if (!strcmp(key, "color_sort_seconds")) *value = ix->color_seconds[1];
+    else if (!strcmp(key, "color_number_seconds")) *value = ix->color_seconds[2];
+    else if (!strcmp(key, "derived_bytes")) *value = kmer + ftab + ahead + deep + ckpt + locate + color;
     else if (!strcmp(key, "ahead_no_ff")) *value = ix->ahead_tallied ? ix->ahead_no_ff : -1.0;
     else if (!strcmp(key, "device_scratch_bytes")) {         // device scratch the *_device calls hold: mask words (retired ones too), vector, segment workspace
-        double b = (double)ix->dmask_cap + (double)ix->scratch_cap[movi_index::kTmp] + (double)ix->seg_ws.cap;
+        double b = (double)ix->dmask_cap + (double)ix->scratch_cap[movi_index::kTmp] + (double)ix->seg_ws.cap + (double)ix->color_scratch_cap;
         for (const auto &r : ix->dmask_retired) b += (double)r.second;
         *value = b;
     }
@@ -1541,6 +1584,9 @@ static void release_scratch(movi_index *ix) {
     ix->pipe_ev.clear();
     if (ix->seg_ws.buf) (void)hipFree(ix->seg_ws.buf);
     ix->seg_ws = SegWorkspace();
+    if (ix->d_color_scratch) (void)hipFree(ix->d_color_scratch);
+    ix->d_color_scratch = nullptr;
+    ix->color_scratch_cap = 0;
     if (ix->dmask) (void)hipFree(ix->dmask);               // (graphs captured over movi_pml_device on this handle are invalid from here on)
     ix->dmask = nullptr;
     ix->dmask_cap = 0;
@@ -2479,8 +2525,10 @@ int movi_count_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *
 
 int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *derived_bytes) {
     if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
-    if (what & ~(uint32_t)(MOVI_PREPARE_PML | MOVI_PREPARE_COUNT | MOVI_PREPARE_ZML | MOVI_PREPARE_SA)) return fail(MOVI_ERR_ARG, "unknown MOVI_PREPARE_* bit");
+    if (what & ~(uint32_t)(MOVI_PREPARE_PML | MOVI_PREPARE_COUNT | MOVI_PREPARE_ZML | MOVI_PREPARE_SA | MOVI_PREPARE_COLOR))
+        return fail(MOVI_ERR_ARG, "unknown MOVI_PREPARE_* bit");
     if ((what & MOVI_PREPARE_SA) && !ix->sa_rate) return fail(MOVI_ERR_ARG, kNoSsa);
+    if ((what & MOVI_PREPARE_COLOR) && !ix->d_color_inds) return fail(MOVI_ERR_ARG, kNoColor);
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     ix->ahead_retry_in = 0;                                           // an explicit call asks the device now
@@ -2501,6 +2549,12 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
     if (what & MOVI_PREPARE_SA) {
         // the sampled suffix array and the locate rows were built when it was attached: only the kernels' code object is loaded here
         (void)preload_sa(ix->kmode, ix->dev.idx32 != 0);
+        (void)hipGetLastError();
+    }
+    if (what & MOVI_PREPARE_COLOR) {
+        // the counter scratch of movi_multi_classify_device and its kernel's code object: the call then allocates nothing
+        if (hipError_t e = grow_color_scratch(ix); e != hipSuccess) return fail_hip(e, "reserving the counter scratch of --multi-classify");
+        (void)preload_color(ix->kmode, ix->dev.idx32 != 0);
         (void)hipGetLastError();
     }
     ix->prepared = true;
@@ -2891,6 +2945,287 @@ int movi_sa_entries_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_
     auto harvest = [](const uint8_t *, uint64_t, uint64_t, HostPool::Group *) {};
     // (chunk by chunk, synchronously: 8 bytes per base come down, the locate walk is ~100 gathers per base -- nothing to overlap)
     return run_host(false, ix, h_bases, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest, 0);
+}
+
+}  // extern "C"
+
+// -------------------------------------------------------------------------- Movi Color (default colour mode)
+
+namespace {
+
+void detach_color(movi_index *ix) {
+    if (ix->d_color_flat) (void)hipFree(ix->d_color_flat);
+    if (ix->d_color_inds) (void)hipFree(ix->d_color_inds);
+    ix->d_color_flat = nullptr;
+    ix->d_color_inds = nullptr;
+    ix->color_flat.clear();
+    ix->color_inds.clear();
+    ix->color_taxa.clear();
+    ix->color_species = 0;
+}
+
+// ix->color_flat / color_inds / color_species are set: check them and put them on the device
+int attach_color(movi_index *ix, const char *what) {
+    const uint64_t fs = ix->color_flat.size();
+    for (uint64_t i = 0; i < ix->color_inds.size(); i++) {               // every run's set lies inside the table and names known documents
+        const uint64_t at = ix->color_inds[i];
+        bool ok = at < fs && at + 1 + ix->color_flat[at] <= fs;
+        for (uint64_t k = 0; ok && k < ix->color_flat[at]; k++) ok = ix->color_flat[at + 1 + k] < ix->color_species;
+        if (!ok) {
+            detach_color(ix);
+            return fail(MOVI_ERR_FORMAT, std::string(what) + ": the document set of run " + std::to_string(i) + " does not lie inside the flat colour table "
+                                         "or names a document beyond num_species");
+        }
+    }
+    hipError_t e = hipMalloc(&ix->d_color_flat, std::max<size_t>(fs * 2, 8));
+    if (e == hipSuccess) e = hipMalloc(&ix->d_color_inds, ix->color_inds.size() * 8);
+    if (e == hipSuccess) e = hipMemcpy(ix->d_color_flat, ix->color_flat.data(), fs * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(ix->d_color_inds, ix->color_inds.data(), ix->color_inds.size() * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { detach_color(ix); return fail_hip(e, "uploading the colour tables"); }
+    return MOVI_OK;
+}
+
+ColorTables color_tables(const movi_index *ix) {
+    ColorTables ct;
+    ct.flat = ix->d_color_flat;
+    ct.inds = ix->d_color_inds;
+    ct.flat_size = ix->color_flat.size();
+    ct.num_species = ix->color_species;
+    return ct;
+}
+
+int multi_classify_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t min_len,
+                          movi_mc_read_t *d_out, uint32_t *d_counts, uint16_t *d_pml, uint8_t *d_err, const uint32_t *d_order, hipStream_t s,
+                          DevStats *d_stats, uint32_t *d_scratch = nullptr, size_t scratch_cap = 0) {
+    // d_scratch / scratch_cap: counters of the caller's own for a call without counter rows (a chunk of a *_host call, which may run
+    // beside other chunks of the same handle); nullptr: the handle's scratch -- one movi_multi_classify_device call at a time
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (!mode_has_thresholds(ix->desc.mode))
+        return fail(MOVI_ERR_ARG, "--multi-classify is a PML query, which needs thresholds: use a *-thresholds index");
+    if (!ix->d_color_inds) return fail(MOVI_ERR_ARG, kNoColor);
+    if (min_len > 255u) return fail(MOVI_ERR_ARG, "min_len is a uint8_t in the reference: at most 255");
+    if (n_reads == 0) return MOVI_OK;
+    if (!d_offsets || !d_out || (n_bases && !d_bases)) return fail(MOVI_ERR_ARG, "NULL device buffer");
+    if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
+    HIP_TRY(hipSetDevice(ix->device));
+    if (!d_stats) d_stats = ix->d_stats;
+    const uint64_t S = ix->color_species;
+    if (d_scratch && scratch_cap < S * 4) return fail(MOVI_ERR_ARG, "counter scratch smaller than one read's counters");
+    if (!d_counts && !d_scratch && ix->color_scratch_cap < S * 4) {      // not prepared: the scratch is reserved here, outside a capture only
+        if (stream_capturing(s)) return fail(MOVI_ERR_ARG, "movi_multi_classify_device under a stream capture needs movi_index_prepare(MOVI_PREPARE_COLOR) first");
+        HIP_TRY(grow_color_scratch(ix));
+    }
+    // reads go through the counters chunk by chunk: at most "color_scratch_bytes" of them are live at a time
+    if (!d_scratch) { d_scratch = ix->d_color_scratch; scratch_cap = ix->color_scratch_cap; }
+    const uint64_t budget = d_counts ? std::max<uint64_t>(ix->color_scratch_bytes, S * 4)
+                                     : std::min<uint64_t>(scratch_cap, std::max<uint64_t>(ix->color_scratch_bytes, S * 4));
+    const uint64_t chunk = std::max<uint64_t>(1, budget / (S * 4));
+    HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(DevStats), s));
+    if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, n_reads * S * 4, s));
+    for (uint64_t t0 = 0; t0 < n_reads; t0 += chunk) {
+        const uint64_t t1 = std::min(n_reads, t0 + chunk);
+        if (!d_counts) HIP_TRY(hipMemsetAsync(d_scratch, 0, (t1 - t0) * S * 4, s));
+        HIP_TRY(launch_color(ix->dev, color_tables(ix), min_len, d_bases, d_offsets, t0, t1, d_pml, reinterpret_cast<McRead *>(d_out),
+                             d_counts ? d_counts : d_scratch, d_counts != nullptr, d_err, d_stats, d_order, s, &ix->last_launch));
+    }
+    return MOVI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int movi_color_build(movi_index_t *ix, const uint64_t *doc_offsets, const uint32_t *doc_ids, uint64_t n_docs, void *stream) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (!doc_offsets || n_docs == 0) return fail(MOVI_ERR_ARG, "no document offsets");
+    if (n_docs > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 documents");
+    for (uint64_t i = 0; i < n_docs; i++)
+        if (doc_offsets[i] <= (i ? doc_offsets[i - 1] : 0))
+            return fail(MOVI_ERR_ARG, "the document offsets must be strictly increasing and start above 0 (an empty document at entry " + std::to_string(i) + ")");
+    // load_document_info, src/move_structure_io.cpp:659-687: no ids = i + 1; the ids in use, ascending, become 0 .. num_species - 1
+    std::vector<uint32_t> raw(n_docs);
+    for (uint64_t i = 0; i < n_docs; i++) raw[i] = doc_ids ? doc_ids[i] : (uint32_t)(i + 1);
+    std::vector<uint32_t> taxa(raw);
+    std::sort(taxa.begin(), taxa.end());
+    taxa.erase(std::unique(taxa.begin(), taxa.end()), taxa.end());
+    if (taxa.size() > 0xFFFFu) return fail(MOVI_ERR_ARG, "more than 65535 distinct document ids: the colour tables hold documents as uint16_t");
+    std::vector<uint16_t> ids(n_docs);
+    for (uint64_t i = 0; i < n_docs; i++) ids[i] = (uint16_t)(std::lower_bound(taxa.begin(), taxa.end(), raw[i]) - taxa.begin());
+    HIP_TRY(hipSetDevice(ix->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (ix->desc.r + 1 > 0x7FFFFFFFull)
+        return fail(MOVI_ERR_ARG, "the colour builder cannot run on a table of 2^31 - 1 rows or more yet (it walks from a sampled suffix array, whose "
+                                  "locate rows need one 32-bit-indexed device scan)");
+    if (!ix->sa_rate)                                                    // the text position of every BWT position comes from the samples
+        if (int rc = movi_ssa_build(ix, 100, stream)) return rc;
+    detach_color(ix);
+    uint64_t *d_keys = nullptr, n_keys = 0, key_cap = 0;
+    uint32_t bad = 0;
+    const hipError_t e = build_color_keys(ix->kmode, ix->dev, loc_args(ix), doc_offsets, ids.data(), (uint32_t)n_docs, ix->color_chunk_keys,
+                                          ix->cfg.num_cus, s, &d_keys, &n_keys, &bad, &ix->color_chunks, ix->color_seconds, &ix->last_launch, &key_cap);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        return fail(MOVI_ERR_HIP, "building the document sets: out of device memory -- the sorted unique (run, document) keys so far (" + std::to_string(n_keys) +
+                                      ") and the next stretch of the text do not fit the key budget of " + std::to_string(key_cap) +
+                                      " keys (two 8-byte buffers and the sort's scratch within half of the free device memory, at most 2^30 keys)");
+    }
+    if (e != hipSuccess) return fail_hip(e, "building the document sets");
+    if (bad)
+        return fail(MOVI_ERR_INVARIANT, "the walks from the sampled suffix array do not visit every BWT position exactly once (" + std::to_string(bad) +
+                                            " finding(s)): corrupt index, or a sampled suffix array of another index?");
+    std::vector<uint64_t> keys(n_keys);
+    const hipError_t e2 = hipMemcpy(keys.data(), d_keys, n_keys * 8, hipMemcpyDeviceToHost);
+    (void)hipFree(d_keys);
+    if (e2 != hipSuccess) return fail_hip(e2, "reading the document sets back");
+    // build_doc_sets, src/move_structure_color.cpp:57-63: a set gets its number at the first run, in run order, that has it -- and
+    // flat_and_serialize_colors_vectors, src/move_structure_io.cpp:515-534: sets laid out in that order, size first
+    const auto tn = std::chrono::steady_clock::now();
+    const uint64_t r = ix->desc.r;
+    std::unordered_map<std::string, uint64_t> seen;
+    std::vector<uint16_t> flat, docs;
+    std::vector<uint64_t> inds(r);
+    uint64_t k = 0;
+    for (uint64_t i = 0; i < r; i++) {
+        docs.clear();
+        while (k < n_keys && (keys[k] >> 16) == i) docs.push_back((uint16_t)(keys[k++] & 0xFFFFu));
+        if (docs.empty()) return fail(MOVI_ERR_INVARIANT, "run " + std::to_string(i) + " has no document");
+        const auto ins = seen.emplace(std::string(reinterpret_cast<const char *>(docs.data()), docs.size() * 2), flat.size());
+        if (ins.second) {
+            flat.push_back((uint16_t)docs.size());
+            flat.insert(flat.end(), docs.begin(), docs.end());
+        }
+        inds[i] = ins.first->second;
+    }
+    if (k != n_keys) return fail(MOVI_ERR_INVARIANT, "document keys beyond the last run");
+    if (flat.size() >= (1ull << 40)) return fail(MOVI_ERR_ARG, "the flat colour table needs more than 40 bits of offset (MoveTally, include/move_row.hpp:13-26)");
+    ix->color_seconds[2] = std::chrono::duration<double>(std::chrono::steady_clock::now() - tn).count();
+    ix->color_flat.swap(flat);
+    ix->color_inds.swap(inds);
+    ix->color_species = (uint32_t)taxa.size();
+    if (int rc = attach_color(ix, "movi_color_build")) return rc;
+    ix->color_taxa.swap(taxa);
+    return MOVI_OK;
+}
+
+int movi_color_get(const movi_index_t *ix, uint64_t *flat_size, uint16_t *h_flat, uint64_t flat_cap, uint64_t *h_inds, uint64_t inds_cap,
+                   uint32_t *num_species, uint32_t *h_to_taxon_id, uint64_t taxa_cap) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (ix->color_inds.empty()) return fail(MOVI_ERR_ARG, kNoColor);
+    if (flat_size) *flat_size = ix->color_flat.size();
+    if (num_species) *num_species = ix->color_species;
+    if ((h_flat && flat_cap < ix->color_flat.size()) || (h_inds && inds_cap < ix->color_inds.size()) || (h_to_taxon_id && taxa_cap < ix->color_taxa.size()))
+        return fail(MOVI_ERR_ARG, "a buffer of movi_color_get is too small");
+    if (h_flat) memcpy(h_flat, ix->color_flat.data(), ix->color_flat.size() * 2);
+    if (h_inds) memcpy(h_inds, ix->color_inds.data(), ix->color_inds.size() * 8);
+    if (h_to_taxon_id) memcpy(h_to_taxon_id, ix->color_taxa.data(), ix->color_taxa.size() * 4);
+    return MOVI_OK;
+}
+
+int movi_color_save(movi_index_t *ix, const char *path) {
+    if (!ix || !path) return fail(MOVI_ERR_ARG, "NULL argument");
+    if (ix->color_inds.empty()) return fail(MOVI_ERR_ARG, kNoColor);
+    // flat_and_serialize_colors_vectors, src/move_structure_io.cpp:542-546: u64 size | u16 flat_colors | r MoveTally (u32 low, u8 high)
+    std::vector<uint8_t> tally(ix->color_inds.size() * 5);
+    for (uint64_t i = 0; i < ix->color_inds.size(); i++) {
+        const uint64_t v = ix->color_inds[i];
+        const uint32_t lo = (uint32_t)v;
+        memcpy(&tally[i * 5], &lo, 4);
+        tally[i * 5 + 4] = (uint8_t)(v >> 32);
+    }
+    const std::string tmp = std::string(path) + ".tmp";                // renamed over `path` once complete
+    FILE *f = fopen(tmp.c_str(), "wb");
+    if (!f) return fail(MOVI_ERR_IO, std::string("cannot write ") + tmp);
+    const uint64_t fs = ix->color_flat.size();
+    bool ok = fwrite(&fs, 8, 1, f) == 1 && fwrite(ix->color_flat.data(), 2, fs, f) == fs && fwrite(tally.data(), 1, tally.size(), f) == tally.size();
+    ok = (fclose(f) == 0) && ok;
+    if (ok) ok = std::rename(tmp.c_str(), path) == 0;
+    else (void)std::remove(tmp.c_str());
+    if (!ok) return fail(MOVI_ERR_IO, std::string("writing ") + path + " failed");
+    return MOVI_OK;
+}
+
+int movi_color_load(movi_index_t *ix, const char *path, uint32_t num_species) {
+    if (!ix || !path) return fail(MOVI_ERR_ARG, "NULL argument");
+    if (num_species == 0 || num_species > 0xFFFFu) return fail(MOVI_ERR_ARG, "num_species must be between 1 and 65535");
+    FILE *f = fopen(path, "rb");
+    if (!f)       // deserialize_doc_sets_flat, src/move_structure_io.cpp:587-592
+        return fail(MOVI_ERR_IO, std::string("[deserialize doc sets flat] Failed to open document sets flat file at ") + path);
+    const uint64_t r = ix->desc.r;
+    uint64_t fs = 0;
+    bool ok = read_exact(f, &fs, 8);
+    ok = ok && fseek(f, 0, SEEK_END) == 0;
+    const long end = ok ? ftell(f) : -1;
+    const bool shape = ok && end >= 8 && fs < (1ull << 40) && (uint64_t)end == 8 + fs * 2 + r * 5;
+    std::vector<uint16_t> flat;
+    std::vector<uint8_t> tally;
+    if (shape) {
+        flat.resize(fs);
+        tally.resize(r * 5);
+        ok = fseek(f, 8, SEEK_SET) == 0 && read_exact(f, flat.data(), fs * 2) && read_exact(f, tally.data(), r * 5);
+    }
+    fclose(f);
+    if (!ok) return fail(MOVI_ERR_FORMAT, std::string(path) + " is truncated");
+    if (!shape) return fail(MOVI_ERR_FORMAT, std::string(path) + ": a flat colour table of " + std::to_string(fs) + " entries and its length do not fit an index of " +
+                                                 std::to_string(r) + " rows");
+    HIP_TRY(hipSetDevice(ix->device));
+    detach_color(ix);
+    ix->color_inds.resize(r);
+    for (uint64_t i = 0; i < r; i++) {
+        uint32_t lo;
+        memcpy(&lo, &tally[i * 5], 4);
+        ix->color_inds[i] = (uint64_t)lo | ((uint64_t)tally[i * 5 + 4] << 32);
+    }
+    ix->color_flat.swap(flat);
+    ix->color_species = num_species;
+    return attach_color(ix, path);
+}
+
+int movi_multi_classify_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                               uint32_t min_len, movi_mc_read_t *d_out, uint32_t *d_counts, uint16_t *d_out_pml, uint8_t *d_read_err,
+                               const uint32_t *d_read_order, void *stream) {
+    return multi_classify_device(ix, d_bases, d_offsets, n_reads, n_bases, min_len, d_out, d_counts, d_out_pml, d_read_err, d_read_order,
+                                 static_cast<hipStream_t>(stream), nullptr);
+}
+
+int movi_multi_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint32_t min_len,
+                             movi_mc_read_t *h_out, uint32_t *h_counts, uint16_t *h_out_pml, uint8_t *h_read_err, movi_query_stats_t *stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (!mode_has_thresholds(ix->desc.mode))
+        return fail(MOVI_ERR_ARG, "--multi-classify is a PML query, which needs thresholds: use a *-thresholds index");
+    if (ix->color_inds.empty()) return fail(MOVI_ERR_ARG, kNoColor);
+    if (n_reads == 0) return MOVI_OK;
+    if (!h_offsets || !h_out || (h_offsets[n_reads] != h_offsets[0] && !h_bases)) return fail(MOVI_ERR_ARG, "NULL host buffer");
+    if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
+    HIP_TRY(hipSetDevice(ix->device));
+    const uint64_t S = ix->color_species;
+    struct { void *p; } d_o{}, d_c{}, d_pml{};
+    auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
+        HIP_TRY(c.alloc(movi_index::kA, nr * sizeof(movi_mc_read_t), &d_o.p));
+        // the chunk's own counters, from its own staging (chunks of the overlapped path walk side by side): the caller's rows whole,
+        // or scratch within "color_scratch_bytes" through which the chunk's reads go in turn
+        const size_t cbytes = h_counts ? nr * S * 4 : (size_t)std::min<uint64_t>(nr * S * 4, std::max<uint64_t>(ix->color_scratch_bytes, S * 4));
+        HIP_TRY(c.alloc(movi_index::kS, cbytes, &d_c.p));
+        if (h_out_pml) HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_pml.p));
+        return multi_classify_device(ix, db, dof, nr, nb, min_len, static_cast<movi_mc_read_t *>(d_o.p), h_counts ? static_cast<uint32_t *>(d_c.p) : nullptr,
+                                     h_out_pml ? static_cast<uint16_t *>(d_pml.p) : nullptr, derr, nullptr, c.s, c.d_stats,
+                                     h_counts ? nullptr : static_cast<uint32_t *>(d_c.p), h_counts ? 0 : cbytes);
+    };
+    // page-locked block of a chunk in flight: out[nr] | counts[nr * S]
+    auto fetch = [&](ChunkCtx &c, uint64_t first, uint64_t nr, uint64_t b0, uint64_t nb) -> int {
+        HIP_TRY(c.down_small(h_out + first, 0, c.d[movi_index::kA], nr * sizeof(movi_mc_read_t)));
+        if (h_counts) HIP_TRY(c.down_small(h_counts + first * S, nr * sizeof(movi_mc_read_t), c.d[movi_index::kS], nr * S * 4));
+        if (h_out_pml) HIP_TRY(c.down(h_out_pml + b0, c.d[movi_index::kOut], nb * 2));
+        return MOVI_OK;
+    };
+    auto harvest = [&](const uint8_t *h, uint64_t first, uint64_t nr, HostPool::Group *) {
+        memcpy(h_out + first, h, nr * sizeof(movi_mc_read_t));
+        if (h_counts) memcpy(h_counts + first * S, h + nr * sizeof(movi_mc_read_t), nr * S * 4);
+    };
+    // chunked through the host loop like the count query; overlapped where the reads sit in page-locked memory and no vector comes down
+    const bool overlapped = !h_out_pml && worth_overlapping_small_results(h_offsets, n_reads) && is_pinned(h_bases);
+    return run_host(overlapped, ix, h_bases, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest,
+                    sizeof(movi_mc_read_t) + (h_counts ? S * 4 : 0));
 }
 
 }  // extern "C"

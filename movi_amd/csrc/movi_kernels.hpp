@@ -393,6 +393,32 @@ hipError_t launch_sa_pos(const DevIndex &ix, const uint8_t *d_bases, const uint6
 hipError_t build_sampled_sa(int mode, const DevIndex &ix, const LocArgs &loc, uint64_t *d_samples, DevStats *d_stats, int num_cus,
                             hipStream_t stream, uint32_t *bad, LaunchInfo *info);
 hipError_t preload_sa(int mode, bool idx32);   // load the translation unit's code object now (movi_index_prepare)
+// d_pos[m] = the packed position of BWT position m * loc.rate, m < n_samples (what build_sampled_sa starts its list from).
+hipError_t launch_sample_positions(int mode, const DevIndex &ix, const LocArgs &loc, uint64_t n_samples, uint64_t *d_pos, hipStream_t stream);
+
+// Movi Color (movi_walk_color.hip; the tables and the key are stated in movi_color.hpp).
+struct ColorTables {
+    const uint16_t *flat = nullptr;     // every distinct set: size, then its sorted members
+    const uint64_t *inds = nullptr;     // r offsets into flat
+    uint64_t flat_size = 0;
+    uint32_t num_species = 0;
+};
+// One read's result of the multi-class scoring (movi_mc_read_t): ReadProcessor::process_char, src/read_processor.cpp:122-186.
+struct McRead { uint16_t best, second; uint32_t colors_count, sum_ml, best_count, second_count, reserved_; };
+// Lane slots [t0, t1) of a batch of n_reads reads.  d_counts: num_species u32 per read, zeroed by the caller; indexed by read
+// (by_read) or by slot - t0 (the handle's scratch).  d_pml optional.
+hipError_t launch_color(const DevIndex &ix, const ColorTables &ct, uint32_t min_len, const uint8_t *d_bases, const uint64_t *d_offsets,
+                        uint64_t t0, uint64_t t1, uint16_t *d_pml, McRead *d_out, uint32_t *d_counts, bool by_read, uint8_t *d_err,
+                        DevStats *d_stats, const uint32_t *d_order, hipStream_t stream, LaunchInfo *info);
+hipError_t preload_color(int mode, bool idx32);
+// The builder: the (row, document) pairs of every BWT position, sorted and unique, in a buffer of the call's own (*d_keys, to be
+// hipFree'd by the caller; *n_keys pairs).  loc: the attached sampled suffix array.  h_doc_ends / h_doc_ids: n_docs strictly
+// increasing end offsets and the documents' numbers.  chunk_keys: at most this many BWT positions per chunk (0 = what the device's
+// free memory allows).  *bad (host) = findings that a consistent table and array cannot produce.  seconds[0] / [1]: walks / sorts.
+hipError_t build_color_keys(int mode, const DevIndex &ix, const LocArgs &loc, const uint64_t *h_doc_ends, const uint16_t *h_doc_ids,
+                            uint32_t n_docs, uint64_t chunk_keys, int num_cus, hipStream_t stream, uint64_t **d_keys, uint64_t *n_keys,
+                            uint32_t *bad, uint32_t *n_chunks, double *seconds, LaunchInfo *info, uint64_t *key_cap = nullptr);
+// (on hipErrorOutOfMemory *n_keys = the unique keys held when the next stretch did not fit and *key_cap = the budget, in keys)
 
 // Compaction of per-read results of variable length (the host path of both): d_first[0..n] = exclusive prefix of the counts d_n
 // (d_first[n] = their total); then read i's d_n[i] elements of elem_bytes (8 or 16) from d_src[d_offsets[i]..] to d_out[d_first[i]..].

@@ -317,6 +317,13 @@ hipError_t locate_rows_all_p(const uint4 *d_loc, uint64_t first, uint64_t cnt, u
     return hipGetLastError();
 }
 
+hipError_t launch_sample_positions(int mode, const DevIndex &ix, const LocArgs &loc, uint64_t n_samples, uint64_t *d_pos, hipStream_t stream) {
+    if ((mode != 6 && mode != 3) || loc.rate == 0u || !loc.rows || ix.r > 0x7FFFFFFFull * 256) return hipErrorInvalidValue;
+    if (mode == 6) hipLaunchKernelGGL(sample_pos_kernel<6>, dim3(blocks_of(ix.r)), dim3(256), 0, stream, loc.rows, ix.r, loc.rate, n_samples, d_pos);
+    else hipLaunchKernelGGL(sample_pos_kernel<3>, dim3(blocks_of(ix.r)), dim3(256), 0, stream, loc.rows, ix.r, loc.rate, n_samples, d_pos);
+    return hipGetLastError();
+}
+
 hipError_t build_sampled_sa(int mode, const DevIndex &ix, const LocArgs &loc, uint64_t *d_samples, DevStats *d_stats, int num_cus,
                             hipStream_t stream, uint32_t *bad_out, LaunchInfo *info) {
     const uint64_t n = loc.n, rate = loc.rate, m = (n + rate - 1) / rate, entries = n / rate + 1;

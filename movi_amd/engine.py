@@ -454,6 +454,61 @@ class MoveIndex:
         sa, _, _ = self.query_sa_entries_packed(bases, offs, want_pml=False)
         return [sa[int(offs[i]): int(offs[i + 1])] for i in range(len(reads))]
 
+    # -- Movi Color: colour tables and multi-class classification -------------------
+    MC_DTYPE = np.dtype([("best", "<u2"), ("second", "<u2"), ("colors_count", "<u4"), ("sum_ml", "<u4"), ("best_count", "<u4"), ("second_count", "<u4"), ("reserved_", "<u4")])   # movi_mc_read_t
+    DOC_NONE = 0xFFFF
+
+    def build_colors(self, doc_offsets, doc_ids=None, stream=0):
+        """movi_color_build: the colour tables from the document end offsets (and taxon ids), built on the device and attached."""
+        offs = np.ascontiguousarray(doc_offsets, np.uint64)
+        ids = np.ascontiguousarray(doc_ids, np.uint32) if doc_ids is not None else None
+        check(lib().movi_color_build(self._h, offs.ctypes.data, ids.ctypes.data if ids is not None else None, offs.size,
+                                     C.c_void_p(stream) if stream else None))
+
+    def save_colors(self, path):
+        """movi_color_save: the attached tables as the reference's doc_sets_flat.bin."""
+        check(lib().movi_color_save(self._h, str(path).encode()))
+
+    def load_colors(self, path, num_species):
+        check(lib().movi_color_load(self._h, str(path).encode(), int(num_species)))
+
+    def colors(self):
+        """(flat_colors u16, flat offsets per run u64, num_species, to_taxon_id u32 -- empty after a load)."""
+        fs, ns = C.c_uint64(0), C.c_uint32(0)
+        check(lib().movi_color_get(self._h, C.byref(fs), None, 0, None, 0, C.byref(ns), None, 0))
+        flat, inds, taxa = np.zeros(fs.value, np.uint16), np.zeros(self.desc.r, np.uint64), np.zeros(ns.value, np.uint32)
+        check(lib().movi_color_get(self._h, None, flat.ctypes.data, flat.size, inds.ctypes.data, inds.size, None, None, 0))
+        check(lib().movi_color_get(self._h, None, None, 0, None, 0, None, taxa.ctypes.data, taxa.size))
+        return flat, inds, int(ns.value), taxa[:int(self.info("color_taxa"))]
+
+    def multi_classify_packed(self, bases, offs, min_len=1, want_counts=True, want_pml=False, want_err=False):
+        """movi_multi_classify_host -> (per-read records (MC_DTYPE), counter rows [n, num_species] or None, u16 PMLs or None,
+        QueryStats[, err, rc])."""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        n = offs.size - 1
+        ns = C.c_uint32(0)
+        check(lib().movi_color_get(self._h, None, None, 0, None, 0, C.byref(ns), None, 0))
+        out = np.zeros(max(n, 1), self.MC_DTYPE)
+        counts = np.zeros((max(n, 1), ns.value), np.uint32) if want_counts else None
+        pml = np.zeros(max(bases.size, 1), np.uint16) if want_pml else None
+        err = np.zeros(max(n, 1), np.uint8)
+        st = QueryStatsC()
+        rc = lib().movi_multi_classify_host(self._h, bases.ctypes.data, offs.ctypes.data, n, int(min_len), out.ctypes.data,
+                                            counts.ctypes.data if want_counts else None, pml.ctypes.data if want_pml else None,
+                                            err.ctypes.data, C.byref(st))
+        res = (out[:n], counts[:n] if want_counts else None, pml[:bases.size] if want_pml else None, QueryStats(st))
+        if want_err:
+            return res + (err[:n], rc)
+        check(rc)
+        return res
+
+    def multi_classify(self, reads, min_len=1):
+        """Per read (best, second, colors_count, sum_ml, counter row)."""
+        bases, offs = _pack_reads(reads)
+        out, counts, _, _ = self.multi_classify_packed(bases, offs, min_len)
+        return [(int(o["best"]), int(o["second"]), int(o["colors_count"]), int(o["sum_ml"]), counts[i]) for i, o in enumerate(out)]
+
     # -- device-pointer queries (bench / torch interop) ---------------------------
     def pml_device(self, d_bases, d_offs, n_reads, n_bases, d_out, d_err=0, stream=0, d_order=0):
         check(lib().movi_pml_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offs), n_reads, n_bases,
@@ -523,7 +578,15 @@ class MoveIndex:
                                            C.c_void_p(d_order) if d_order else None,
                                            C.c_void_p(stream) if stream else None))
 
-    PREPARE_PML, PREPARE_COUNT, PREPARE_ZML, PREPARE_SA = 1, 2, 4, 8
+    def multi_classify_device(self, d_bases, d_offs, n_reads, n_bases, min_len, d_out, d_counts=0, d_pml=0, d_err=0, stream=0, d_order=0):
+        """movi_multi_classify_device: d_out = n_reads 24-byte records; d_counts = 0 keeps the counters in the handle's scratch."""
+        check(lib().movi_multi_classify_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offs), n_reads, n_bases, int(min_len),
+                                               C.c_void_p(d_out), C.c_void_p(d_counts) if d_counts else None,
+                                               C.c_void_p(d_pml) if d_pml else None, C.c_void_p(d_err) if d_err else None,
+                                               C.c_void_p(d_order) if d_order else None,
+                                               C.c_void_p(stream) if stream else None))
+
+    PREPARE_PML, PREPARE_COUNT, PREPARE_ZML, PREPARE_SA, PREPARE_COLOR = 1, 2, 4, 8, 16
 
     def prepare(self, what=1 | 2 | 4, stream=0):
         """movi_index_prepare: build the handle's derived tables now (not inside the first query); returns their bytes."""

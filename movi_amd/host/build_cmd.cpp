@@ -20,9 +20,10 @@ int run_build(const Options &o) {
     if (mode < 0)
         throw UsageError("index type '" + o.index_type + "' is not supported (regular-thresholds, blocked-thresholds, "
                          "sampled-thresholds, regular, blocked, sampled)");
-    const std::string err = movi_build_index_from_fasta(o.ref_file, mode, o.index_dir, o.separators);
+    const std::string err = movi_build_index_from_fasta(o.ref_file, mode, o.index_dir, o.separators, o.color);
     if (!err.empty()) throw std::runtime_error(err);
     std::cerr << "[movi] The " << o.index_type << " index is written to " << o.index_dir << "/index.movi\n";
+    if (o.color) std::cerr << "[movi] The document offsets are written to " << o.index_dir << "/ref.fa.doc_offsets\n";
     return 0;
 }
 

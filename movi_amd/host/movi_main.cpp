@@ -208,6 +208,8 @@ struct Job {
     std::vector<movi_mem_t> mems;                                     // ... and all of them, read by read (file order)
     std::vector<uint32_t> n_runs, kmers_found;                        // --kmer: runs and found k-mers per read ...
     std::vector<movi_kmer_run_t> runs;                                // ... and all the runs, read by read (file order)
+    std::vector<movi_mc_read_t> mc;                                   // --multi-classify: best / second / counts per read ...
+    std::vector<uint32_t> mc_counts;                                  // ... and, with --report-all, its counter row (num_species per read)
     std::vector<uint64_t> sa;                                         // --sa-entries: one suffix-array entry per base, emission order like pml
     std::vector<uint8_t> err;                                         // per-read error byte
     RawBytes original;                                                // reads as given (--filter after --ignore-illegal-chars 1)
@@ -276,6 +278,21 @@ int run_query(const Options &o) {
     if (o.sa_entries && !std::ifstream(o.index_dir + "/ssa.movi").good())      // deserialize_sampled_SA, src/move_structure_io.cpp:727-730
         throw std::runtime_error("[deserialize sampled SA] Failed to open sampled SA entries file at " + o.index_dir + "/ssa.movi" +
                                  "\nBuild the sampled SA by running the build-SA command.");
+    DocInfo docs;
+    if (o.multi_classify) {
+        // the index first, so that a missing one is reported as such; then deserialize_doc_sets_flat (src/move_structure_io.cpp:587-592)
+        // and load_document_info (:643-649), each with the reference's message
+        struct stat sb;
+        if (stat(o.index_dir.c_str(), &sb) != 0 ||
+            (S_ISDIR(sb.st_mode) && !std::ifstream(o.index_dir + "/index.movi").good() && !std::ifstream(o.index_dir + "/movi_index.bin").good()))
+            throw std::runtime_error("The index does not exist at " + o.index_dir + " (no index.movi in it)");
+        if (!std::ifstream(o.index_dir + "/doc_sets_flat.bin").good())
+            throw std::runtime_error("[deserialize doc sets flat] Failed to open document sets flat file at " + o.index_dir + "/doc_sets_flat.bin");
+        docs = load_doc_info(o.index_dir);
+        if (docs.to_taxon_id.empty() || docs.to_taxon_id.size() > 0xFFFF)
+            throw std::runtime_error("ref.fa.doc_offsets / ref.fa.doc_ids name " + std::to_string(docs.to_taxon_id.size()) + " species: between 1 and 65535 are served");
+    }
+    const uint32_t num_species = (uint32_t)docs.to_taxon_id.size();
     int n_dev = 0;
     check(movi_device_count(&n_dev), "no usable GPU");
     if (n_dev < 1) throw EngineError("no usable GPU: the MI355X engine has no CPU fallback");
@@ -363,6 +380,12 @@ int run_query(const Options &o) {
     }
     if (o.sa_entries)                                                  // deserialize_sampled_SA, src/move_structure_io.cpp:724-744 (every GPU holds the samples beside its table)
         for (auto *hd : handles) check(movi_ssa_load(hd, (o.index_dir + "/ssa.movi").c_str()), "loading the sampled suffix array");
+    if (o.multi_classify)                                              // deserialize_doc_sets_flat: every GPU holds the colour tables beside its table
+        for (auto *hd : handles) {
+            if (const char *e = std::getenv("MOVI_COLOR_SCRATCH_BYTES"))           // test hook: reads through the counter scratch in several chunks
+                check(movi_set_option(hd, "color_scratch_bytes", std::atoll(e)), "MOVI_COLOR_SCRATCH_BYTES");
+            check(movi_color_load(hd, (o.index_dir + "/doc_sets_flat.bin").c_str(), num_species), "loading the colour tables");
+        }
     if (o.seg_len >= 0)
         for (auto *hd : handles) check(movi_set_option(hd, "seg_len", o.seg_len), "--seg-len");
     // (the ZML parse does not walk on the look-ahead rows unless "zml_ahead" asks for it: `--zml --ahead-rows 1` builds nothing)
@@ -388,7 +411,7 @@ int run_query(const Options &o) {
     // 14 M-row index hides and a 1 B-row one does not (bench.py big_table.cli_path: 0.31 s of "processing" for 0.03 s of work).
     for (auto *hd : handles) {                                         // (errors here are not the query's: the real calls report)
         if (o.pml && o.logs) continue;                                 // --logs runs on the first kernel, which uses none of the derived tables
-        (void)movi_index_prepare(hd, o.sa_entries ? MOVI_PREPARE_SA : o.pml ? MOVI_PREPARE_PML : (o.zml ? MOVI_PREPARE_ZML : MOVI_PREPARE_COUNT), nullptr, nullptr);   // (--mem: the count tables; --sa-entries: its own walk, no table of the PML walk)
+        (void)movi_index_prepare(hd, o.multi_classify ? MOVI_PREPARE_COLOR : o.sa_entries ? MOVI_PREPARE_SA : o.pml ? MOVI_PREPARE_PML : (o.zml ? MOVI_PREPARE_ZML : MOVI_PREPARE_COUNT), nullptr, nullptr);   // (--mem: the count tables; --sa-entries: its own walk, no table of the PML walk)
         // ... and so is the device staging of a chunk's host call (three hipMallocs: 1.2 ms of the first chunk's 3 ms call otherwise):
         // a chunk's bases with the slack of its last batch, its result vector when one comes back, reads down to 64 bases long
         const int64_t cb = (int64_t)std::min<uint64_t>(chunk_bases + (chunk_bases >> 3), 1ull << 31) / (o.gpus > 0 ? o.gpus : 1);
@@ -432,7 +455,14 @@ int run_query(const Options &o) {
             classifier.write_report_header(*report);
         }
     }
-    const bool open_files = (!o.write_stdout || o.classify) && o.write_output_allowed();
+    // --multi-classify writes one report, to the -o file itself (open_output_files, src/utils.cpp:323-326) or to --stdout; the PML
+    // file the reference opens beside it stays empty there and is not created here
+    std::ofstream mc_file;
+    if (o.multi_classify && !o.write_stdout && o.write_output_allowed()) {
+        mc_file.open(o.out_file);
+        if (!mc_file.good()) throw std::runtime_error("Failed to open the output file: " + o.out_file);
+    }
+    const bool open_files = (!o.write_stdout || o.classify) && o.write_output_allowed() && !o.multi_classify;
     if (open_files) {
         std::string prefix = !o.out_file.empty() ? o.out_file : o.read_file + "." + index_type;
         if (o.kmer) {                                                 // <out_file or reads.<index type>>.kmers.<k> (src/utils.cpp:348-366)
@@ -562,6 +592,16 @@ int run_query(const Options &o) {
         } else {
             order.resize(n);
             for (size_t i = 0; i < n; i++) order[i] = (uint32_t)i;
+        }
+        if (o.multi_classify) {                                       // write_mls, src/read_processor.cpp:489-562: one line per read, the PML records' order
+            std::string txt;
+            txt.reserve(n * 24);
+            for (uint32_t i : order)
+                append_mls_line(txt, rs.id(i), rs.len(i), job.mc[i], o.report_all ? job.mc_counts.data() + (size_t)i * num_species : nullptr,
+                                docs.to_taxon_id, o.report_all, o.min_diff_frac, o.min_score_frac);
+            std::ostream &out = o.write_stdout ? static_cast<std::ostream &>(std::cout) : mc_file;
+            out.write(txt.data(), (std::streamsize)txt.size());
+            return;
         }
         if (sa_file.is_open()) {                                      // output_base_stats(DataType::sa_entry), src/utils.cpp:212-246: the PML records' order
             std::string rec;
@@ -712,6 +752,7 @@ int run_query(const Options &o) {
             if (o.pml && o.logs) continue;                             // --logs runs on the first kernel, which uses none of the derived tables
             if (o.pml && o.classify && !o.write_output_allowed())
                 (void)movi_pml_classify_host(hd, wb, wo, 1, (uint32_t)o.bin_width, classifier.max_value_thr, &wa, &wbl, &wsum, &we, nullptr);
+            else if (o.multi_classify) { movi_mc_read_t wr; (void)movi_multi_classify_host(hd, wb, wo, 1, o.min_len, &wr, nullptr, nullptr, &we, nullptr); }
             else if (o.sa_entries) { uint64_t wsa[32]; (void)movi_sa_entries_host(hd, wb, wo, 1, wp, wsa, &we, nullptr); }
             else if (o.pml) (void)movi_pml_host(hd, wb, wo, 1, wp, &we, nullptr);
             else if (o.zml) (void)movi_zml_host(hd, wb, wo, 1, wp, &we, nullptr);
@@ -755,10 +796,14 @@ int run_query(const Options &o) {
         job.bins_below.assign(verdict_only ? n : 0, 0);
         job.bins_sum.assign(verdict_only ? n : 0, 0);
         // `--no-output` without classification: the walk runs, nothing comes back (movi_pml_host with a NULL vector)
-        const bool walk_only = o.ml() && !o.classify && !o.write_output_allowed();
+        const bool walk_only = o.ml() && !o.classify && (!o.write_output_allowed() || o.multi_classify);   // (--multi-classify: no vector comes back)
         job.pml.ensure(o.ml() && !verdict_only && !walk_only ? rs.bases.size() : 0, pin_this_chunk(rs.bases.size() * 2));
         if (logs) { job.log_ff.resize(rs.bases.size()); job.log_scan.resize(rs.bases.size()); }
         if (o.sa_entries) job.sa.resize(rs.bases.size());
+        if (o.multi_classify) {
+            job.mc.resize(n);
+            job.mc_counts.resize(o.report_all ? n * (size_t)num_species : 0);
+        }
         job.matched.assign(o.count ? n : 0, 0);
         job.counts.assign(o.count ? n : 0, 0);
         job.n_mems.assign(o.mem ? n : 0, 0);
@@ -781,6 +826,9 @@ int run_query(const Options &o) {
             else if (o.pml && logs)
                 rc = movi_pml_logs_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, job.pml.data(), job.log_ff.data(),
                                         job.log_scan.data(), job.err.data() + a, nullptr);
+            else if (o.multi_classify)
+                rc = movi_multi_classify_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, o.min_len, job.mc.data() + a,
+                                              o.report_all ? job.mc_counts.data() + a * (size_t)num_species : nullptr, nullptr, job.err.data() + a, nullptr);
             else if (o.sa_entries)                                    // (--no-output: computed and discarded, as the reference does)
                 rc = movi_sa_entries_host(handles[g], rs.bases.data(), rs.offsets.data() + a, b - a, walk_only ? nullptr : job.pml.data(),
                                           job.sa.data(), job.err.data() + a, nullptr);
@@ -942,6 +990,41 @@ int run_build_sa(const Options &o) {
     return 0;
 }
 
+// `movi color` (src/movi.cpp: build_doc_pats + build_doc_sets + flat_and_serialize_colors_vectors): INDEX/doc_sets_flat.bin from index.movi and
+// INDEX/ref.fa.doc_offsets (+ ref.fa.doc_ids), on the GPU.
+int run_color(const Options &o) {
+    const DocInfo docs = load_doc_info(o.index_dir);
+    if (docs.offsets.empty()) throw std::runtime_error(o.index_dir + "/ref.fa.doc_offsets holds no document");
+    const auto t0 = std::chrono::steady_clock::now();
+    movi_index_t *h = nullptr;
+    check(movi_index_load(o.device, o.index_dir.c_str(), &h), "loading the index");
+    struct Closer { movi_index_t *h; ~Closer() { movi_index_destroy(h); } } closer{h};
+    if (const char *e = std::getenv("MOVI_COLOR_CHUNK_KEYS"))           // test hook: several chunks on a small text
+        check(movi_set_option(h, "color_chunk_keys", std::atoll(e)), "MOVI_COLOR_CHUNK_KEYS");
+    // a sampled suffix array that `movi build-SA` left in the directory is used as it is (any rate); without one the build makes its own
+    const bool have_ssa = std::ifstream(o.index_dir + "/ssa.movi").good();
+    if (have_ssa) check(movi_ssa_load(h, (o.index_dir + "/ssa.movi").c_str()), "loading the sampled suffix array");
+    const auto t1 = std::chrono::steady_clock::now();
+    check(movi_color_build(h, docs.offsets.data(), docs.ids.empty() ? nullptr : docs.ids.data(), docs.offsets.size(), nullptr), "building the document sets");
+    const auto t2 = std::chrono::steady_clock::now();
+    const std::string name = o.index_dir + "/doc_sets_flat.bin";
+    check(movi_color_save(h, name.c_str()), "writing doc_sets_flat.bin");
+    const auto t3 = std::chrono::steady_clock::now();
+    uint64_t flat_size = 0;
+    uint32_t species = 0;
+    check(movi_color_get(h, &flat_size, nullptr, 0, nullptr, 0, &species, nullptr, 0), "the colour tables");
+    double walk = 0, sort = 0, number = 0, chunks = 0;
+    (void)movi_index_info(h, "color_walk_seconds", &walk);
+    (void)movi_index_info(h, "color_sort_seconds", &sort);
+    (void)movi_index_info(h, "color_number_seconds", &number);
+    (void)movi_index_info(h, "color_chunks", &chunks);
+    std::cerr << "[movi] The flat color table (flat_colors.size(): " << flat_size << ", " << docs.offsets.size() << " documents, " << species
+              << " species) is written to " << name << " (index load " << std::chrono::duration<double>(t1 - t0).count() << " s, build "
+              << std::chrono::duration<double>(t2 - t1).count() << " s" << (have_ssa ? " on ssa.movi" : ", its own sampled suffix array included") << ": walk " << walk << " s, sort " << sort << " s in " << (uint64_t)chunks
+              << " chunk(s), numbering " << number << " s; write " << std::chrono::duration<double>(t3 - t2).count() << " s)\n";
+    return 0;
+}
+
 // `movi plan`: the host-side batching + record order, without any GPU work.
 int run_plan(const Options &o) {
     std::ifstream file_in;
@@ -983,7 +1066,11 @@ int main(int argc, char **argv) {
         if (o.command == "view") return view_bpf(o, std::cout);
         if (o.command == "plan") return run_plan(o);
         if (o.command == "null") return run_null(o);
-        if (o.command == "build") return run_build(o);
+        if (o.command == "build") {                                    // --color: the document offsets with the index, then the colour step
+            const int rc = run_build(o);
+            return (rc == 0 && o.color) ? run_color(o) : rc;
+        }
+        if (o.command == "color") return run_color(o);
         if (o.command == "build-SA") return run_build_sa(o);
         return run_query(o);
     } catch (const UsageError &e) {

@@ -29,10 +29,18 @@ const Spec kSpecs[] = {
     {"logs", 0, false},          {"mmap", 0, false},        {"gen-reads", 0, false},
     {"fasta", 'f', true},          {"separators", 0, false},  {"seg-len", 0, true},
     {"ahead-rows", 0, true},        {"sample-rate", 0, true},
+    // Movi Color, default colour mode (src/movi_parser.cpp:119-121, 164-179, 193-199)
+    {"multi-classify", 0, false}, {"min-len", 0, true},     {"report-all", 0, false},
+    {"min-diff-frac", 0, true},  {"min-score-frac", 0, true}, {"color", 0, false},
+    // ... and the flags of its other modes: recognised, refused by name
+    {"full", 0, false},          {"compress", 0, false},    {"freq-compress", 0, false},
+    {"tree-compress", 0, false}, {"color-vectors", 0, false}, {"pvalue-scoring", 0, false},
+    {"early-stop", 0, false},    {"report-colors", 0, false}, {"report-color-ids", 0, false},
+    {"color-move-rows", 0, false},
     // recognised but unsupported query types / features
     {"zml", 0, false},           {"mem", 0, false},         {"rpml", 0, false},
     {"kmer", 0, false},          {"kmer-count", 0, false},  {"sa-entries", 0, false},
-    {"multi-classify", 0, false}, {"ftab-k", 0, true},      {"multi-ftab", 0, false},
+    {"ftab-k", 0, true},         {"multi-ftab", 0, false},
     {"k-length", 'k', true},     {"min-mem-length", 'l', true},
 };
 
@@ -45,6 +53,22 @@ const Spec *find_short(char c) {
     for (const Spec &s : kSpecs)
         if (s.short_name && s.short_name == c) return &s;
     return nullptr;
+}
+
+float to_float(const std::string &name, const std::string &v) {
+    char *end = nullptr;
+    const float x = std::strtof(v.c_str(), &end);
+    if (v.empty() || (end && *end)) throw UsageError("Argument '" + v + "' failed to parse for option '" + name + "'");
+    return x;
+}
+
+// The colour modes this engine does not serve: each refusal names its flag
+void refuse_color_modes(const std::map<std::string, std::vector<std::string>> &seen) {
+    for (const char *bad : {"full", "compress", "freq-compress", "tree-compress", "color-vectors", "pvalue-scoring", "early-stop",
+                            "report-colors", "report-color-ids", "color-move-rows"})
+        if (seen.count(bad))
+            throw UsageError(std::string("--") + bad + " is not supported by the MI355X engine: Movi Color is served in its default colour mode only "
+                             "(flat colour table, one document set per run)");
 }
 
 long to_int(const std::string &name, const std::string &v) {
@@ -65,11 +89,14 @@ std::string usage() {
            "       movi query -i DIR -r FILE|- --kmer [-k K] [--ftab-k K'] [-o PREFIX] [--stdout] [--no-output]\n"
            "                      [--reverse] [--ignore-illegal-chars 1] [--gpus N] [--device D]   (--kmer-count, --rpml: not supported)\n"
            "       movi query -i DIR -r FILE|- --sa-entries [-o PREFIX] [--no-output] ...   (PML + <prefix>.sa_entries.bpf; after build-SA)\n"
+           "       movi query -i DIR -r FILE|- --multi-classify -o REPORT|--stdout [--min-len N] [--report-all [--min-diff-frac F | --min-score-frac F]]\n"
+           "                      [--no-output] [--reverse] [--gpus N] [--device D]   (after movi color; default colour mode only)\n"
            "       movi build-SA -i DIR [--sample-rate N] [--device D]\n"
+           "       movi color -i DIR [--device D]   (DIR/ref.fa.doc_offsets [+ ref.fa.doc_ids] -> DIR/doc_sets_flat.bin)\n"
            "       movi view --bpf FILE\n"
            "       movi null -i DIR [--gen-reads -f REF.fasta] [--pml|--zml]\n"
            "       movi build -i DIR -f REF.fasta [--type regular-thresholds|blocked-thresholds|sampled-thresholds|regular|blocked|sampled]\n"
-           "                  [--separators]\n";
+           "                  [--separators] [--color]\n";
 }
 
 Options parse_args(int argc, char **argv) {
@@ -124,10 +151,11 @@ Options parse_args(int argc, char **argv) {
         o.index_dir = val("index");
         o.read_file = val("read");
         if (has("out-file")) o.out_file = val("out-file");
-        for (const char *bad : {"rpml", "kmer-count", "multi-classify", "multi-ftab"})
+        for (const char *bad : {"rpml", "kmer-count", "multi-ftab"})
             if (has(bad))
                 throw UsageError(std::string("--") + bad + " is not supported by the MI355X engine (PML, ZML, count, MEM and "
-                                 "k-mer presence queries, and --sa-entries with PML, only)");
+                                 "k-mer presence queries, --sa-entries and --multi-classify with PML, only)");
+        refuse_color_modes(seen);
         // --mmap (src/movi_parser.cpp: "Use memory mapping to read the index") is accepted and implied: movi_index_load
         // always maps the file and uploads the rows straight from the page cache
                 if (has("bin-width")) o.bin_width = (size_t)to_int("bin-width", val("bin-width"));
@@ -189,6 +217,24 @@ Options parse_args(int argc, char **argv) {
             if (!o.pml) throw UsageError("--sa-entries reports the positions of the PML walk: it cannot be combined with --zml, --count, --mem or --kmer");
             if (o.classify || o.logs) throw UsageError("--sa-entries cannot be combined with --classify, --filter or --logs");
         }
+        o.multi_classify = has("multi-classify");
+        if (has("min-len")) {                                     // cxxopts::value<uint8_t>, src/movi_parser.cpp:172
+            const long v = to_int("min-len", val("min-len"));
+            if (v < 0 || v > 255) throw UsageError("Argument '" + val("min-len") + "' failed to parse for option 'min-len'");
+            o.min_len = (uint32_t)v;
+        }
+        o.report_all = has("report-all");
+        if (has("min-diff-frac")) o.min_diff_frac = to_float("min-diff-frac", val("min-diff-frac"));
+        if (has("min-score-frac")) o.min_score_frac = to_float("min-score-frac", val("min-score-frac"));
+        if (o.multi_classify) {
+            if (!o.pml || o.sa_entries)
+                throw UsageError("--multi-classify scores the PML walk: it cannot be combined with --zml, --count, --mem, --kmer or --sa-entries");
+            if (o.classify || o.logs) throw UsageError("--multi-classify cannot be combined with --classify, --filter or --logs");
+            if (o.out_file.empty() && !o.write_stdout && !o.no_output)
+                throw UsageError("--multi-classify writes its report to the file given with -o / --out-file (or to --stdout)");
+        } else if (o.report_all || has("min-len") || has("min-diff-frac") || has("min-score-frac")) {
+            throw UsageError("--min-len, --report-all, --min-diff-frac and --min-score-frac belong to --multi-classify");
+        }
         if (o.kmer) {
             if (o.classify || o.logs) throw UsageError("--kmer cannot be combined with --classify, --filter or --logs");
             if (o.k == 0) throw UsageError("-k / --k-length must be at least 1");
@@ -229,6 +275,15 @@ Options parse_args(int argc, char **argv) {
         o.ref_file = val("fasta");
         if (has("type")) o.index_type = val("type");
         o.separators = has("separators");
+        o.color = has("color");                                   // src/movi_parser.cpp:119-121
+        refuse_color_modes(seen);
+        if (has("device")) o.device = (int)to_int("device", val("device"));
+    } else if (o.command == "color") {
+        // src/movi_parser.cpp:193-199, handled at :319-330
+        if (seen["index"].size() != 1) throw UsageError("Please specify the index directory file.");
+        o.index_dir = val("index");
+        refuse_color_modes(seen);
+        if (has("device")) o.device = (int)to_int("device", val("device"));
     } else if (o.command == "build-SA") {
         // src/movi_parser.cpp:308-317
         if (seen["index"].size() != 1) throw UsageError("Please specify the index directory file.");
@@ -248,8 +303,8 @@ Options parse_args(int argc, char **argv) {
         o.small_bpf = has("small-bpf");
         o.large_bpf = has("large-bpf");
     } else {
-        throw UsageError("The '" + o.command + "' action is not part of the MI355X engine (query, view, null, build and build-SA only); use "
-                         "the reference movi for inspect / color / ftab.");
+        throw UsageError("The '" + o.command + "' action is not part of the MI355X engine (query, view, null, build, build-SA and color only); use "
+                         "the reference movi for inspect / ftab.");
     }
     return o;
 }

@@ -10,7 +10,7 @@
 namespace movi_host {
 
 struct Options {
-    std::string command;          // "query" | "view" | "null" | "plan" | "build" | "build-SA"
+    std::string command;          // "query" | "view" | "null" | "plan" | "build" | "build-SA" | "color"
     std::string index_dir;        // -i / --index
     std::string read_file;        // -r / --read ("-" = stdin)
     std::string out_file;         // -o / --out-file
@@ -25,6 +25,12 @@ struct Options {
     bool mem = false;             // --mem: maximal exact matches (src/mem_finder.cpp), one line per MEM
     bool kmer = false;            // --kmer: k-mer presence (src/sequitur.cpp:322-421), one line per read
     bool sa_entries = false;      // --sa-entries: one suffix-array entry per base beside the PML file (needs INDEX/ssa.movi: build-SA)
+    bool multi_classify = false;  // --multi-classify: PML walk + document scoring, one report line per read (needs INDEX/doc_sets_flat.bin: movi color)
+    uint32_t min_len = 1;         // --min-len (uint8_t, movi_options.hpp: min_match_len)
+    bool report_all = false;      // --report-all
+    float min_diff_frac = 0.05f;  // --min-diff-frac
+    float min_score_frac = 0.0f;  // --min-score-frac (non-zero turns the min-diff-frac mode off)
+    bool color = false;           // build --color: ref.fa.doc_offsets + the colour step
     uint64_t sample_rate = 100;   // build-SA --sample-rate (movi_options.hpp: SA_sample_rate)
     uint32_t k = 31;              // -k / --k-length (movi_options.hpp:254)
     uint32_t min_mem_length = 25; // -l / --min-mem-length (movi_options.hpp:255)
@@ -64,6 +70,6 @@ struct UsageError : std::runtime_error {
 // Throws UsageError with the reference's message texts where they exist.
 Options parse_args(int argc, char **argv);
 std::string usage();
-int run_build(const Options &o);  // build_cmd.cpp
+int run_build(const Options &o);  // build_cmd.cpp (writes DIR/ref.fa.doc_offsets too when o.color)
 
 }  // namespace movi_host

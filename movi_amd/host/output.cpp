@@ -345,6 +345,70 @@ void append_mem_line(std::string &txt, std::string_view id, const movi_mem_t &m)
     txt.push_back('\n');
 }
 
+constexpr double kUnclassifiedThreshold = 0.4;                         // #define UNCLASSIFIED_THRESHOLD 0.4, include/utils.hpp:169
+
+DocInfo load_doc_info(const std::string &index_dir) {
+    DocInfo d;
+    const std::string name = index_dir + "/ref.fa.doc_offsets";
+    std::ifstream in(name);
+    if (!in.good()) throw std::runtime_error("[load document info] doc_offsets file not found at \"" + name + "\"");
+    uint64_t v;
+    while (in >> v) d.offsets.push_back(v);
+    std::ifstream ids(index_dir + "/ref.fa.doc_ids");
+    std::vector<uint32_t> raw;
+    if (ids.good()) {
+        uint32_t x;
+        while (ids >> x) d.ids.push_back(x);
+        raw = d.ids;
+    } else {
+        for (size_t i = 0; i < d.offsets.size(); i++) raw.push_back((uint32_t)(i + 1));
+    }
+    if (!d.ids.empty() && d.ids.size() != d.offsets.size())           // (the reference indexes doc_ids by document: out of range there)
+        throw std::runtime_error(index_dir + "/ref.fa.doc_ids holds " + std::to_string(d.ids.size()) + " ids for the " +
+                                 std::to_string(d.offsets.size()) + " documents of ref.fa.doc_offsets");
+    std::sort(raw.begin(), raw.end());                                 // taxon_id_compress is a std::map: ascending taxa
+    raw.erase(std::unique(raw.begin(), raw.end()), raw.end());
+    d.to_taxon_id = raw;
+    return d;
+}
+
+void append_mls_line(std::string &txt, std::string_view id, uint64_t read_length, const movi_mc_read_t &res, const uint32_t *counts,
+                     const std::vector<uint32_t> &to_taxon_id, bool report_all, float min_diff_frac, float min_score_frac) {
+    constexpr uint16_t kNone = 0xFFFF;
+    txt.append(id);
+    txt.push_back(',');
+    const float pml_mean = static_cast<float>(res.sum_ml) / read_length;
+    if (pml_mean < kUnclassifiedThreshold || res.best == kNone) {      // not present: the float against the double constant, as there
+        txt += report_all ? "0\n" : "0,0\n";
+        return;
+    }
+    auto taxon = [&](uint32_t d) { return std::to_string(d < to_taxon_id.size() ? to_taxon_id[d] : 0u); };
+    if (report_all) {
+        if (min_score_frac == 0) txt += taxon(res.best);               // the min-diff-frac mode names the best document whatever happens
+        uint32_t written = 0;
+        const uint32_t best_cnt = res.best_count;
+        for (uint32_t i = 0; i < to_taxon_id.size(); i++) {
+            if (min_score_frac == 0) {
+                const float diff_best = static_cast<float>(best_cnt - counts[i]);
+                if (i != res.best && diff_best < min_diff_frac * best_cnt) { txt.push_back(','); txt += taxon(i); }
+            } else if (static_cast<float>(counts[i]) >= min_score_frac * res.colors_count) {
+                txt.push_back(',');
+                txt += taxon(i);
+                written += 1;
+            }
+        }
+        if (min_score_frac != 0 && written == 0) txt.push_back('0');
+    } else if (res.second == kNone) {
+        txt += taxon(res.best) + ",0";
+    } else {
+        const uint32_t best_cnt = res.best_count, second_cnt = res.second_count;
+        const float second_best_diff = static_cast<float>(best_cnt - second_cnt);
+        if (second_best_diff < 0.05 * best_cnt) txt += taxon(res.best) + "," + taxon(res.second);
+        else txt += taxon(res.best) + ",0";
+    }
+    txt.push_back('\n');
+}
+
 void append_sa_record(std::string &out, std::string_view id, const uint64_t *entries, uint64_t count) {
     const uint16_t st_length = (uint16_t)id.size();                   // (the reference's uint16_t conversion of the id's length)
     out.append(reinterpret_cast<const char *>(&st_length), sizeof(st_length));

@@ -71,6 +71,20 @@ void append_kmer_line(std::string &txt, std::string_view id, uint64_t query_leng
                       const movi_kmer_run_t *runs, uint64_t n_runs);
 void append_mem_line(std::string &txt, std::string_view id, const movi_mem_t &m);   // one MEM line (output_mems, count as u16)   // the same line, appended
 
+// Movi Color.  DocInfo: MoveStructure::load_document_info (src/move_structure_io.cpp:643-687) -- DIR/ref.fa.doc_offsets (cumulative
+// document ends), the optional DIR/ref.fa.doc_ids (a taxon per document; absent: i + 1), the taxa in use numbered in ascending order.
+struct DocInfo {
+    std::vector<uint64_t> offsets;
+    std::vector<uint32_t> ids;               // as given (empty: no doc_ids file)
+    std::vector<uint32_t> to_taxon_id;       // compressed number -> taxon
+};
+// throws with the reference's message when doc_offsets is missing, and when doc_ids holds another number of entries than doc_offsets
+DocInfo load_doc_info(const std::string &index_dir);
+// One report line of `--multi-classify` (ReadProcessor::write_mls, src/read_processor.cpp:489-562; UNCLASSIFIED_THRESHOLD,
+// include/utils.hpp:169), float arithmetic as there.  counts: the read's num_species counters (--report-all; may be NULL otherwise).
+void append_mls_line(std::string &txt, std::string_view id, uint64_t read_length, const movi_mc_read_t &res, const uint32_t *counts,
+                     const std::vector<uint32_t> &to_taxon_id, bool report_all, float min_diff_frac, float min_score_frac);
+
 class Classifier {
 public:
     // Reads DIR/movi.pml.nulldb; returns max_value_thr = max(percentile, 3) + 1.

@@ -459,8 +459,10 @@ static std::vector<uint8_t> build_index(std::vector<uint8_t> &text, int mode) {
 }
 
 // FASTA -> the indexed text (prepare_ref: every record forward + reverse complement, cleaned; with `separators` a '%'
-// after every sequence).  Returns false when the file cannot be read.
-static bool text_from_fasta(const std::string &path, bool separators, std::vector<uint8_t> &text) {
+// after every sequence).  Returns false when the file cannot be read.  doc_ends (optional): where every record's document ends in the
+// text -- prepare_ref's doc_offsets for one FASTA (src/prepare_ref.cpp:37, :66, :73-76, :121-127): a document is a record with its reverse
+// complement and its separators.
+static bool text_from_fasta(const std::string &path, bool separators, std::vector<uint8_t> &text, std::vector<uint64_t> *doc_ends = nullptr) {
     std::ifstream in(path);
     if (!in.good()) return false;
     std::string line, seq;
@@ -468,20 +470,22 @@ static bool text_from_fasta(const std::string &path, bool separators, std::vecto
     while (std::getline(in, line)) {
         while (!line.empty() && (line.back() == '\r' || line.back() == '\n' || line.back() == ' ')) line.pop_back();
         if (!line.empty() && line[0] == '>') {
-            if (have) append_clean(text, seq, separators);
+            if (have) { append_clean(text, seq, separators); if (doc_ends) doc_ends->push_back(text.size()); }
             seq.clear();
             have = true;
         } else if (have) seq += line;
     }
-    if (have) append_clean(text, seq, separators);
+    if (have) { append_clean(text, seq, separators); if (doc_ends) doc_ends->push_back(text.size()); }
     return true;
 }
 
 // `movi build` of the host CLI (movi_amd/host/build_cmd.cpp includes this file with MOVI_BUILD_INDEX_NO_MAIN):
-// FASTA file -> OUT_DIR/index.movi of the given type.  Returns a message on failure, "" on success.
-std::string movi_build_index_from_fasta(const std::string &fasta, int mode, const std::string &out_dir, bool separators) {
+// FASTA file -> OUT_DIR/index.movi of the given type.  Returns a message on failure, "" on success.  doc_offsets: OUT_DIR/ref.fa.doc_offsets
+// is written too (`movi build --color`), one cumulative end per line as prepare_ref writes them.
+std::string movi_build_index_from_fasta(const std::string &fasta, int mode, const std::string &out_dir, bool separators, bool doc_offsets = false) {
     std::vector<uint8_t> text;
-    if (!text_from_fasta(fasta, separators, text)) return "cannot open " + fasta;
+    std::vector<uint64_t> doc_ends;
+    if (!text_from_fasta(fasta, separators, text, &doc_ends)) return "cannot open " + fasta;
     if (text.empty()) return "no sequence in " + fasta;
     if ((uint64_t)text.size() + 1 >= (1ull << 31)) return "text too long for the in-memory constructor (2^31 characters, reverse complements included)";
     mkdir(out_dir.c_str(), 0777);
@@ -490,6 +494,12 @@ std::string movi_build_index_from_fasta(const std::string &fasta, int mode, cons
     f.write(reinterpret_cast<const char *>(img.data()), (std::streamsize)img.size());
     f.close();
     if (!f.good()) return "cannot write " + out_dir + "/index.movi";
+    if (doc_offsets) {
+        std::ofstream d(out_dir + "/ref.fa.doc_offsets");
+        for (uint64_t e : doc_ends) d << e << "\n";
+        d.close();
+        if (!d.good()) return "cannot write " + out_dir + "/ref.fa.doc_offsets";
+    }
     return "";
 }
 
