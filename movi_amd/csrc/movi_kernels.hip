@@ -719,120 +719,119 @@ __global__ __launch_bounds__(256) void seg_finalize_kernel(const uint32_t *__res
 namespace {
 size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 constexpr int kSegOverrun = 4;   // a boundary lane looks for its meeting point over at most this many seg_len of bases
-// The segment length of one call: cfg.seg_len, or shorter (down to 512) when the batch is so small that even then the
-// segments would not fill the GPU: `waves` wavefronts of segments per CU are aimed at.  The ZML parse is latency-bound
-// and wants many (24: 25 k x 10 kbp 13.4 -> 17.2 Gbases/s, 5 k 1.0 uncut -> 6.9, 1 %-error reads 7.7 uncut -> 15.1); the
-// PML walk pays more per boundary than it gains from lanes beyond ~8 per CU (with 24: 5 k x 10 kbp 7.5 -> 18.2, but
-// 200 x 1 Mbp 27.5 -> 20.5 and 1 %-error reads 25.3 -> 20.4).  A full batch (100 k x 10 kbp) keeps cfg.seg_len.
-uint32_t call_seg_len(const LaunchCfg &cfg, uint64_t n_bases, uint64_t waves) {
-    const uint64_t want = (n_bases / ((uint64_t)cfg.num_cus * 64ull * waves)) & ~31ull;
-    const uint64_t lo = cfg.seg_len < 512 ? (uint64_t)cfg.seg_len : 512ull;
-    return (uint32_t)(want < lo ? lo : (want > (uint64_t)cfg.seg_len ? (uint64_t)cfg.seg_len : want));
-}
+
+TableFacts facts(const DevIndex &ix) {   // what the launch policy (movi_launch_policy.hpp) reads of the index
+    return {ix.r, ix.idx32 != 0u, ix.sep != 0u, ix.rows2 != nullptr, ix.rows3 != nullptr, ix.hints != 0u, ix.rows2_count != 0u};
 }
 
-// The segmented PML path: plan (count, scan, fill), K1, K2, K3.  Everything on `stream`, nothing read back: the grids are
-// sized for the most segments the batch could have (n_reads + n_bases / seg_len) and surplus lanes leave at once.
-// Is there anything to gain?  One lane per read already fills the GPU when there are enough reads of about the same
-// length (100 k x 10 kbp: 40.5 Gbases/s either way); segments pay when lanes are scarce -- fewer than 4 wavefronts of reads
-// per CU: 60 k x 10 kbp 28.6 -> 34.3, 25 k 12.1 -> 31.4, 200 x 1 Mbp 0.11 -> 27 Gbases/s -- or when the batch is ragged
-// (its longest read holds a lane long after the others are done; log-normal lengths around 10 kbp: 12.2 -> 32.3).
-// *declined = true: nothing was launched, the caller goes on with one lane per read.  `ragged_hint`: 1 / 0 when the
-// caller knows the lengths (the *_host entry points), -1 when only the device does: then a big batch costs one
-// reduction kernel and a 4-byte read-back -- this call waits for `stream` there.
-static hipError_t launch_pml_segmented(const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
-                                       uint64_t n_bases, uint16_t *d_out, uint8_t *d_err, DevStats *d_stats,
-                                       const LaunchCfg &cfg, hipStream_t stream, SegWorkspace *ws, bool big_batch_cap,
-                                       int ragged_hint, bool *declined, const ClsArgs &bins, int *verdict, LaunchInfo *info) {
-    // `verdict` (optional, in / out): a caller that cuts one batch into several launches (the overlapped host path) lets
-    // the first one probe and hands its verdict to the others -- 1: cut without probing (no read-back, the launch stays
-    // asynchronous), 0: do not cut; -1 on entry: not decided yet.
-    // cfg.seg_probe == 2: the CALLER decides (cfg.seg_verdict) -- no probe, no length reduction, no read-back: the launch
-    // stays asynchronous (stream capture, callers that pipeline several streams).
+// grow-only: a workspace of fewer than `need` bytes is freed and one of `alloc` bytes takes its place
+hipError_t seg_ws_reserve(SegWorkspace *ws, size_t need, size_t alloc) {
+    if (ws->cap >= need) return hipSuccess;
+    if (ws->buf) (void)hipFree(ws->buf);
+    ws->buf = nullptr; ws->cap = 0;
+    const hipError_t e = hipMalloc(&ws->buf, alloc);
+    if (e == hipSuccess) ws->cap = alloc;
+    return e;
+}
+
+// ---- the front half of both segment plans (launch_pml_segmented, launch_zml_segmented): decide, lay the workspace out, probe, cut.
+// Where the two plans differ:
+struct SegShape {
+    uint64_t waves;                 // wavefronts of segments per CU aimed at (call_seg_len)
+    uint64_t ragged_waves;          // a batch of this many wavefronts of reads per CU and more is cut only if it is ragged
+    size_t fin_bytes, ckpt_bytes;   // the plan's records: SegFin / SegCkpt or ZSegFin / ZSegCkpt
+    int n_extra;                    // regions of the caller's own behind the plan's ...
+    size_t extra_bytes[2];          // ... and their sizes
+    bool read_back;                 // the verdict is read back even when nothing was probed
+};
+struct SegPrelude {
+    uint64_t max_seg = 0;           // the most segments the batch could have: what the grids are sized for
+    uint64_t *first = nullptr, *seg_in = nullptr, *seg_out = nullptr;
+    uint32_t *seg_l = nullptr, *seg_j = nullptr, *seg_rem = nullptr;
+    SegJoin *join = nullptr;
+    uint8_t *on_chain = nullptr, *read_fail = nullptr;
+    void *ckpt = nullptr, *fin = nullptr;
+    SegTot *tot = nullptr;
+    uint32_t *go = nullptr;         // go | probes | probes in step
+    uint8_t *extra[2] = {nullptr, nullptr};
+    template <typename Args>        // SegArgs / ZSegArgs
+    void fill(Args &seg, uint64_t n_reads) const {
+        seg.seg_in = seg_in; seg.seg_out = seg_out; seg.seg_len = seg_l; seg.n_seg = first + n_reads;
+        seg.ckpt = static_cast<decltype(seg.ckpt)>(ckpt);
+        seg.fin = static_cast<decltype(seg.fin)>(fin);
+        seg.tot = tot; seg.read_fail = read_fail;
+    }
+};
+// Everything on `stream`; the grids are sized for the most segments the batch could have (n_reads + n_bases / seg_len) and surplus
+// lanes leave at once.  *declined = true: nothing of the plan was launched, the caller goes on with one lane per read.
+// `verdict` (optional, in / out): a caller that cuts one batch into several launches (the overlapped host path) lets
+// the first one probe and hands its verdict to the others -- 1: cut without probing (no read-back, the launch stays
+// asynchronous), 0: do not cut; -1 on entry: not decided yet.
+// cfg.seg_probe == 2: the CALLER decides (cfg.seg_verdict) -- no probe, no length reduction, no read-back: the launch
+// stays asynchronous (stream capture, callers that pipeline several streams).
+// `ragged_hint`: 1 / 0 when the caller knows the lengths (the *_host entry points), -1 when only the device does: then a big
+// batch costs one reduction kernel and a 4-byte read-back -- this call waits for `stream` there.
+// launch_probe(tally): launches the plan's probe kernel (is this a batch whose walks fall into step quickly?).
+template <typename Probe>
+hipError_t seg_prelude(const SegShape &sh, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, const LaunchCfg &cfg,
+                       hipStream_t stream, SegWorkspace *ws, int ragged_hint, bool *declined, int *verdict, Probe launch_probe,
+                       SegPrelude *P) {
+    *declined = true;
     int forced = -1;
     if (verdict && *verdict >= 0) forced = *verdict;
     if (cfg.seg_probe == 2) forced = cfg.seg_verdict ? 1 : 0;
-    if (forced == 0) { *declined = true; return hipSuccess; }
+    if (forced == 0) return hipSuccess;
     const bool probe = cfg.seg_probe == 1 && forced != 1;
-    // a verdict-only call (bins, no PML vector) keeps its PMLs in the workspace, sized from n_bases: for offsets that only
-    // the device has seen (ragged_hint < 0) the verdict of seg_decide_kernel -- which checks them -- is always read back
-    const bool ws_pml = bins.bin_width && !d_out;
-    if (ws_pml && ragged_hint < 0 && cfg.seg_probe == 2) { *declined = true; return hipSuccess; }
-    const bool read_back = probe || (ws_pml && ragged_hint < 0);
-    // Classification bins (bins.bin_width != 0): not fused into this walk -- a bin spans segments -- but reduced from the
-    // resident PML vector afterwards (classify_kernel: 2 B per base, streaming); without a caller's vector (d_out == NULL:
-    // verdicts only) the PMLs go to the workspace.
-    *declined = false;
-    const uint32_t S = call_seg_len(cfg, n_bases, 8);
-    if (cfg.seg_probe == 1 && n_reads >= (uint64_t)cfg.num_cus * 64ull * 4ull) {
-        if (ragged_hint == 0) { *declined = true; return hipSuccess; }
+    const bool read_back = probe || sh.read_back;
+    const uint32_t S = call_seg_len(cfg, n_bases, sh.waves);
+    hipError_t e = hipSuccess;
+    if (cfg.seg_probe == 1 && n_reads >= (uint64_t)cfg.num_cus * 64ull * sh.ragged_waves) {
+        if (ragged_hint == 0) return hipSuccess;
         if (ragged_hint < 0) {
-            if (ws->cap < 64) {
-                if (ws->buf) (void)hipFree(ws->buf);
-                ws->buf = nullptr;
-                ws->cap = 0;
-                hipError_t ea = hipMalloc(&ws->buf, 4096);
-                if (ea != hipSuccess) return ea;
-                ws->cap = 4096;
-            }
+            e = seg_ws_reserve(ws, 64, 4096);
+            if (e != hipSuccess) return e;
             uint32_t *d_max = static_cast<uint32_t *>(ws->buf), h_max = 0;
-            hipError_t ea = hipMemsetAsync(d_max, 0, 4, stream);
-            if (ea != hipSuccess) return ea;
+            e = hipMemsetAsync(d_max, 0, 4, stream);
+            if (e != hipSuccess) return e;
             hipLaunchKernelGGL(seg_maxlen_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, stream, d_offsets, n_reads, d_max);
-            ea = hipMemcpyAsync(&h_max, d_max, 4, hipMemcpyDeviceToHost, stream);
-            if (ea == hipSuccess) ea = hipStreamSynchronize(stream);
-            if (ea != hipSuccess) return ea;
-            if ((uint64_t)h_max * 2ull <= (n_bases / n_reads) * 3ull) { *declined = true; return hipSuccess; }   // longest read <= 1.5 x the mean
+            e = hipMemcpyAsync(&h_max, d_max, 4, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) return e;
+            if ((uint64_t)h_max * 2ull <= (n_bases / n_reads) * 3ull) return hipSuccess;   // longest read <= 1.5 x the mean
         }
     }
     const uint64_t max_seg = n_reads + n_bases / S + 1;
     if (max_seg > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const uint64_t n_ck = (n_bases >> 5) + 2;
     size_t temp_bytes = 0;
-    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr,
-                                                    (int)(n_reads + 1), stream);
+    e = hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (int)(n_reads + 1), stream);
     if (e != hipSuccess) return e;
     // carve the workspace
     size_t off = 0;
     auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes ? bytes : 8); return o; };
     const size_t o_nof = take((n_reads + 1) * 8), o_first = take((n_reads + 1) * 8), o_temp = take(temp_bytes),
                  o_in = take(max_seg * 8), o_out = take(max_seg * 8), o_len = take(max_seg * 4), o_j = take(max_seg * 4),
-                 o_rem = take(max_seg * 4), o_fin = take(max_seg * sizeof(SegFin)), o_tot = take(max_seg * sizeof(SegTot)),
+                 o_rem = take(max_seg * 4), o_fin = take(max_seg * sh.fin_bytes), o_tot = take(max_seg * sizeof(SegTot)),
                  o_join = take(max_seg * sizeof(SegJoin)), o_chain = take(max_seg), o_fail = take(n_reads),
-                 o_ck = take(n_ck * sizeof(SegCkpt)), o_go = take(32),
-                 o_pml = take((bins.bin_width && !d_out) ? n_bases * 2 : 0), o_err = take((bins.bin_width && !d_err) ? n_reads : 0);
-    if (ws->cap < off) {
-        if (ws->buf) (void)hipFree(ws->buf);
-        ws->buf = nullptr;
-        ws->cap = 0;
-        const size_t want = off + (off >> 3);
-        e = hipMalloc(&ws->buf, want);
-        if (e != hipSuccess) return e;
-        ws->cap = want;
-    }
+                 o_ck = take(n_ck * sh.ckpt_bytes), o_go = take(32);
+    size_t o_extra[2] = {0, 0};
+    for (int i = 0; i < sh.n_extra; ++i) o_extra[i] = take(sh.extra_bytes[i]);
+    e = seg_ws_reserve(ws, off, off + (off >> 3));
+    if (e != hipSuccess) return e;
     uint8_t *B = static_cast<uint8_t *>(ws->buf);
-    if (bins.bin_width && !d_out) d_out = reinterpret_cast<uint16_t *>(B + o_pml);
-    if (bins.bin_width && !d_err) d_err = B + o_err;
-    uint64_t *n_of = reinterpret_cast<uint64_t *>(B + o_nof), *first = reinterpret_cast<uint64_t *>(B + o_first);
-    uint64_t *seg_in = reinterpret_cast<uint64_t *>(B + o_in), *seg_out = reinterpret_cast<uint64_t *>(B + o_out);
-    uint32_t *seg_l = reinterpret_cast<uint32_t *>(B + o_len), *seg_j = reinterpret_cast<uint32_t *>(B + o_j),
-             *seg_rem = reinterpret_cast<uint32_t *>(B + o_rem);
-    SegJoin *join = reinterpret_cast<SegJoin *>(B + o_join);
-    uint8_t *on_chain = B + o_chain, *read_fail = B + o_fail;
-    SegArgs seg;
-    seg.seg_in = seg_in; seg.seg_out = seg_out; seg.seg_len = seg_l; seg.n_seg = first + n_reads;
-    seg.ckpt = reinterpret_cast<SegCkpt *>(B + o_ck);
-    seg.fin = reinterpret_cast<SegFin *>(B + o_fin);
-    seg.tot = reinterpret_cast<SegTot *>(B + o_tot);
-    seg.read_fail = read_fail;
-    uint32_t *go = reinterpret_cast<uint32_t *>(B + o_go);               // go | probes | probes in step
-    seg.go = go;
+    uint64_t *n_of = reinterpret_cast<uint64_t *>(B + o_nof);
+    P->max_seg = max_seg; P->first = reinterpret_cast<uint64_t *>(B + o_first);
+    P->seg_in = reinterpret_cast<uint64_t *>(B + o_in); P->seg_out = reinterpret_cast<uint64_t *>(B + o_out);
+    P->seg_l = reinterpret_cast<uint32_t *>(B + o_len); P->seg_j = reinterpret_cast<uint32_t *>(B + o_j);
+    P->seg_rem = reinterpret_cast<uint32_t *>(B + o_rem); P->join = reinterpret_cast<SegJoin *>(B + o_join);
+    P->on_chain = B + o_chain; P->read_fail = B + o_fail;
+    P->ckpt = B + o_ck; P->fin = B + o_fin; P->tot = reinterpret_cast<SegTot *>(B + o_tot);
+    uint32_t *go = P->go = reinterpret_cast<uint32_t *>(B + o_go);
+    for (int i = 0; i < sh.n_extra; ++i) P->extra[i] = B + o_extra[i];
     const unsigned bt256 = 256;
-    // the probe: is this a batch whose walks fall into step quickly?
     e = hipMemsetAsync(go, 0, 32, stream);
     if (e != hipSuccess) return e;
-    if (probe)
-        hipLaunchKernelGGL(seg_probe_kernel<6>, dim3(16), dim3(64), 0, stream, ix, d_bases, d_offsets, n_reads, 32u, 384u, go + 1);
+    if (probe) launch_probe(go + 1);
     hipLaunchKernelGGL(seg_decide_kernel, dim3(1), dim3(1), 0, stream, go + 1, (uint32_t)probe, go, d_offsets, n_reads, n_bases);
     if (read_back) {
         // The verdict is read back (this call waits for the probe): a batch it advises against then takes exactly the
@@ -842,73 +841,84 @@ static hipError_t launch_pml_segmented(const DevIndex &ix, const uint8_t *d_base
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         if (e != hipSuccess) return e;
         if (verdict && probe) *verdict = h_go ? 1 : 0;
-        if (!h_go) { *declined = true; return hipSuccess; }
+        if (!h_go) return hipSuccess;
     }
+    // (go == 0 -- a probe nobody read back cannot say so here, but offsets that break the contract can: seg_decide_kernel --
+    // leaves the plan without segments: K1 / K2 idle, seg_finalize_kernel hands every read to K3)
+    *declined = false;
     hipLaunchKernelGGL(seg_count_kernel, dim3((unsigned)((n_reads + 1 + bt256 - 1) / bt256)), dim3(bt256), 0, stream, d_offsets,
                        n_reads, S, n_of, go);
-    e = hipcub::DeviceScan::ExclusiveSum(B + o_temp, temp_bytes, n_of, first, (int)(n_reads + 1), stream);
+    e = hipcub::DeviceScan::ExclusiveSum(B + o_temp, temp_bytes, n_of, P->first, (int)(n_reads + 1), stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(seg_fill_kernel, dim3((unsigned)((n_reads + bt256 - 1) / bt256)), dim3(bt256), 0, stream, d_offsets,
-                       n_reads, S, first, seg_in, seg_out, seg_l, seg_j, seg_rem);
-    // K1 and K3b: the window-parallel lane state machine in blocks of one wavefront, capped like any big batch
+                       n_reads, S, P->first, P->seg_in, P->seg_out, P->seg_l, P->seg_j, P->seg_rem);
+    return hipSuccess;
+}
+}  // namespace
+
+// The segmented PML path: plan (seg_prelude), K1, K2, K3.  Nothing read back beyond the prelude's verdict.
+// Is there anything to gain?  One lane per read already fills the GPU when there are enough reads of about the same
+// length (100 k x 10 kbp: 40.5 Gbases/s either way); segments pay when lanes are scarce -- fewer than 4 wavefronts of reads
+// per CU: 60 k x 10 kbp 28.6 -> 34.3, 25 k 12.1 -> 31.4, 200 x 1 Mbp 0.11 -> 27 Gbases/s -- or when the batch is ragged
+// (its longest read holds a lane long after the others are done; log-normal lengths around 10 kbp: 12.2 -> 32.3).
+static hipError_t launch_pml_segmented(const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
+                                       uint64_t n_bases, uint16_t *d_out, uint8_t *d_err, DevStats *d_stats,
+                                       const LaunchCfg &cfg, hipStream_t stream, SegWorkspace *ws, bool big_batch_cap,
+                                       int ragged_hint, bool *declined, const ClsArgs &bins, int *verdict, LaunchInfo *info) {
+    // a verdict-only call (bins, no PML vector) keeps its PMLs in the workspace, sized from n_bases: for offsets that only
+    // the device has seen (ragged_hint < 0) the verdict of seg_decide_kernel -- which checks them -- is always read back
+    const bool ws_pml = bins.bin_width && !d_out;
+    if (ws_pml && ragged_hint < 0 && cfg.seg_probe == 2) { *declined = true; return hipSuccess; }
+    // Classification bins (bins.bin_width != 0): not fused into this walk -- a bin spans segments -- but reduced from the
+    // resident PML vector afterwards (classify_kernel: 2 B per base, streaming); without a caller's vector (d_out == NULL:
+    // verdicts only) the PMLs go to the workspace.
+    const SegShape shape = {kSegWavesPml, kSegRaggedWavesPml, sizeof(SegFin), sizeof(SegCkpt), 2,
+                            {ws_pml ? (size_t)n_bases * 2 : 0, (bins.bin_width && !d_err) ? (size_t)n_reads : 0}, ws_pml && ragged_hint < 0};
+    SegPrelude pre;
+    hipError_t e = seg_prelude(shape, d_offsets, n_reads, n_bases, cfg, stream, ws, ragged_hint, declined, verdict, [&](uint32_t *tally) {
+        hipLaunchKernelGGL(seg_probe_kernel<6>, dim3(16), dim3(64), 0, stream, ix, d_bases, d_offsets, n_reads, 32u, 384u, tally);
+    }, &pre);
+    if (e != hipSuccess || *declined) return e;
+    if (ws_pml) d_out = reinterpret_cast<uint16_t *>(pre.extra[0]);
+    if (bins.bin_width && !d_err) d_err = pre.extra[1];
+    const uint64_t max_seg = pre.max_seg;
+    SegArgs seg;
+    pre.fill(seg, n_reads);
+    seg.go = pre.go;
+    const unsigned bt256 = 256;
+    // K1 and K3b: the window-parallel lane state machine in blocks of one wavefront, capped like any big batch (plan_pml_seg)
     const int bt = 64;
-    const bool seg_deep = ix.rows3 != nullptr && ix.idx32 != 0u && cfg.deep > 0 && cfg.stage_reads != 0;   // K1 / K3 on the deep rows only on request ("deep" 1): segments are long reads (launch_pml's rule)
-    auto lds_for = [&](uint64_t lanes) -> size_t {
-        int wpc = cfg.waves_per_cu;
-        if (wpc < 0) wpc = 0;
-        if (cfg.waves_per_cu == 0 && big_batch_cap && lanes > (uint64_t)cfg.num_cus * 64u * 18u)
-            wpc = ((ix.rows2 != nullptr || seg_deep) && cfg.stage_reads != 0) ? kCapWavesAhead : kCapWaves;
-        if (wpc > 0 && wpc < 32) return ((163840u / (unsigned)wpc) & ~1023u) - 1024u;
-        return 0;
-    };
-    const ClsArgs cls;
-    const uint32_t *d_order = nullptr;
-    // (segments and re-walked reads stage their bases through LDS and walk on the look-ahead rows like any other launch:
-    // launch_pml's policy -- the cap's padding, or what the launch's wavefronts per CU leave of the CU's LDS)
+    const TableFacts T = facts(ix);
+    const PmlPlan k1 = plan_pml_seg(T, cfg, max_seg, big_batch_cap), k3 = plan_pml_seg(T, cfg, n_reads, big_batch_cap);
     DevIndex ixl = ix;
     ixl.inwin = cfg.inwin ? 1u : 0u;
+    const bool seg_deep = ix.rows3 != nullptr && ix.idx32 != 0u && cfg.deep > 0 && cfg.stage_reads != 0;
     ixl.hint_w = seg_deep ? (cfg.hints != 0 ? 2u : 0u) : ((cfg.hints != 0 && ix.hints != 0u && ix.rows2 != nullptr) ? 3u : 0u);
-    // (pair-shared gathers on tables beyond the TLBs' reach: launch_pml's rule)
-    const bool seg_pair = !seg_deep && (cfg.pair_loads > 0 || (cfg.pair_loads < 0 && ix.r * (ix.rows2 != nullptr ? 16ull : 8ull) >= kPairLoadBytes));
-    size_t dyn_lds = 0;
-    bool seg_ring = false;
-    auto stage_for = [&](uint64_t lanes) {
-        dyn_lds = lds_for(lanes);
-        if (cfg.stage_reads != 0 && dyn_lds == 0) {
-            const uint64_t wn = ((lanes + bt - 1) / bt + (uint64_t)cfg.num_cus - 1) / (uint64_t)cfg.num_cus;
-            if (wn <= 18) dyn_lds = std::min<size_t>(21504 + (cfg.out_ring != 0 ? kOutRingBytes : 0u), ((163840u / (unsigned)(wn + std::max<uint64_t>(2, wn / 4))) & ~1023u) - 1024u);
-        }
-        // (segments are long reads: their PMLs leave through the ring in LDS where the block has room for it -- launch_pml)
-        const size_t ring_b = (cfg.out_ring != 0 && cfg.stage_reads != 0 && dyn_lds >= kOutRingBytes + 96u * 64u) ? kOutRingBytes : 0;
-        const uint32_t cap = (uint32_t)std::min<size_t>(1024, ((dyn_lds - ring_b) / 64) & ~(size_t)15);
-        ixl.stage_lds = (cfg.stage_reads != 0 && cap >= 96) ? cap : 0u;
-        seg_ring = ring_b != 0 && ixl.stage_lds != 0u;
-    };
-    auto launch_seg = [&](int segv, uint64_t lanes, LaunchInfo *li) -> hipError_t {
-        stage_for(lanes);
+    auto launch_seg = [&](int segv, uint64_t lanes, const PmlPlan &sp, LaunchInfo *li) -> hipError_t {
+        ixl.stage_lds = sp.stage_lds;
         WalkLaunch L;
-        L.grid = dim3((unsigned)((lanes + bt - 1) / bt)); L.block = dim3(bt); L.dyn_lds = dyn_lds; L.stream = stream;
+        L.grid = dim3((unsigned)((lanes + bt - 1) / bt)); L.block = dim3(bt); L.dyn_lds = sp.dyn_lds; L.stream = stream;
         L.ix = ixl; L.bases = d_bases; L.offs = d_offsets; L.n = lanes; L.out = d_out; L.err = d_err; L.stats = d_stats;
-        L.order = d_order; L.cls = cls; L.seg = seg;
-        L.cls_mode = 0; L.sep = ix.sep ? 1 : 0; L.stg = ixl.stage_lds != 0u ? 1 : 0;
-        L.ahd = (L.stg && seg_deep) ? 2 : ((L.stg && ix.rows2 != nullptr) ? 1 : 0); L.psh = (L.stg && seg_pair) ? 1 : 0; L.ring = seg_ring ? 1 : 0;
+        L.seg = seg;
+        L.cls_mode = 0; L.sep = ix.sep ? 1 : 0; L.stg = sp.stage_lds != 0u ? 1 : 0;
+        L.ahd = sp.use_deep ? 2 : (sp.use_ahead ? 1 : 0); L.psh = sp.use_pair ? 1 : 0; L.ring = sp.use_ring ? 1 : 0;
         return ix.idx32 ? launch_walkseg_u32(segv, L, li) : launch_walkseg_u64(segv, L, li);
     };
-    e = launch_seg(1, max_seg, info);
+    e = launch_seg(1, max_seg, k1, info);
     if (e != hipSuccess) return e;
     if (info) {                                           // the dominant kernel: K1
         info->variant = 14; info->block_threads = 64; info->segmented = 1; info->idx64 = ix.idx32 ? 0 : 1;
-        info->waves_per_cu = 0; info->staged = (int)ixl.stage_lds; info->ahead = ixl.stage_lds == 0u ? 0 : (seg_deep ? 2 : (ix.rows2 != nullptr ? 1 : 0));
+        info->waves_per_cu = 0; info->staged = (int)k1.stage_lds; info->ahead = k1.use_deep ? 2 : (k1.use_ahead ? 1 : 0);
     }
     // (blocks of one wavefront: a boundary lane that has to walk far holds up only the 63 beside it)
     const uint32_t max_over = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (uint64_t)cfg.seg_len * (uint64_t)kSegOverrun);
     hipLaunchKernelGGL((seg_stitch_kernel<6, 0>), dim3((unsigned)((max_seg + kStitchLanes - 1) / kStitchLanes)), dim3(64), 0, stream, ix, d_bases, seg,
-                       seg_j, seg_rem, max_over, on_chain, d_out, join);
-    hipLaunchKernelGGL(seg_finalize_kernel, dim3((unsigned)((n_reads + bt256 - 1) / bt256)), dim3(bt256), 0, stream, go, first, n_reads,
-                       seg.tot, join, seg_l, seg_rem, on_chain, read_fail, d_err, d_stats);
+                       pre.seg_j, pre.seg_rem, max_over, pre.on_chain, d_out, pre.join);
+    hipLaunchKernelGGL(seg_finalize_kernel, dim3((unsigned)((n_reads + bt256 - 1) / bt256)), dim3(bt256), 0, stream, pre.go, pre.first, n_reads,
+                       seg.tot, pre.join, pre.seg_l, pre.seg_rem, pre.on_chain, pre.read_fail, d_err, d_stats);
     hipLaunchKernelGGL((seg_stitch_kernel<6, 1>), dim3((unsigned)((max_seg + kStitchLanes - 1) / kStitchLanes)), dim3(64), 0, stream, ix, d_bases, seg,
-                       seg_j, seg_rem, max_over, on_chain, d_out, join);
-    e = launch_seg(2, n_reads, nullptr);
+                       pre.seg_j, pre.seg_rem, max_over, pre.on_chain, d_out, pre.join);
+    e = launch_seg(2, n_reads, k3, nullptr);
     if (e == hipSuccess) e = hipGetLastError();
     if (e == hipSuccess && bins.bin_width)
         e = launch_classify(d_out, d_offsets, n_reads, bins.bin_width, bins.thr, bins.above, bins.below, bins.sum_max, stream, d_err);
@@ -1005,120 +1015,19 @@ size_t take_launch_log(char *buf, size_t cap) {
     return all.size();
 }
 
-// The launch policy of one PML call, apart from the segment plan's own decisions (launch_pml_segmented): which kernel, which block,
-// how much dynamic LDS and what it holds.  launch_pml acts on it; pml_mask_needs_tmp asks it whether the reset-mask output can
-// come straight from the walk.
-namespace {
-struct PmlPlan {
-    int v = 14, bt = 64, wpc = 0;
-    bool seg_eligible = false;       // a batch of long reads: the segment plan gets the first say (it may decline)
-    size_t dyn_lds = 0;
-    uint32_t stage_lds = 0;
-    bool use_ring = false, use_ahead = false, use_pair = false;
-    bool use_deep = false;           // the walk runs on the deep rows (DevIndex::rows3: three bases per gather)
-};
-PmlPlan plan_pml(const DevIndex &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, int cm, bool logging, bool have_seg_ws,
-                 bool ordered, bool want_mask) {
-    PmlPlan P;
-    // Variants: 0 first correct kernel (serves --logs), 1 base-synchronous packed I/O (tables of fewer than 8 rows, batches of
-    // fewer than 16 bases; A/B), 14 = the lane state machine over row windows (pml_kernel_flatp, movi_walk.hpp; the default).
-    // (2-13 were experiments -- branchy / row-at-a-time state machines, 2/4-row neighbour windows, the unpipelined window
-    // kernel, hop-by-hop advances, lane refill -- measured slower or no faster and removed; numbers in DESIGN.md section 3.)
-    // Auto selection (measured on MI355X, profiles/r02_*): the state machine in blocks of ONE wavefront, and -- when there are
-    // more reads than ~18 waves per CU -- at most kCapWaves wavefronts resident per CU.  Why a cap: between two
-    // iterations of a lane its cache lines (the row window's neighbours, its read, its output) must survive in the
-    // 4 MiB L2 of its XCD; with all 32 wave slots of a CU walking, 8 MiB of lines are in flight per XCD and neighbour
-    // rows are refetched from the fabric.  1 M x 150 bp, Gbases/s, uncapped / capped at 8-10 waves per CU /
-    // variant 1 (base-synchronous: its neighbour loads follow the gather at once, so it wants all the occupancy it can
-    // get): pangenome 14 M rows 43.2 / 48.2 / 46.4; random tables of 10 M rows 40.0 / 47.5 / 43.6, 60 M 35.7 / 40.8 /
-    // 36.3, 250 M (2 GB) 29.1 / 32.8 / 29.2, 500 M 27.9 / 30.3 / 27.7, 1 B (8 GB) 27.4 / 27.7 / 28.3.
-    int v = cfg.pml_variant;
-    // (batches of up to ~18 waves per CU run in ONE round, uncapped: with the cap, 224 k reads = 13.7 waves per CU run as
-    // a full round of 9 and a half-empty one -- 38.3 against 39.2 Gbases/s; 300 k reads: 38.2 against 41.2; from 400 k
-    // reads on the cap wins: 43.9 against 41.7.  profiles/r02_occupancy_cap_sweeps.txt)
-    const bool big_batch = n_reads > (uint64_t)cfg.num_cus * 64u * 18u;
-    if (v < 0) v = 14;
-    if (v == 14 && (ix.r < 8 || n_bases < 16)) v = 1;                        // the clamped window needs >= 4 rows (r >= 8: two windows), the
-                                                                             // 16-base fetches >= 16 bytes of bases
-    if (cm != 0 && v == 0) v = 1;                                            // the first kernel carries no fused bins
-    if (logging) v = 0;                                                      // per-base logs: the first kernel keeps them
-    P.v = v;
-    // Batches of long reads: segment-parallel (plain PML through the default kernel only).  One lane per read leaves the
-    // GPU short of walks -- 100 k reads are 6 wavefronts per CU, and a single 1 Mbp read holds its lane for 2 s --;
-    // cut into segments the same batch fills it like a batch of short reads.
-    P.seg_eligible = have_seg_ws && !logging && cfg.seg_len >= 32 && !ordered && v == 14 && cfg.block_threads <= 64 &&
-                     n_bases / n_reads >= 2ull * (uint64_t)cfg.seg_len && n_reads + n_bases / (uint64_t)cfg.seg_len < 0x7FFFFFF0ull;
-    const int bt = cfg.block_threads > 0 ? cfg.block_threads : 64;           // one wavefront per block: finest dispatch grain
-    P.bt = bt;
-    const uint64_t blocks = (n_reads + bt - 1) / bt;
-    int wpc = cfg.waves_per_cu;
-    if (wpc < 0) wpc = 0;
-    const bool stage_ok = cfg.stage_reads != 0 && bt == 64 && v == 14;                  // the staged kernels: one-wavefront blocks of the default walk
-    // ... on the deep rows where the handle holds them and the batch is one of short reads: three bases per gather pay where reads follow the
-    // text (c2: fabric lines per base 0.584 -> 0.477, 80.3 -> 89.6 Gbases/s with reset masks out); 10 kbp reads with 8 % substitutions spend
-    // their iterations on repositions, which three-row windows serve worse than four-row ones (59.3 -> 44.4): profiles/r06_deep_rows.txt
-    const bool deep_ok = stage_ok && ix.rows3 != nullptr && ix.idx32 != 0u &&
-                         (cfg.deep > 0 || (cfg.deep < 0 && n_bases / n_reads < kDeepReadLen));
-    const bool ahead_ok = stage_ok && (ix.rows2 != nullptr || deep_ok);                 // ... or on the look-ahead rows
-    if (cfg.waves_per_cu == 0 && v == 14 && big_batch)
-        wpc = deep_ok ? kCapWavesDeep : (ahead_ok ? kCapWavesAhead : kCapWaves);     // the auto policy above
-    P.wpc = wpc;
-    // Occupancy cap: enforced by the dispatcher through the block's LDS allocation (160 KiB per CU); blocks beyond
-    // the cap queue and start as resident ones retire.
-    size_t dyn_lds = 0;
-    if (wpc > 0) {
-        int bpc = wpc / (bt / 64);
-        if (bpc < 1) bpc = 1;
-        if (bpc < 32) dyn_lds = ((163840u / (unsigned)bpc) & ~1023u) - 1024u;
-    }
-    // Reads staged through LDS (pml_kernel_flatp<..., STG = 1>): the block's dynamic LDS holds the next stage_lds bases of each
-    // of its 64 reads.  A capped launch has that LDS anyway (the padding: 21 KiB = 336 bases per lane at the default cap of 7
-    // wavefronts per CU, 16 KiB = 256 at 9); an uncapped one (a batch of at most ~18 wavefronts per CU, one round) gets what
-    // its wavefronts per CU leave of the 160 KiB, so that the round stays one round.  Long reads roll through the same
-    // stretch (stage_from in the kernel).  cfg.stage_reads: 1 = whenever it fits (default), 0 = never.
-    // PMLs out through a ring in LDS (the kernel has the numbers): launches of long reads -- few wavefronts, each
-    // one's own instruction stream most of an iteration -- where the block's LDS holds the ring beside 96 staged bases.
-    // cfg.out_ring: -1 = this policy, 0 / 1 = never / wherever it fits (A/B).  (Reset masks out: no PML leaves, no ring.)
-    const bool ring_wanted = stage_ok && !want_mask && (cfg.out_ring > 0 || (cfg.out_ring < 0 && n_bases / n_reads >= kOutRingReadLen));
-    if (stage_ok && wpc == 0) {
-        const uint64_t wn = (blocks + (uint64_t)cfg.num_cus - 1) / (uint64_t)cfg.num_cus;      // wavefronts per CU of this launch
-        // (room for a quarter more: the dispatcher does not deal the blocks out evenly, and a CU that may hold no more than the
-        // average leaves its surplus queued -- 150 k reads, 9.2 wavefronts per CU: 41.2 Gbases/s with room for 10, 45.8 for 12)
-        const uint64_t room = wn + std::max<uint64_t>(2, wn / 4);
-        if (wn <= 18) dyn_lds = std::min<size_t>(21504 + (ring_wanted ? kOutRingBytes : 0u), ((163840u / (unsigned)room) & ~1023u) - 1024u);
-    }
-    const size_t ring_b = (ring_wanted && dyn_lds >= kOutRingBytes + 96u * 64u) ? kOutRingBytes : 0;
-    const uint32_t stage_cap = (uint32_t)std::min<size_t>(1024, ((dyn_lds - ring_b) / 64) & ~(size_t)15);
-    P.dyn_lds = dyn_lds;
-    P.stage_lds = (stage_ok && stage_cap >= 96) ? stage_cap : 0u;
-    P.use_ring = ring_b != 0 && P.stage_lds != 0u;
-    P.use_deep = deep_ok && P.stage_lds != 0u;
-    P.use_ahead = ahead_ok && P.stage_lds != 0u;
-    // pair-shared gathers (pml_kernel_flatp<..., PSH = 1>): the staged default walk on the plain or the look-ahead rows
-    // Where: on tables beyond the reach of the per-CU TLBs (~2 GB), where a lane's two (four) 16-byte loads are as many
-    // translation requests and the L2 TLB's request rate bounds the walk -- real BWT of 226 M rows on the look-ahead rows (3.6 GB
-    // copy) 39.4 -> 50.8 Gbases/s, the random 1 B-row table 32.6 -> 34.7 on its plain rows and 21.4 -> 44.2 on the look-ahead
-    // copy (16 GB); below that the exchange costs about what the merged accesses give (random 25 / 50 / 100 M rows +4 / +5 / -2 %,
-    // real 113 M rows +1.5 %, c2 -2.5 %, c3 -9 %: profiles/r04_pair_shared_gathers.txt).  "pair_loads" 1 / 0 forces it.
-    const uint64_t walked_bytes = ix.r * (P.use_ahead ? 16ull : 8ull);
-    P.use_pair = (cfg.pair_loads > 0 || (cfg.pair_loads < 0 && walked_bytes >= kPairLoadBytes)) && P.stage_lds != 0u && v == 14 && !P.use_deep;
-    return P;
-}
-}  // namespace
-
 // movi_pml_device's own choice ("pml_via_mask" -1): the vector through reset masks wherever the default walk writes the masks itself and
 // the register packer would otherwise write the vector -- batches of short reads (mean length below kOutRingReadLen; long reads keep the
 // ring in LDS, which is as good there: c3 16.76 against 16.66 ms).  Measured, vector out, packer -> fused masks: c2 on the deep rows 78.4
 // -> 86.7 Gbases/s, the random 10 M-row table 62.4 -> 64.8, the 1 B-row table 42.3 -> 46.0 (profiles/r06_mask_path.txt).
 bool pml_vector_via_masks(const DevIndex &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, bool have_seg_ws, bool ordered) {
     if (n_reads == 0) return false;
-    const PmlPlan P = plan_pml(ix, cfg, n_reads, n_bases, 0, false, have_seg_ws, ordered, true);
+    const PmlPlan P = plan_pml(facts(ix), cfg, n_reads, n_bases, 0, false, have_seg_ws, ordered, true);
     return !P.seg_eligible && P.v == 14 && P.stage_lds != 0u && n_bases / n_reads < kOutRingReadLen;
 }
 
 bool pml_mask_needs_tmp(const DevIndex &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, bool have_seg_ws) {
     if (n_reads == 0) return false;
-    const PmlPlan P = plan_pml(ix, cfg, n_reads, n_bases, 0, false, have_seg_ws, false, true);
+    const PmlPlan P = plan_pml(facts(ix), cfg, n_reads, n_bases, 0, false, have_seg_ws, false, true);
     return P.seg_eligible || P.v != 14 || P.stage_lds == 0u;
 }
 
@@ -1132,7 +1041,7 @@ hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
     const bool logging0 = cls.log_ff != nullptr || cls.log_scan != nullptr;
     if (want_mask && mask.expand_out) {
         // the caller wants the VECTOR and lends scratch for masks: through masks only where the walk writes them itself
-        const PmlPlan P0 = plan_pml(ix, cfg, n_reads, n_bases, 0, logging0, seg_ws != nullptr, d_order != nullptr, true);
+        const PmlPlan P0 = plan_pml(facts(ix), cfg, n_reads, n_bases, 0, logging0, seg_ws != nullptr, d_order != nullptr, true);
         if (P0.seg_eligible || P0.v != 14 || P0.stage_lds == 0u || cls.bin_width != 0) {
             want_mask = false;
             d_out = mask.expand_out;
@@ -1147,7 +1056,7 @@ hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
     if (mode != 6) return hipErrorInvalidValue;
     const bool logging = cls.log_ff != nullptr || cls.log_scan != nullptr;
     if (logging && (cm != 0 || want_mask)) return hipErrorInvalidValue;
-    const PmlPlan P = plan_pml(ix, cfg, n_reads, n_bases, cm, logging, seg_ws != nullptr, d_order != nullptr, want_mask);
+    const PmlPlan P = plan_pml(facts(ix), cfg, n_reads, n_bases, cm, logging, seg_ws != nullptr, d_order != nullptr, want_mask);
     const int v = P.v;
     if (P.seg_eligible && (!want_mask || d_out)) {
         bool declined = false;
@@ -1451,66 +1360,6 @@ __global__ __launch_bounds__(256) void count_kernel_v0(DevIndex ix, const uint8_
         if (scw) atomicAdd(&stats->scans, (unsigned long long)scw);
         if (erw) atomicAdd(&stats->errors, (unsigned long long)erw);
     }
-}
-
-// the count query as a lane state machine (zml_kernel_flat<..., CNT = 1>, with the ZML kernels below)
-static hipError_t launch_count_flat(int mode, const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
-                                    uint64_t *d_matched, uint64_t *d_count, uint8_t *d_err, DevStats *d_stats, const uint32_t *d_order,
-                                    const LaunchCfg &cfg, hipStream_t stream, LaunchInfo *info, bool pair);
-
-hipError_t launch_count(int mode, const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets,
-                        uint64_t n_reads, uint64_t *d_matched, uint64_t *d_count, uint8_t *d_err,
-                        DevStats *d_stats, const uint32_t *d_order, const LaunchCfg &cfg, hipStream_t stream,
-                        LaunchInfo *info, uint64_t n_bases) {
-    if (n_reads == 0) return hipSuccess;
-    // Blocks of one wavefront; on a cache-resident table (up to the 256 MiB of the Infinity Cache) and a batch of more than
-    // ~24 wavefronts of reads per CU at most kCountCapWaves wavefronts resident per CU -- the same L2-retention effect as in
-    // launch_pml: the search's neighbour rows (interval shrink, fast-forwards) must survive between a lane's steps.
-    // profiles/r03_count_ftab.txt: pangenome 61.2 -> 67.5 Gbases/s (cap 15 - 16; 14: 66.2, 17: 64.2, 20: 62.5), random 80 MB
-    // table 52.4 -> 54.6; HBM-resident tables lose with any cap (1.6 GB: 47.3 uncapped, 43.2 at 16) or are indifferent (8 GB).
-    const int bt = cfg.block_threads > 0 ? cfg.block_threads : 64;
-    int wpc = cfg.waves_per_cu > 0 ? cfg.waves_per_cu : 0;
-    const bool ahead = mode == 6 && ix.rows2 != nullptr && ix.rows2_count != 0u;   // the search walks on the look-ahead rows where they pay
-    // Round 5 -- the search as a LANE STATE MACHINE over row windows (zml_kernel_flat<..., CNT = 1>; by pairs of lanes on plain rows of
-    // 2 GB and more) wherever it can run: tables of 8 rows and more, batches of 16 bases and more, one-wavefront blocks.  Gbases/s of
-    // read bases, count_kernel_v0 -> the state machine (profiles/r05_c5_count_pmc.txt): the 1 B-row blocked-thresholds table of BASELINE
-    // config 5 37.2 -> 56.4 - 56.9 (without the pairs 32.3), random 200 M rows 46.6 -> 68.0, the c2 pangenome 71.4 (on its look-ahead
-    // rows) -> 84.0 (on the plain rows).  cfg.count_variant: -1 = this policy, 0 = count_kernel_v0 (A/B; tiny tables and batches), 1 = the
-    // state machine or nothing.
-    const bool flat_ok = (mode == 6 || mode == 3) && ix.r >= 8 && n_bases >= 16 && bt == 64;
-    const bool big = ix.r * 8ull >= kPairLoadBytes;
-    if (flat_ok && cfg.count_variant != 0)
-        return launch_count_flat(mode, ix, d_bases, d_offsets, n_reads, d_matched, d_count, d_err, d_stats, d_order, cfg, stream, info,
-                                 cfg.pair_loads > 0 || (cfg.pair_loads < 0 && big));
-    if (cfg.count_variant > 0) return hipErrorInvalidValue;
-    if (cfg.waves_per_cu == 0 && ix.r * (ahead ? 16ull : 8ull) <= (256ull << 20) &&   // (the bytes of the table the search walks on)
-        n_reads > (uint64_t)cfg.num_cus * 64ull * 24ull) wpc = kCountCapWaves;
-    size_t dyn_lds = 0;
-    if (wpc > 0) {
-        int bpc = wpc / (bt / 64);
-        if (bpc < 1) bpc = 1;
-        if (bpc < 32) dyn_lds = std::min<size_t>(65536 - 1024, ((163840u / (unsigned)bpc) & ~1023u) - 1024u);
-    }
-    if (info) {
-        snprintf(info->kernel, sizeof(info->kernel), "count_kernel_v0<%d, %d>", mode, ahead ? 1 : 0);
-        info->variant = 0; info->block_threads = bt; info->waves_per_cu = wpc; info->segmented = 0; info->idx64 = 1; info->staged = 0;
-        info->ahead = ahead ? 1 : 0;
-    }
-    const uint64_t blocks = (n_reads + bt - 1) / bt;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    dim3 grid((unsigned)blocks), block((unsigned)bt);
-    // resident layouts: 6 = regular-thresholds rows, 3 = regular rows (threshold-less types: 12-bit lengths)
-    if (mode == 6 && ahead)
-        hipLaunchKernelGGL((count_kernel_v0<6, 1>), grid, block, dyn_lds, stream, ix, d_bases, d_offsets, n_reads,
-                           d_matched, d_count, d_err, d_stats, d_order);
-    else if (mode == 6)
-        hipLaunchKernelGGL(count_kernel_v0<6>, grid, block, dyn_lds, stream, ix, d_bases, d_offsets, n_reads,
-                           d_matched, d_count, d_err, d_stats, d_order);
-    else if (mode == 3)
-        hipLaunchKernelGGL(count_kernel_v0<3>, grid, block, dyn_lds, stream, ix, d_bases, d_offsets, n_reads,
-                           d_matched, d_count, d_err, d_stats, d_order);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------- ZML
@@ -2275,188 +2124,140 @@ __global__ __launch_bounds__(256) void zml_kernel_flat(DevIndex ix, const uint8_
     }
 }
 
-// The segmented ZML parse (the PML one, launch_pml_segmented, has the reasoning): plan, probe (verdict read back), K1 =
-// zml_kernel<MODE, 1> over the segments, K2 = zml_stitch_kernel find + write, K3 = seg_finalize_kernel + zml_kernel<MODE, 2>.
+// ---- from a launch's run-time choices (ZmlLaunch, movi_kernels.hpp) to its instantiation, as walk_go / walk_pick do for the PML walk
+// (movi_walk.hpp).  The kernel is named once, from the template arguments, as rocprofv3 prints it -- every argument, none dropped:
+// tests/test_zml_coverage_gpu.py holds these names to the code object's symbols.
+static hipError_t zml_launched(const char *name, LaunchInfo *info) {
+    if (info) snprintf(info->kernel, sizeof(info->kernel), "%s", name);
+    note_walk_launch(name);
+    return hipGetLastError();
+}
+template <int MODE, typename IdxT, int SEG, int AH, int PSH, int CNT>
+static hipError_t zml_go(const ZmlLaunch &L, LaunchInfo *info) {
+    hipLaunchKernelGGL((zml_kernel_flat<MODE, IdxT, SEG, AH, PSH, CNT>), L.grid, L.block, L.dyn_lds, L.stream, L.ix, L.bases, L.offs, L.n, L.out,
+                       L.err, L.stats, L.order, L.seg_args, L.matched, L.count);
+    char name[96];
+    snprintf(name, sizeof(name), "zml_kernel_flat<%d, %s, %d, %d, %d, %d>", MODE, sizeof(IdxT) == 4 ? "unsigned int" : "unsigned long", SEG, AH, PSH, CNT);
+    return zml_launched(name, info);
+}
+template <int MODE, int SEG>
+static hipError_t zml_sync_go(const ZmlLaunch &L, LaunchInfo *info) {
+    hipLaunchKernelGGL((zml_kernel<MODE, SEG>), L.grid, L.block, L.dyn_lds, L.stream, L.ix, L.bases, L.offs, L.n, L.out, L.err, L.stats, L.order,
+                       L.seg_args);
+    char name[96];
+    snprintf(name, sizeof(name), "zml_kernel<%d, %d>", MODE, SEG);
+    return zml_launched(name, info);
+}
+template <int MODE, int AH>
+static hipError_t count_v0_go(const ZmlLaunch &L, LaunchInfo *info) {
+    hipLaunchKernelGGL((count_kernel_v0<MODE, AH>), L.grid, L.block, L.dyn_lds, L.stream, L.ix, L.bases, L.offs, L.n, L.matched, L.count, L.err,
+                       L.stats, L.order);
+    if (info) snprintf(info->kernel, sizeof(info->kernel), "count_kernel_v0<%d, %d>", MODE, AH);   // (the launch log never listed this kernel)
+    return hipGetLastError();
+}
+// the state machine: K1 of the segment plan runs on the plain rows with every lane's own loads; the look-ahead rows are mode 6's and exclude the pairs
+template <int MODE, typename IdxT>
+static hipError_t zml_pick(const ZmlLaunch &L, LaunchInfo *info) {
+    if (L.seg) return zml_go<MODE, IdxT, 1, 0, 0, 0>(L, info);
+    if (L.ahead) {
+        if constexpr (MODE == 6) {
+            if (L.pair) return hipErrorInvalidValue;
+            return L.cnt ? zml_go<6, IdxT, 0, 1, 0, 1>(L, info) : zml_go<6, IdxT, 0, 1, 0, 0>(L, info);
+        } else {
+            return hipErrorInvalidValue;
+        }
+    }
+    switch ((L.pair ? 2 : 0) | (L.cnt ? 1 : 0)) {
+    case 0: return zml_go<MODE, IdxT, 0, 0, 0, 0>(L, info);
+    case 1: return zml_go<MODE, IdxT, 0, 0, 0, 1>(L, info);
+    case 2: return zml_go<MODE, IdxT, 0, 0, 1, 0>(L, info);
+    default: return zml_go<MODE, IdxT, 0, 0, 1, 1>(L, info);
+    }
+}
+// the base-synchronous kernels: zml_kernel over reads (0), segments (1: K1) or re-walked reads (2: K3); count_kernel_v0
+template <int MODE>
+static hipError_t zml_sync_pick(const ZmlLaunch &L, LaunchInfo *info) {
+    if (L.cnt) {
+        if constexpr (MODE == 6) { if (L.ahead) return count_v0_go<6, 1>(L, info); }
+        return L.ahead ? hipErrorInvalidValue : count_v0_go<MODE, 0>(L, info);
+    }
+    switch (L.seg) {
+    case 0: return zml_sync_go<MODE, 0>(L, info);
+    case 1: return zml_sync_go<MODE, 1>(L, info);
+    default: return zml_sync_go<MODE, 2>(L, info);
+    }
+}
+static hipError_t zml_dispatch(const ZmlLaunch &L, LaunchInfo *info) {
+    if (L.mode == 6) return !L.flat ? zml_sync_pick<6>(L, info) : (L.idx32 ? zml_pick<6, uint32_t>(L, info) : zml_pick<6, uint64_t>(L, info));
+    if (L.mode == 3) return !L.flat ? zml_sync_pick<3>(L, info) : (L.idx32 ? zml_pick<3, uint32_t>(L, info) : zml_pick<3, uint64_t>(L, info));
+    return hipErrorInvalidValue;
+}
+
+// The segmented ZML parse (the PML one, launch_pml_segmented, has the reasoning): plan and probe (seg_prelude), K1 = the state machine or
+// zml_kernel<MODE, 1> over the segments (zml_seg_k1_flat), K2 = zml_stitch_kernel find + write, K3 = seg_finalize_kernel + zml_kernel<MODE, 2>.
 // Unlike the PML walk the ZML parse is latency-bound even on a full batch of long reads (100 k x 10 kbp: 19 Gbases/s), so
 // there is something to gain up to 8 wavefronts of reads per CU.
 template <int MODE>
 static hipError_t launch_zml_segmented(const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
                                        uint64_t n_bases, uint16_t *d_out, uint8_t *d_err, DevStats *d_stats, const LaunchCfg &cfg,
-                                       hipStream_t stream, SegWorkspace *ws, int ragged_hint, bool *declined, int *verdict) {
-    *declined = false;
-    int forced = -1;                                       // as launch_pml_segmented: seg_probe == 2 = the caller's verdict
-    if (verdict && *verdict >= 0) forced = *verdict;
-    if (cfg.seg_probe == 2) forced = cfg.seg_verdict ? 1 : 0;
-    if (forced == 0) { *declined = true; return hipSuccess; }
-    const bool probe = cfg.seg_probe == 1 && forced != 1;
-    const uint32_t S = call_seg_len(cfg, n_bases, 24);
-    hipError_t e = hipSuccess;
-    if (cfg.seg_probe == 1 && n_reads >= (uint64_t)cfg.num_cus * 64ull * 8ull) {
-        if (ragged_hint == 0) { *declined = true; return hipSuccess; }
-        if (ragged_hint < 0) {
-            if (ws->cap < 64) {
-                if (ws->buf) (void)hipFree(ws->buf);
-                ws->buf = nullptr;
-                ws->cap = 0;
-                e = hipMalloc(&ws->buf, 4096);
-                if (e != hipSuccess) return e;
-                ws->cap = 4096;
-            }
-            uint32_t *d_max = static_cast<uint32_t *>(ws->buf), h_max = 0;
-            e = hipMemsetAsync(d_max, 0, 4, stream);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(seg_maxlen_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, stream, d_offsets, n_reads, d_max);
-            e = hipMemcpyAsync(&h_max, d_max, 4, hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) return e;
-            if ((uint64_t)h_max * 2ull <= (n_bases / n_reads) * 3ull) { *declined = true; return hipSuccess; }
-        }
-    }
-    const uint64_t max_seg = n_reads + n_bases / S + 1;
-    if (max_seg > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const uint64_t n_ck = (n_bases >> 5) + 2;
-    size_t temp_bytes = 0;
-    e = hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, (uint64_t *)nullptr, (uint64_t *)nullptr, (int)(n_reads + 1), stream);
-    if (e != hipSuccess) return e;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes ? bytes : 8); return o; };
-    const size_t o_nof = take((n_reads + 1) * 8), o_first = take((n_reads + 1) * 8), o_temp = take(temp_bytes),
-                 o_in = take(max_seg * 8), o_out = take(max_seg * 8), o_len = take(max_seg * 4), o_j = take(max_seg * 4),
-                 o_rem = take(max_seg * 4), o_fin = take(max_seg * sizeof(ZSegFin)), o_tot = take(max_seg * sizeof(SegTot)),
-                 o_join = take(max_seg * sizeof(SegJoin)), o_chain = take(max_seg), o_fail = take(n_reads),
-                 o_ck = take(n_ck * sizeof(ZSegCkpt)), o_go = take(32);
-    if (ws->cap < off) {
-        if (ws->buf) (void)hipFree(ws->buf);
-        ws->buf = nullptr;
-        ws->cap = 0;
-        const size_t want = off + (off >> 3);
-        e = hipMalloc(&ws->buf, want);
-        if (e != hipSuccess) return e;
-        ws->cap = want;
-    }
-    uint8_t *B = static_cast<uint8_t *>(ws->buf);
-    uint64_t *n_of = reinterpret_cast<uint64_t *>(B + o_nof), *first = reinterpret_cast<uint64_t *>(B + o_first);
-    uint64_t *seg_in = reinterpret_cast<uint64_t *>(B + o_in), *seg_out = reinterpret_cast<uint64_t *>(B + o_out);
-    uint32_t *seg_l = reinterpret_cast<uint32_t *>(B + o_len), *seg_j = reinterpret_cast<uint32_t *>(B + o_j),
-             *seg_rem = reinterpret_cast<uint32_t *>(B + o_rem);
-    SegJoin *join = reinterpret_cast<SegJoin *>(B + o_join);
-    uint8_t *on_chain = B + o_chain, *read_fail = B + o_fail;
-    ZSegArgs seg;
-    seg.seg_in = seg_in; seg.seg_out = seg_out; seg.seg_len = seg_l; seg.n_seg = first + n_reads;
-    seg.ckpt = reinterpret_cast<ZSegCkpt *>(B + o_ck);
-    seg.fin = reinterpret_cast<ZSegFin *>(B + o_fin);
-    seg.tot = reinterpret_cast<SegTot *>(B + o_tot);
-    seg.read_fail = read_fail;
-    uint32_t *go = reinterpret_cast<uint32_t *>(B + o_go);               // go | probes | probes in step
+                                       hipStream_t stream, SegWorkspace *ws, int ragged_hint, bool *declined, int *verdict, LaunchInfo *info) {
+    const SegShape shape = {kSegWavesZml, kSegRaggedWavesZml, sizeof(ZSegFin), sizeof(ZSegCkpt), 0, {0, 0}, false};
+    SegPrelude pre;
+    hipError_t e = seg_prelude(shape, d_offsets, n_reads, n_bases, cfg, stream, ws, ragged_hint, declined, verdict, [&](uint32_t *tally) {
+        hipLaunchKernelGGL(zml_probe_kernel<MODE>, dim3(16), dim3(64), 0, stream, ix, d_bases, d_offsets, n_reads, 32u, 384u, tally);
+    }, &pre);
+    if (e != hipSuccess || *declined) return e;
+    const uint64_t max_seg = pre.max_seg;
     const unsigned bt256 = 256;
-    e = hipMemsetAsync(go, 0, 32, stream);
+    ZmlLaunch L;
+    L.stream = stream; L.ix = ix; L.bases = d_bases; L.offs = d_offsets; L.out = d_out; L.err = d_err; L.stats = d_stats;
+    pre.fill(L.seg_args, n_reads);
+    L.mode = MODE; L.idx32 = ix.idx32 ? 1 : 0;
+    // K1, the dominant kernel
+    L.flat = zml_seg_k1_flat(ix.r, n_bases) ? 1 : 0;
+    const unsigned k1_bt = L.flat ? 64 : bt256;
+    L.seg = 1; L.n = max_seg; L.grid = dim3((unsigned)((max_seg + k1_bt - 1) / k1_bt)); L.block = dim3(k1_bt);
+    e = zml_dispatch(L, info);
     if (e != hipSuccess) return e;
-    if (probe)
-        hipLaunchKernelGGL(zml_probe_kernel<MODE>, dim3(16), dim3(64), 0, stream, ix, d_bases, d_offsets, n_reads, 32u, 384u, go + 1);
-    hipLaunchKernelGGL(seg_decide_kernel, dim3(1), dim3(1), 0, stream, go + 1, (uint32_t)probe, go, d_offsets, n_reads, n_bases);
-    if (probe) {
-        uint32_t h_go = 0;
-        e = hipMemcpyAsync(&h_go, go, 4, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return e;
-        if (verdict) *verdict = h_go ? 1 : 0;
-        if (!h_go) { *declined = true; return hipSuccess; }
-    }
-    // (go == 0 -- a probe nobody read back cannot say so here, but offsets that break the contract can: seg_decide_kernel --
-    // leaves the plan without segments: K1 / K2 idle, seg_finalize_kernel hands every read to K3)
-    hipLaunchKernelGGL(seg_count_kernel, dim3((unsigned)((n_reads + 1 + bt256 - 1) / bt256)), dim3(bt256), 0, stream, d_offsets,
-                       n_reads, S, n_of, go);
-    e = hipcub::DeviceScan::ExclusiveSum(B + o_temp, temp_bytes, n_of, first, (int)(n_reads + 1), stream);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(seg_fill_kernel, dim3((unsigned)((n_reads + bt256 - 1) / bt256)), dim3(bt256), 0, stream, d_offsets,
-                       n_reads, S, first, seg_in, seg_out, seg_l, seg_j, seg_rem);
-    const uint32_t *d_order = nullptr;
-    // K1: the lane state machine where the plain query would use it (tables up to 3 GB), else the base-synchronous kernel
-    {   // (movi_launch_log: the plan's K1 and K3 kernels by name, like the walk kernel's)
-        char nm[96];
-        if (ix.r <= (3ull << 30) / 8 && ix.r >= 8 && n_bases >= 16) snprintf(nm, sizeof(nm), "zml_kernel_flat<%d, %s, 1, 0, 0, 0>", MODE, ix.idx32 ? "unsigned int" : "unsigned long");
-        else snprintf(nm, sizeof(nm), "zml_kernel<%d, 1>", MODE);
-        note_walk_launch(nm);
-        snprintf(nm, sizeof(nm), "zml_kernel<%d, 2>", MODE);
-        note_walk_launch(nm);
-    }
-    if (ix.r <= (3ull << 30) / 8 && ix.r >= 8 && n_bases >= 16) {
-        if (ix.idx32)
-            hipLaunchKernelGGL((zml_kernel_flat<MODE, uint32_t, 1>), dim3((unsigned)((max_seg + 63) / 64)), dim3(64), 0, stream, ix,
-                               d_bases, d_offsets, max_seg, d_out, d_err, d_stats, d_order, seg, nullptr, nullptr);
-        else
-            hipLaunchKernelGGL((zml_kernel_flat<MODE, uint64_t, 1>), dim3((unsigned)((max_seg + 63) / 64)), dim3(64), 0, stream, ix,
-                               d_bases, d_offsets, max_seg, d_out, d_err, d_stats, d_order, seg, nullptr, nullptr);
-    } else {
-        hipLaunchKernelGGL((zml_kernel<MODE, 1>), dim3((unsigned)((max_seg + bt256 - 1) / bt256)), dim3(bt256), 0, stream, ix, d_bases,
-                           d_offsets, max_seg, d_out, d_err, d_stats, d_order, seg);
+    if (info) {
+        info->variant = L.flat; info->block_threads = (int)k1_bt; info->waves_per_cu = 0; info->segmented = 1; info->staged = 0; info->ahead = 0;
+        info->idx64 = ix.idx32 ? 0 : 1;
     }
     const uint32_t max_over = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (uint64_t)cfg.seg_len * (uint64_t)kSegOverrun);
-    hipLaunchKernelGGL((zml_stitch_kernel<MODE, 0>), dim3((unsigned)((max_seg + 63) / 64)), dim3(64), 0, stream, ix, d_bases, seg,
-                       seg_j, seg_rem, max_over, on_chain, d_out, join);
-    hipLaunchKernelGGL(seg_finalize_kernel, dim3((unsigned)((n_reads + bt256 - 1) / bt256)), dim3(bt256), 0, stream, go, first, n_reads,
-                       seg.tot, join, seg_l, seg_rem, on_chain, read_fail, d_err, d_stats);
-    hipLaunchKernelGGL((zml_stitch_kernel<MODE, 1>), dim3((unsigned)((max_seg + 63) / 64)), dim3(64), 0, stream, ix, d_bases, seg,
-                       seg_j, seg_rem, max_over, on_chain, d_out, join);
-    hipLaunchKernelGGL((zml_kernel<MODE, 2>), dim3((unsigned)((n_reads + bt256 - 1) / bt256)), dim3(bt256), 0, stream, ix, d_bases,
-                       d_offsets, n_reads, d_out, d_err, d_stats, d_order, seg);
-    return hipGetLastError();
+    hipLaunchKernelGGL((zml_stitch_kernel<MODE, 0>), dim3((unsigned)((max_seg + 63) / 64)), dim3(64), 0, stream, ix, d_bases, L.seg_args,
+                       pre.seg_j, pre.seg_rem, max_over, pre.on_chain, d_out, pre.join);
+    hipLaunchKernelGGL(seg_finalize_kernel, dim3((unsigned)((n_reads + bt256 - 1) / bt256)), dim3(bt256), 0, stream, pre.go, pre.first, n_reads,
+                       pre.tot, pre.join, pre.seg_l, pre.seg_rem, pre.on_chain, pre.read_fail, d_err, d_stats);
+    hipLaunchKernelGGL((zml_stitch_kernel<MODE, 1>), dim3((unsigned)((max_seg + 63) / 64)), dim3(64), 0, stream, ix, d_bases, L.seg_args,
+                       pre.seg_j, pre.seg_rem, max_over, pre.on_chain, d_out, pre.join);
+    L.flat = 0; L.seg = 2; L.n = n_reads; L.grid = dim3((unsigned)((n_reads + bt256 - 1) / bt256)); L.block = dim3(bt256);   // K3
+    return zml_dispatch(L, nullptr);
 }
 
-static hipError_t launch_count_flat(int mode, const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
-                                    uint64_t *d_matched, uint64_t *d_count, uint8_t *d_err, DevStats *d_stats, const uint32_t *d_order,
-                                    const LaunchCfg &cfg, hipStream_t stream, LaunchInfo *info, bool pair) {
-    const uint64_t blocks = (n_reads + 63) / 64;
+// The count query (plan_count): the lane state machine (zml_kernel_flat<..., CNT = 1>) wherever it can run, else count_kernel_v0.
+hipError_t launch_count(int mode, const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets,
+                        uint64_t n_reads, uint64_t *d_matched, uint64_t *d_count, uint8_t *d_err,
+                        DevStats *d_stats, const uint32_t *d_order, const LaunchCfg &cfg, hipStream_t stream,
+                        LaunchInfo *info, uint64_t n_bases) {
+    if (n_reads == 0) return hipSuccess;
+    const ZmlPlan P = plan_count(facts(ix), cfg, mode, n_reads, n_bases);
+    if (!P.valid) return hipErrorInvalidValue;
+    const uint64_t blocks = (n_reads + P.bt - 1) / P.bt;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)blocks), block(64);
-    const int wpc = cfg.waves_per_cu > 0 ? cfg.waves_per_cu : 0;     // "waves_per_cu": occupancy cap by LDS padding (<= 64 KiB here), as launch_zml
-    size_t dyn_lds = 0;
-    if (wpc > 0) {
-        const int bpc = wpc < 3 ? 3 : wpc;
-        if (bpc < 32) dyn_lds = ((163840u / (unsigned)bpc) & ~1023u) - 1024u;
-    }
-    // reads staged through LDS (round 6; blocks of one wavefront): the cap's padding, or kZmlStageBytes of their own (16 wavefronts per CU)
-    DevIndex ixl = ix;
-    if (cfg.stage_reads != 0) {
-        if (dyn_lds < kZmlStageBytes) dyn_lds = kZmlStageBytes;
-        ixl.stage_lds = (uint32_t)std::min<size_t>(1024, (dyn_lds / 64) & ~(size_t)15);
-    }
-    // ("zml_ahead" 1, round 6: the search on the look-ahead rows where the handle holds them -- a base both of whose LF moves land without a
-    // fast-forward is complete without the target rows; measured: profiles/r06_zml_count.txt)
-    const bool ahead = cfg.zml_ahead != 0 && mode == 6 && ix.rows2 != nullptr && !pair;
-    {
-        char nm[96];
-        snprintf(nm, sizeof(nm), "zml_kernel_flat<%d, %s, 0, %d, %d, 1>", mode, ix.idx32 ? "unsigned int" : "unsigned long", ahead ? 1 : 0, pair ? 1 : 0);
-        note_walk_launch(nm);
-    }
+    ZmlLaunch L;
+    L.grid = dim3((unsigned)blocks); L.block = dim3((unsigned)P.bt); L.dyn_lds = P.dyn_lds; L.stream = stream;
+    L.ix = ix; L.bases = d_bases; L.offs = d_offsets; L.n = n_reads; L.err = d_err; L.stats = d_stats; L.order = d_order;
+    L.matched = d_matched; L.count = d_count;
+    if (P.stage_lds != 0u) L.ix.stage_lds = P.stage_lds;
+    L.mode = mode; L.flat = P.v; L.idx32 = ix.idx32 ? 1 : 0; L.ahead = P.ahead ? 1 : 0; L.pair = P.pair ? 1 : 0; L.cnt = 1;
+    const hipError_t e = zml_dispatch(L, info);
     if (info) {
-        snprintf(info->kernel, sizeof(info->kernel), "zml_kernel_flat<%d, %s, 0, %d, %d, 1>", mode, ix.idx32 ? "unsigned int" : "unsigned long", ahead ? 1 : 0, pair ? 1 : 0);
-        info->variant = 1; info->block_threads = 64; info->waves_per_cu = wpc; info->segmented = 0; info->idx64 = ix.idx32 ? 0 : 1; info->staged = (int)ixl.stage_lds;
-        info->ahead = ahead ? 1 : 0;
+        info->variant = P.v; info->block_threads = P.bt; info->waves_per_cu = P.wpc; info->segmented = 0;
+        info->idx64 = (P.v == 0 || !ix.idx32) ? 1 : 0;   // (count_kernel_v0 has 64-bit row indexes only)
+        info->staged = P.v == 0 ? 0 : (int)L.ix.stage_lds;
+        info->ahead = P.ahead ? 1 : 0;
     }
-    if (ahead) {
-        if (ix.idx32)
-            hipLaunchKernelGGL((zml_kernel_flat<6, uint32_t, 0, 1, 0, 1>), grid, block, dyn_lds, stream, ixl, d_bases, d_offsets, n_reads,
-                               (uint16_t *)nullptr, d_err, d_stats, d_order, ZSegArgs(), d_matched, d_count);
-        else
-            hipLaunchKernelGGL((zml_kernel_flat<6, uint64_t, 0, 1, 0, 1>), grid, block, dyn_lds, stream, ixl, d_bases, d_offsets, n_reads,
-                               (uint16_t *)nullptr, d_err, d_stats, d_order, ZSegArgs(), d_matched, d_count);
-        return hipGetLastError();
-    }
-#define MOVI_LAUNCH_CNT(M, T, P)                                                                                          \
-    hipLaunchKernelGGL((zml_kernel_flat<M, T, 0, 0, P, 1>), grid, block, dyn_lds, stream, ixl, d_bases, d_offsets, n_reads, \
-                       (uint16_t *)nullptr, d_err, d_stats, d_order, ZSegArgs(), d_matched, d_count)
-#define MOVI_LAUNCH_CNT_M(M)                                                                                              \
-    do {                                                                                                                  \
-        if (ix.idx32) { if (pair) MOVI_LAUNCH_CNT(M, uint32_t, 1); else MOVI_LAUNCH_CNT(M, uint32_t, 0); }                \
-        else { if (pair) MOVI_LAUNCH_CNT(M, uint64_t, 1); else MOVI_LAUNCH_CNT(M, uint64_t, 0); }                         \
-    } while (0)
-    if (mode == 6) MOVI_LAUNCH_CNT_M(6);
-    else if (mode == 3) MOVI_LAUNCH_CNT_M(3);
-    else return hipErrorInvalidValue;
-#undef MOVI_LAUNCH_CNT_M
-#undef MOVI_LAUNCH_CNT
-    return hipGetLastError();
+    return e;
 }
 
 hipError_t launch_zml(int mode, const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets,
@@ -2464,107 +2265,28 @@ hipError_t launch_zml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
                       const uint32_t *d_order, const LaunchCfg &cfg, hipStream_t stream, SegWorkspace *seg_ws,
                       int ragged_hint, int *seg_verdict, LaunchInfo *info) {
     if (n_reads == 0) return hipSuccess;
-    if (seg_ws && cfg.seg_len >= 32 && !d_order && cfg.zml_variant < 0 && cfg.block_threads == 0 && cfg.waves_per_cu <= 0 &&
-        n_bases / n_reads >= 2ull * (uint64_t)cfg.seg_len && n_reads + n_bases / (uint64_t)cfg.seg_len < 0x7FFFFFF0ull &&
-        (mode == 6 || mode == 3)) {
+    if (zml_seg_eligible(cfg, mode, n_reads, n_bases, seg_ws != nullptr, d_order != nullptr)) {
         bool declined = false;
         const hipError_t es = mode == 6 ? launch_zml_segmented<6>(ix, d_bases, d_offsets, n_reads, n_bases, d_out, d_err, d_stats, cfg,
-                                                                  stream, seg_ws, ragged_hint, &declined, seg_verdict)
+                                                                  stream, seg_ws, ragged_hint, &declined, seg_verdict, info)
                                         : launch_zml_segmented<3>(ix, d_bases, d_offsets, n_reads, n_bases, d_out, d_err, d_stats, cfg,
-                                                                  stream, seg_ws, ragged_hint, &declined, seg_verdict);
-        if (es == hipSuccess && !declined && info) {
-            const bool sm = ix.r <= (3ull << 30) / 8 && ix.r >= 8 && n_bases >= 16;
-            if (sm) snprintf(info->kernel, sizeof(info->kernel), "zml_kernel_flat<%d, %s, 1, 0, 0, 0>", mode, ix.idx32 ? "unsigned int" : "unsigned long");
-            else snprintf(info->kernel, sizeof(info->kernel), "zml_kernel<%d, 1>", mode);
-            info->variant = sm ? 1 : 0; info->block_threads = sm ? 64 : 256; info->waves_per_cu = 0; info->segmented = 1; info->staged = 0; info->ahead = 0;
-            info->idx64 = ix.idx32 ? 0 : 1;
-        }
+                                                                  stream, seg_ws, ragged_hint, &declined, seg_verdict, info);
         if (es != hipSuccess || !declined) return es;
     }
-    // 0 = base-synchronous kernel, 1 = lane state machine.  Measured (profiles/r02_zml_state_machine.txt), Gbases/s,
-    // kernel 0 / 1: 100 k x 10 kbp 12.1 / 19.1 (pangenome), 12.2 / 18.2 (random 10 M rows); 1 M x 150 bp 36.8 / 39.2 and
-    // 34.1 / 36.8; random tables of 120 M rows 24.6 / 28.3, 250 M (2 GB) 23.4 / 26.6, 500 M (4 GB) 21.3 / 16.6, 1 B (8 GB)
-    // 17.0 / 13.8.  The state machine fetches two 4-row windows (four 16-byte loads, i.e. ~8 TLB lookups) per iteration:
-    // beyond the ~1.7 GB reach of a CU's TLB that costs more than the base-synchronous kernel's dependent trips, so auto
-    // picks it for tables up to 3 GB.  (Its first form walked the windows with eight sequential hops and was no faster
-    // than kernel 0 anywhere: 12.4 on the long reads, 32.6 on the short ones; the closed-form window walk made it.)
-    // Round 4: with the two windows fetched by PAIRS of lanes (zml_kernel_flat<..., PSH = 1>: half the translation requests) the
-    // state machine serves the tables beyond 3 GB too: 1 B rows 16.8 (kernel 0) / 13.9 (kernel 1) -> 25.0 Gbases/s; below 2 GB the
-    // exchange costs more than it gives (c2: 38.2 -> 36.6), so there the lanes keep their own loads (profiles/r04_zml_ahead.txt;
-    // "pair_loads" 0: the old policy, 1: pairs everywhere).
-    // (`ahead` and `pair` are settled BEFORE the kernel is picked: a caller who asks for the look-ahead rows forgoes the pairs, and
-    // beyond 3 GB the unpaired state machine is the slowest of the three -- 13.9 against kernel 0's 16.8 Gbases/s at 1 B rows)
-    int v = cfg.zml_variant;
-    const bool big = ix.r * 8ull >= kPairLoadBytes;
-    const bool want_ahead = cfg.zml_ahead != 0 && mode == 6 && ix.rows2 != nullptr;
-    const bool can_pair = !want_ahead && (cfg.pair_loads > 0 || (cfg.pair_loads < 0 && big));
-    if (v < 0) v = (ix.r <= (3ull << 30) / 8 || can_pair) ? 1 : 0;
-    if (v == 1 && (ix.r < 8 || n_bases < 16)) v = 0;     // the clamped windows need >= 4 rows, the 16-base fetches 16 bytes
-    const int bt = cfg.block_threads > 0 ? cfg.block_threads : (v == 1 ? 64 : 256);
-    const uint64_t blocks = (n_reads + bt - 1) / bt;
-    if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    dim3 grid((unsigned)blocks), block((unsigned)bt);
-    // The state machine on the look-ahead rows (round 4; "zml_ahead" 1, where the copy exists): a base both of whose LF moves
-    // land without a fast-forward is complete without the target rows.  Lane iterations per base on c2 1.45 -> 0.98 -- and 37.3
-    // instead of 38.2 Gbases/s (eight 16-byte loads per iteration instead of four, SIMT 0.72 -> 0.64; random 10 M-row table 35.9 ->
-    // 35.0: profiles/r04_zml_ahead.txt), so it is an option, not the default.
-    const bool ahead = want_ahead && v == 1;
-    const bool pair = v == 1 && can_pair;
-    {
-        char nm[96];
-        if (v == 1) snprintf(nm, sizeof(nm), "zml_kernel_flat<%d, %s, 0, %d, %d, 0>", mode, ix.idx32 ? "unsigned int" : "unsigned long", ahead ? 1 : 0, pair ? 1 : 0);
-        else snprintf(nm, sizeof(nm), "zml_kernel<%d, 0>", mode);
-        note_walk_launch(nm);
-    }
+    const ZmlPlan P = plan_zml(facts(ix), cfg, mode, n_bases);
+    const uint64_t blocks = (n_reads + P.bt - 1) / P.bt;
+    if (blocks > 0x7FFFFFFFull || !P.valid) return hipErrorInvalidValue;
+    ZmlLaunch L;
+    L.grid = dim3((unsigned)blocks); L.block = dim3((unsigned)P.bt); L.dyn_lds = P.dyn_lds; L.stream = stream;
+    L.ix = ix; L.bases = d_bases; L.offs = d_offsets; L.n = n_reads; L.out = d_out; L.err = d_err; L.stats = d_stats; L.order = d_order;
+    if (P.stage_lds != 0u) L.ix.stage_lds = P.stage_lds;
+    L.mode = mode; L.flat = P.v; L.idx32 = ix.idx32 ? 1 : 0; L.ahead = P.ahead ? 1 : 0; L.pair = P.pair ? 1 : 0;
+    const hipError_t e = zml_dispatch(L, info);
     if (info) {
-        if (v == 1) snprintf(info->kernel, sizeof(info->kernel), "zml_kernel_flat<%d, %s, 0, %d, %d, 0>", mode, ix.idx32 ? "unsigned int" : "unsigned long",
-                             ahead ? 1 : 0, pair ? 1 : 0);
-        else snprintf(info->kernel, sizeof(info->kernel), "zml_kernel<%d, 0>", mode);
-        info->variant = v; info->block_threads = bt; info->waves_per_cu = cfg.waves_per_cu > 0 ? cfg.waves_per_cu : 0; info->staged = 0; info->ahead = ahead ? 1 : 0;
+        info->variant = P.v; info->block_threads = P.bt; info->waves_per_cu = P.wpc; info->staged = 0; info->ahead = P.ahead ? 1 : 0;
         info->segmented = 0; info->idx64 = ix.idx32 ? 0 : 1;
     }
-    size_t dyn_lds = 0;                                  // occupancy cap by LDS padding, as in launch_pml (<= 64 KiB here)
-    if (cfg.waves_per_cu > 0) {
-        int bpc = cfg.waves_per_cu / (bt / 64);
-        if (bpc < 3) bpc = 3;
-        if (bpc < 32) dyn_lds = ((163840u / (unsigned)bpc) & ~1023u) - 1024u;
-    }
-    DevIndex ixl = ix;                                   // reads staged through LDS (round 6): the state machine in blocks of one wavefront
-    if (v == 1 && bt == 64 && cfg.stage_reads != 0) {
-        if (dyn_lds < kZmlStageBytes) dyn_lds = kZmlStageBytes;
-        ixl.stage_lds = (uint32_t)std::min<size_t>(1024, (dyn_lds / 64) & ~(size_t)15);
-    }
-#define MOVI_LAUNCH_ZML(M)                                                                                     \
-    do {                                                                                                       \
-        if (v == 0)                                                                                            \
-            hipLaunchKernelGGL(zml_kernel<M>, grid, block, dyn_lds, stream, ixl, d_bases, d_offsets, n_reads,   \
-                               d_out, d_err, d_stats, d_order, ZSegArgs());                                    \
-        else if (pair && ix.idx32)                                                                             \
-            hipLaunchKernelGGL((zml_kernel_flat<M, uint32_t, 0, 0, 1>), grid, block, dyn_lds, stream, ixl,     \
-                               d_bases, d_offsets, n_reads, d_out, d_err, d_stats, d_order, ZSegArgs(), nullptr, nullptr); \
-        else if (pair)                                                                                         \
-            hipLaunchKernelGGL((zml_kernel_flat<M, uint64_t, 0, 0, 1>), grid, block, dyn_lds, stream, ixl,     \
-                               d_bases, d_offsets, n_reads, d_out, d_err, d_stats, d_order, ZSegArgs(), nullptr, nullptr); \
-        else if (ix.idx32)                                                                                     \
-            hipLaunchKernelGGL((zml_kernel_flat<M, uint32_t>), grid, block, dyn_lds, stream, ixl, d_bases,      \
-                               d_offsets, n_reads, d_out, d_err, d_stats, d_order, ZSegArgs(), nullptr, nullptr); \
-        else                                                                                                   \
-            hipLaunchKernelGGL((zml_kernel_flat<M, uint64_t>), grid, block, dyn_lds, stream, ixl, d_bases,      \
-                               d_offsets, n_reads, d_out, d_err, d_stats, d_order, ZSegArgs(), nullptr, nullptr); \
-    } while (0)
-    // resident layouts: 6 = regular-thresholds rows, 3 = regular rows (threshold-less types: 12-bit lengths)
-    if (mode == 6 && ahead) {
-        if (ix.idx32)
-            hipLaunchKernelGGL((zml_kernel_flat<6, uint32_t, 0, 1>), grid, block, dyn_lds, stream, ixl, d_bases, d_offsets, n_reads, d_out,
-                               d_err, d_stats, d_order, ZSegArgs(), nullptr, nullptr);
-        else
-            hipLaunchKernelGGL((zml_kernel_flat<6, uint64_t, 0, 1>), grid, block, dyn_lds, stream, ixl, d_bases, d_offsets, n_reads, d_out,
-                               d_err, d_stats, d_order, ZSegArgs(), nullptr, nullptr);
-    } else if (mode == 6) MOVI_LAUNCH_ZML(6);
-    else if (mode == 3) MOVI_LAUNCH_ZML(3);
-    else return hipErrorInvalidValue;
-#undef MOVI_LAUNCH_ZML
-    return hipGetLastError();
+    return e;
 }
 
 // ------------------------------------------------------------ classification bins

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "movi_launch_policy.hpp"   // LaunchCfg, the kCap* / k*ReadLen / k*Bytes constants, the launch plans
+
 namespace movi {
 
 constexpr int kPrefixShift = 5;   // one BWT-position checkpoint every 32 rows (count path)
@@ -122,42 +124,7 @@ struct DevStats {
     unsigned long long pad_;
 };
 
-constexpr int kCountCapWaves = 16;   // the count kernel's cap on cache-resident tables (launch_count)
-constexpr int kCapWaves = 7;   // resident wavefronts per CU of the lane state machine on big batches (round 2: 9, optimum 8-10; round 3, with the reads staged in LDS and the top-of-walk table: 6-8, profiles/r03_occupancy_sweep.txt)
-constexpr int kCapWavesAhead = 9;    // ... when the walk runs on the look-ahead rows: fewer lines per base, more walks in flight pay (profiles/r03_ahead_rows_ab.txt)
-constexpr int kCapWavesDeep = 13;    // ... on the deep rows: fewer lines per base again and more instructions per iteration (c2, cap 9 / 11 / 13 / 14 / 16: vector out 71.8 / 75.7 / 78.4 / 78.7 / 77.9, reset masks out 87.3 / 89.9 / 89.4 / 89.5 / 87.8 Gbases/s: profiles/r06_deep_rows.txt)
-constexpr uint32_t kOutRingBytes = 4096;          // pml_kernel_flatp<..., RING = 1>: the ring in the block's dynamic LDS its PMLs leave through (32 per lane)
-constexpr uint64_t kOutRingReadLen = 1024;        // ... on by itself for batches whose mean read length is at least this (launch_pml)
 constexpr uint32_t kTallySlots = 512;             // pairs of u64 counters a builder's tally is spread over (d_tally: 2 * kTallySlots u64, zeroed)
-constexpr size_t kZmlStageBytes = 10240;          // zml_kernel_flat: dynamic LDS per one-wavefront block for its staged reads (160 bases per lane; 16 wavefronts per CU)
-constexpr uint64_t kDeepReadLen = 1024;           // launch_pml: batches whose mean read length is below this walk on the deep rows (where the handle holds them)
-constexpr uint64_t kPairLoadBytes = 2ull << 30;   // walked tables of this size and more: pair-shared gathers (launch_pml)
-
-struct LaunchCfg {
-    int block_threads = 0;   // 0 = auto: 64 for the PML and count kernels and the ZML state machine (finest dispatch grain), 256 for the base-synchronous ZML kernel
-    // -1 auto; 0 first kernel (plain I/O; serves --logs), 1 base-synchronous packed I/O, 14 = the lane state machine over
-    // row windows, software-pipelined (what auto picks).  (7 / 10 / 13 -- the row-at-a-time state machine, the hop-by-hop
-    // advance, lane refill -- were A/B variants that never earned a default; removed in round 5.)
-    int pml_variant = -1;
-    int zml_variant = -1;  // -1 auto; 0 base-synchronous kernel, 1 lane state machine
-    int count_variant = -1; // -1 auto (launch_count); 0 count_kernel_v0 (base-synchronous), 1 the lane state machine (zml_kernel_flat<..., CNT = 1>)
-    int num_cus = 256;
-    int waves_per_cu = 0;  // 0 = auto (the state machine on big batches: kCapWaves; else no cap); else cap resident waves per CU by padding the block's LDS allocation
-    int seg_len = 2048;    // PML: batches whose mean read length is >= 2 x seg_len are walked segment-parallel (0 = never) ...
-    int seg_probe = 1;     // ... if a probe of the batch finds that walks started mid-read fall into step quickly (0 = always: tests;
-                           // 2 = no probe and no read-back at all, the caller's seg_verdict decides: the launch stays asynchronous)
-    int seg_verdict = 0;   // seg_probe == 2: 1 = cut eligible batches, 0 = one lane per read
-    int stage_reads = 1;   // every lane keeps the next stretch of its read in the block's LDS (rolling for long reads); 0 = off: A/B
-    int inwin = 1;         // repositions inside the window resolved in the same iteration (0 = off: A/B)
-    int out_ring = -1;     // PMLs out through a ring in LDS: -1 = batches of long reads (launch_pml), 0 / 1 = never / wherever it fits (A/B)
-    int classify_fused = -1; // movi_pml_classify_*: -1 auto, 1 = vector + bins fused into the walk, 0 = the walk, then classify_kernel over the vectors
-    int pair_loads = -1;   // the lanes of a pair fetch their row windows together (pml_kernel_flatp<..., PSH = 1>): -1 auto (tables of 2 GB and more), 0 never, 1 always
-    int hints = 1;         // 1: mismatches whose scan leaves the row window jump by the reposition hints of the look-ahead rows (DevIndex::hints); 0 = off: A/B
-    int zml_ahead = 0;     // 1: zml_kernel_flat<6, T, 0, 1> on the look-ahead rows where they exist (a third fewer iterations, no faster: opt-in)
-    int fused_expand = 1;  // 1: a mask walk whose caller wants the vector expands its wavefronts' reads itself (DevIndex::expand_out); 0 = pml_expand_* kernels behind the walk: A/B
-    int kmer_lookahead = -1; // kmer_kernel: -1 = hinted look-ahead with a split chosen by k and the text's length (kmer_look_step), 0 = every end searched from its own base, n >= 2 = split k / n (A/B)
-    int deep = -1;         // the PML walk on the deep rows (DevIndex::rows3) where the handle holds them: -1 = batches of short reads (mean length < kDeepReadLen), 0 never, 1 always
-};
 
 // What a launch_* call actually launched (movi_last_launch): the policy lives in the launchers, so they say what they picked.
 struct LaunchInfo {
@@ -224,10 +191,8 @@ struct ZSegArgs {
     const uint8_t *read_fail = nullptr;
 };
 
-// One launch of the walk kernel (pml_kernel_flatp, movi_walk.hpp): its arguments plus the run-time choices that pick the
-// instantiation.  The launchers (launch_pml, launch_pml_segmented) fill it; the movi_walk*_u32 / _u64 translation units turn
-// it into a launch and name the kernel (every template argument) in `info`.
-struct WalkLaunch {
+// What every launch of a query kernel over a batch carries.
+struct BatchLaunch {
     dim3 grid, block;
     size_t dyn_lds = 0;
     hipStream_t stream = nullptr;
@@ -239,10 +204,24 @@ struct WalkLaunch {
     uint8_t *err = nullptr;
     DevStats *stats = nullptr;
     const uint32_t *order = nullptr;
+};
+// One launch of the walk kernel (pml_kernel_flatp, movi_walk.hpp): its arguments plus the run-time choices that pick the
+// instantiation.  The launchers (launch_pml, launch_pml_segmented) fill it; the movi_walk*_u32 / _u64 translation units turn
+// it into a launch and name the kernel (every template argument) in `info`.
+struct WalkLaunch : BatchLaunch {
     ClsArgs cls;
     SegArgs seg;
     int cls_mode = 0;                     // 0 = PML vector, 1 = vector + classification bins, 2 = bins only
     int sep = 0, stg = 0, ahd = 0, psh = 0, ring = 0;   // separators index / reads staged through LDS / look-ahead rows / pair-shared gathers / PMLs out through the LDS ring (1) or as reset masks (2: `out` holds 32-bit words)
+};
+// One launch of a ZML / count kernel, likewise.  launch_zml, launch_zml_segmented and launch_count fill it; zml_dispatch (movi_kernels.hip)
+// turns it into a launch and names the kernel in `info`.
+struct ZmlLaunch : BatchLaunch {
+    ZSegArgs seg_args;
+    uint64_t *matched = nullptr, *count = nullptr;   // the count query's results (`out` is the ZML parse's)
+    int mode = 6;                         // resident layout: 6 = regular-thresholds rows, 3 = regular rows (threshold-less types: 12-bit lengths)
+    int flat = 0;                         // 1 = the lane state machine (zml_kernel_flat), 0 = base-synchronous (zml_kernel; cnt: count_kernel_v0)
+    int idx32 = 0, seg = 0, ahead = 0, pair = 0, cnt = 0;   // 32-bit row indexes / 1 = segments (K1), 2 = re-walked reads (K3) / look-ahead rows / pair-shared gathers / the count query
 };
 // Diagnostic: when switched on (movi_launch_log), every launch of the walk kernel notes its name -- the K1 / K3 launches of the
 // segment plan included, which LaunchInfo (the dominant kernel only) does not show.

@@ -129,6 +129,7 @@ def test_every_built_zml_and_count_kernel_is_reachable_and_equals_the_oracle(bui
             gpu.set_option("seg_probe", 0)
             z, st = gpu.query_zml_packed(b2, o2)
             assert (z == cpu.zml_batch(b2, o2, threads=2)).all(), kmode
+            assert gpu.last_launch()["kernel"] == "zml_kernel<%d, 1>" % kmode and gpu.last_launch()["segmented"] == 1, gpu.last_launch()
             seen |= read_log()
         gpu.close()
         cpu.close()
