@@ -577,7 +577,8 @@ int movi_sa_entries_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_
  * first-appearance order runs on the host.  Offsets must be strictly increasing and above 0 (MOVI_ERR_ARG: the reference's
  * one-step-per-position rule and a search agree only then); at most 65535 distinct taxa.  MOVI_ERR_INVARIANT if the walks do not visit
  * every BWT position exactly once, or a run is left without a document: never a wrong table.  A table of 2^31 - 1 rows or more is
- * MOVI_ERR_ARG, as for the sampled suffix array.  Replaces attached tables.  Waits.
+ * MOVI_ERR_ARG, as for the sampled suffix array.  Replaces attached tables; once the arguments are accepted, a build that fails --
+ * in movi_ssa_build or in its own walks -- leaves none attached.  Waits.
  * movi_color_save / movi_color_load: DIR/doc_sets_flat.bin.  Loading checks the file's length against r and every run's set against
  * the table and num_species (MOVI_ERR_FORMAT); a missing file is MOVI_ERR_IO with the reference's message naming the path.
  * movi_color_get: the tables as held (any pointer may be NULL; a cap too small: MOVI_ERR_ARG); h_inds as u64; h_to_taxon_id is known

@@ -3056,9 +3056,9 @@ int movi_color_build(movi_index_t *ix, const uint64_t *doc_offsets, const uint32
     if (ix->desc.r + 1 > 0x7FFFFFFFull)
         return fail(MOVI_ERR_ARG, "the colour builder cannot run on a table of 2^31 - 1 rows or more yet (it walks from a sampled suffix array, whose "
                                   "locate rows need one 32-bit-indexed device scan)");
+    detach_color(ix);                                                    // (first: a build that fails leaves no tables attached, older ones included)
     if (!ix->sa_rate)                                                    // the text position of every BWT position comes from the samples
         if (int rc = movi_ssa_build(ix, 100, stream)) return rc;
-    detach_color(ix);
     uint64_t *d_keys = nullptr, n_keys = 0, key_cap = 0;
     uint32_t bad = 0;
     const hipError_t e = build_color_keys(ix->kmode, ix->dev, loc_args(ix), doc_offsets, ids.data(), (uint32_t)n_docs, ix->color_chunk_keys,

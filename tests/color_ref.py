@@ -10,7 +10,7 @@ suffix array of the text, the fields oracle/build_index.py's build_rows derives 
     (flat_colors u16, flat offset per run); flat_file(flat, inds) is doc_sets_flat.bin, read_flat_file its reader (:587-607).
   * score(f, oracle, read, flat, inds, num_species, min_len): process_char's scoring (src/read_processor.cpp:122-186, :237) over
     sa_ref.walk's states, whose PMLs are asserted against the oracle's; the set scored at a base is that of the row the LF step
-    lands on, before the base is compared and possibly repositions the walk.
+    lands on, before the base is compared and possibly repositions the walk.  Match lengths beyond 65535 are carried as they are.
   * mls_line(...): write_mls (src/read_processor.cpp:489-562) in float32 arithmetic."""
 import struct
 
@@ -91,22 +91,25 @@ def tables(f, SA, offsets, doc_ids=None):
     return flat, inds, len(to_taxon), to_taxon
 
 
-def score_states(states, flat, inds, num_species, min_len):
+def score_states(states, flat, inds, num_species, min_len, changes=None):
     """process_char over (the row the walk stands on after the LF step and BEFORE the base is compared -- the one whose set is scored --,
-    -, the PML after the base) per base: (best, second, colors_count, sum_ml mod 2^32, counters)."""
+    -, the match length after the base, unclamped) per base: (best, second, colors_count, sum_ml mod 2^32, counters).  `changes`: a
+    list that receives (base, member, old best, new best) whenever a document takes the lead from another one."""
     cnt = [0] * num_species
     best = second = NONE
     colors_count = total = 0
     ml = 0
-    for row, _, after in states:
+    for k, (row, _, after) in enumerate(states):
         if ml >= min_len:
             colors_count += 1
             at = int(inds[row])
             if at < len(flat):
-                for doc in (int(x) for x in flat[at + 1: at + 1 + int(flat[at])]):
+                for m, doc in enumerate(int(x) for x in flat[at + 1: at + 1 + int(flat[at])]):
                     cnt[doc] += 1
                     if doc != best:
                         if best == NONE or cnt[doc] > cnt[best]:
+                            if changes is not None and best != NONE:
+                                changes.append((k, m, best, doc))
                             second, best = best, doc
                         elif second == NONE or cnt[doc] > cnt[second]:
                             second = doc
@@ -115,14 +118,16 @@ def score_states(states, flat, inds, num_species, min_len):
     return best, second, colors_count, total & 0xFFFFFFFF, cnt
 
 
-def score(f, oracle, read, flat, inds, num_species, min_len, codes=None):
-    w = sa_ref.walk(f, read, codes)
-    assert [x[2] for x in w] == [int(v) for v in oracle.pml(read)], read
-    assert all(x[2] < 65535 for x in w)                         # (the walk's PML is the clamped one: the tests' reads stay far below)
+def score(f, oracle, read, flat, inds, num_species, min_len, codes=None, changes=None):
+    # the match length is carried unclamped (process.match_len is a uint64_t): into the min_len test and into sum_matching_lengths,
+    # a uint32_t that wraps (src/read_processor.cpp:123, :237); only the PML vector holds min(ml, 65535), and that is what is held
+    # to the oracle's
+    w = sa_ref.walk(f, read, codes, clamp=False)
+    assert [min(x[2], 65535) for x in w] == [int(v) for v in oracle.pml(read)], read[:80]
     # the scored row is where the LF step from the state after the base before lands (the read's first base: the last row), not where
     # a reposition of this base then takes the walk
     scored = [(f["r"] - 1 if k == 0 else sa_ref._lf(f, w[k - 1][0], w[k - 1][1])[0], None, w[k][2]) for k in range(len(w))]
-    return score_states(scored, flat, inds, num_species, min_len)
+    return score_states(scored, flat, inds, num_species, min_len, changes)
 
 
 def mls_line(rid, read_len, res, to_taxon, report_all=False, min_diff_frac=0.05, min_score_frac=0.0):

@@ -96,8 +96,9 @@ def code_table(f):
     return t
 
 
-def walk(f, read, codes=None):
-    """[(row, offset, PML)] per base of `read`, last base first."""
+def walk(f, read, codes=None, clamp=True):
+    """[(row, offset, PML)] per base of `read`, last base first.  clamp=False: the match length itself (process.match_len, a
+    uint64_t in the reference) in place of the u16 the PML vector holds -- what color_ref.score adds up and tests against min_len."""
     codes = codes or code_table(f)
     r, sep, end = f["r"], f["sep"], f["end_bwt_idx"]
     code, lens, thr_bits = f["code"], f["lens"], f["thr_bits"]
@@ -127,7 +128,7 @@ def walk(f, read, codes=None):
                 idx += step
                 assert 0 <= idx < r, "no run of the base in that direction"
             off = 0 if down else int(lens[idx]) - 1
-        out.append((idx, off, min(ml, 65535)))
+        out.append((idx, off, min(ml, 65535) if clamp else ml))
     return out
 
 
