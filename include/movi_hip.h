@@ -20,6 +20,7 @@
  *   MoveStructure::query_all_kmers  src/sequitur.cpp:322-421  movi_kmer_host / movi_kmer_device
  *   MoveStructure::get_SA_entries  src/move_structure.cpp:35-48  movi_locate_device / movi_sa_entries_host / movi_sa_entries_device
  *   MoveStructure::find_sampled_SA_entries  src/move_structure_build.cpp:1174-1212  movi_ssa_build
+ *   MoveStructure::build (--preprocessed)  src/move_structure_build.cpp:17-72, :240-324  movi_build_from_rlbwt
  *   MoveStructure::serialize_sampled_SA / deserialize_sampled_SA  src/move_structure_io.cpp:710-744  movi_ssa_save / movi_ssa_load
  *   MoveStructure::build_doc_pats / build_doc_sets  src/move_structure_color.cpp:4-72  movi_color_build
  *   MoveStructure::flat_and_serialize_colors_vectors / deserialize_doc_sets_flat  src/move_structure_io.cpp:513-548,587-607  movi_color_save / movi_color_load
@@ -615,6 +616,28 @@ int movi_multi_classify_device(movi_index_t *ix, const uint8_t *d_bases, const u
  * together do not meet: with h_counts its counter rows whole, without them scratch within "color_scratch_bytes". */
 int movi_multi_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint32_t min_len,
                              movi_mc_read_t *h_out, uint32_t *h_counts, uint16_t *h_out_pml, uint8_t *h_read_err, movi_query_stats_t *stats);
+
+/* ---- index.movi from a run-length BWT ----------------------------------------- */
+
+/* MoveStructure::build() with --preprocessed (src/move_structure_build.cpp:17-72, :240-324): the move table from the BWT's run heads,
+ * run lengths and, for the *-thresholds types, one threshold per run in pfp-thresholds' .thr_pos convention -- on the device, without
+ * the reference's n + 1-bit vector: run starts by a prefix sum, the runs cut at the sorted distinct thresholds and into pieces of
+ * the type's MAX_RUN_LENGTH, LF of the row heads by a per-character sum, id / offset by a binary search per row, the threshold bits
+ * from the nearest row below of every other character, blocked ids (block size halved until they fit the row's id field, the bound
+ * the reference applies in every round, src/move_structure_build.cpp:956) or the tally table, then the
+ * packed rows.  *h_image is the index.movi file, byte for byte serialize()'s with zero header padding, in page-locked memory:
+ * release it with movi_host_free; movi_index_parse reads it as it is.
+ * h_heads[k] / h_lens[k]: the byte and the length of the k-th maximal run, original_r of them; the terminator is byte 0.  h_thr: NULL
+ * for the types without thresholds (2, 3, 5), where it is not read.  Checked on the host before any device call, MOVI_ERR_ARG with
+ * the array and the reason in the message: a NULL argument, an unsupported mode, no run, a run of length zero, 2^40 characters or
+ * more, two neighbouring runs with one head, a terminator count other than 1, an alphabet outside the engine's scope (at most 4
+ * symbols, or '%' + 4: then the table is a separator table, as in the reference), a threshold above the text's length.
+ * More than 2^31 - 2 runs, or rows once the runs are cut, is MOVI_ERR_ARG too: hipcub's item counts are int (chunked scans: not yet).
+ * The text's length may be anything below 2^40.  A threshold strictly inside a row after the cut is MOVI_ERR_INVARIANT (an internal
+ * error: nothing is packed).  Every device allocation is freed on every return path; a failed call leaves *h_image NULL.
+ * Not a capture-safe entry point: it allocates, reads sizes back and waits. */
+int movi_build_from_rlbwt(int device, uint32_t mode, const uint8_t *h_heads, const uint64_t *h_lens, const uint64_t *h_thr /* NULL for modes 2, 3, 5 */,
+                          uint64_t original_r, void **h_image, size_t *image_bytes);      /* release with movi_host_free */
 
 /* ---- page-locked host memory --------------------------------------------------- */
 

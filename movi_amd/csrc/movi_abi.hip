@@ -5,6 +5,7 @@
 #include "../../include/movi_hip.h"
 #include "movi_kernels.hpp"
 #include "movi_expand_host.hpp"
+#include "movi_build.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -2089,6 +2090,26 @@ int movi_host_free(void *p) {
     if (!p) return MOVI_OK;
     HIP_TRY(hipHostFree(p));
     return MOVI_OK;
+}
+
+// ------------------------------------------------------------- index.movi from a run-length BWT (movi_walk_build.hip)
+
+int movi_build_from_rlbwt(int device, uint32_t mode, const uint8_t *h_heads, const uint64_t *h_lens, const uint64_t *h_thr,
+                          uint64_t original_r, void **h_image, size_t *image_bytes) {
+    if (h_image) *h_image = nullptr;
+    if (image_bytes) *image_bytes = 0;
+    if (!h_heads || !h_lens || !h_image || !image_bytes) return fail(MOVI_ERR_ARG, "NULL argument");
+    if (!mode_supported(mode)) return fail(MOVI_ERR_ARG, "unsupported mode");
+    if (mode_has_thresholds(mode) && !h_thr) return fail(MOVI_ERR_ARG, "the *-thresholds types need h_thr");
+    // everything a kernel of the builder relies on, before any device call
+    RlbwtInfo info;
+    RlbwtArray which;
+    std::string why;
+    if (!rlbwt_check(h_heads, h_lens, mode_has_thresholds(mode) ? h_thr : nullptr, original_r, info, which, why))
+        return fail(MOVI_ERR_ARG, std::string(which == kRlbwtHeads ? "h_heads: " : which == kRlbwtLens ? "h_lens: " : "h_thr: ") + why);
+    HIP_TRY(hipSetDevice(device));
+    const int rc = build_from_rlbwt(mode, h_heads, h_lens, mode_has_thresholds(mode) ? h_thr : nullptr, original_r, info, h_image, image_bytes, why);
+    return rc == MOVI_OK ? MOVI_OK : fail(rc, why);
 }
 
 int movi_host_register(void *p, size_t bytes) {

@@ -9,6 +9,7 @@ Reference seam (file:line under /root/reference) -> here:
   MoveStructure::query_all_kmers      src/sequitur.cpp:322-421           -> MoveIndex.query_kmers
   MoveStructure::get_SA_entries       src/move_structure.cpp:35-48       -> MoveIndex.locate / query_sa_entries
   MoveStructure::find_sampled_SA_entries src/move_structure_build.cpp:1174 -> MoveIndex.build_ssa (save_ssa / load_ssa: ssa.movi)
+  MoveStructure::build (--preprocessed) src/move_structure_build.cpp:17-72 -> build_image
 
 All compute happens in libmovi_hip.so on the GPU; this file only marshals
 buffers.  Errors are MoviError (the reference throws std::runtime_error).
@@ -55,6 +56,27 @@ def parse_index_image(image):
     off, nb = C.c_size_t(0), C.c_size_t(0)
     check(lib().movi_index_parse(buf.ctypes.data, buf.size, C.byref(c), C.byref(off), C.byref(nb)))
     return IndexDesc(c), c, off.value, nb.value
+
+
+def build_image(heads, lens, thr, mode, device=0):
+    """movi_build_from_rlbwt: the bytes of index.movi from a run-length BWT, built on the GPU.  heads: one byte per maximal
+    run (bytes or uint8), lens: the runs' lengths, thr: one threshold per run in the .thr_pos convention (None for the types
+    without thresholds: 2, 3, 5).  MoveIndex.from_image takes the result."""
+    heads = np.ascontiguousarray(np.frombuffer(heads, np.uint8) if isinstance(heads, (bytes, bytearray)) else heads, np.uint8)
+    lens = np.ascontiguousarray(lens, np.uint64)
+    if lens.size != heads.size:
+        raise ValueError("heads and lens differ in length")
+    if thr is not None:
+        thr = np.ascontiguousarray(thr, np.uint64)
+        if thr.size != heads.size:
+            raise ValueError("heads and thr differ in length")
+    img, nbytes = C.c_void_p(), C.c_size_t(0)
+    check(lib().movi_build_from_rlbwt(int(device), int(mode), heads.ctypes.data, lens.ctypes.data,
+                                      thr.ctypes.data if thr is not None else None, heads.size, C.byref(img), C.byref(nbytes)))
+    try:
+        return C.string_at(img.value, nbytes.value)
+    finally:
+        lib().movi_host_free(img)
 
 
 def _pack_reads(reads):

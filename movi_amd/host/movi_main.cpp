@@ -252,24 +252,11 @@ private:
 
 // A regular read file is memory-mapped: the parser then cuts lines and batches without copying a byte, and its worker
 // threads copy the sequences straight from the page cache into the chunk; pipes and stdin go through the stream.
-struct InputMapping {
-    void *p = MAP_FAILED;
-    size_t n = 0;
-    ~InputMapping() { if (p != MAP_FAILED) munmap(p, n); }
-};
+// (InputMapping: reads.hpp)
 std::unique_ptr<BatchReader> open_reader(const std::string &path, std::istream &in, size_t min_reads, InputMapping &map) {
-    if (path != "-" && !std::getenv("MOVI_NO_MMAP")) {
-        const int fd = open(path.c_str(), O_RDONLY);
-        struct stat sb;
-        if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0) {
-            map.n = (size_t)sb.st_size;
-            map.p = mmap(nullptr, map.n, PROT_READ, MAP_PRIVATE, fd, 0);
-            // (populating the mapping ahead of the parser from a helper thread -- MADV_POPULATE_READ, 16 MB at a time -- was
-            // measured and dropped: it contends with the parser's own faults for the address-space lock; scan 14 -> 23 ms)
-            if (map.p != MAP_FAILED) madvise(map.p, map.n, MADV_SEQUENTIAL);
-        }
-        if (fd >= 0) close(fd);
-    }
+    // (populating the mapping ahead of the parser from a helper thread -- MADV_POPULATE_READ, 16 MB at a time -- was
+    // measured and dropped: it contends with the parser's own faults for the address-space lock; scan 14 -> 23 ms)
+    if (path != "-" && !std::getenv("MOVI_NO_MMAP")) (void)map.map(path);
     if (map.p != MAP_FAILED) return std::unique_ptr<BatchReader>(new BatchReader(static_cast<const char *>(map.p), map.n, min_reads));
     return std::unique_ptr<BatchReader>(new BatchReader(in, min_reads));
 }
@@ -1070,6 +1057,7 @@ int main(int argc, char **argv) {
             const int rc = run_build(o);
             return (rc == 0 && o.color) ? run_color(o) : rc;
         }
+        if (o.command == "rlbwt") return run_rlbwt(o);
         if (o.command == "color") return run_color(o);
         if (o.command == "build-SA") return run_build_sa(o);
         return run_query(o);

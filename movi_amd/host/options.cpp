@@ -29,6 +29,7 @@ const Spec kSpecs[] = {
     {"logs", 0, false},          {"mmap", 0, false},        {"gen-reads", 0, false},
     {"fasta", 'f', true},          {"separators", 0, false},  {"seg-len", 0, true},
     {"ahead-rows", 0, true},        {"sample-rate", 0, true},
+    {"preprocessed", 0, false},  {"bwt-file", 0, true},     // build from a run-length BWT; movi rlbwt (src/movi_parser.cpp:112, :202-203)
     // Movi Color, default colour mode (src/movi_parser.cpp:119-121, 164-179, 193-199)
     {"multi-classify", 0, false}, {"min-len", 0, true},     {"report-all", 0, false},
     {"min-diff-frac", 0, true},  {"min-score-frac", 0, true}, {"color", 0, false},
@@ -96,7 +97,10 @@ std::string usage() {
            "       movi view --bpf FILE\n"
            "       movi null -i DIR [--gen-reads -f REF.fasta] [--pml|--zml]\n"
            "       movi build -i DIR -f REF.fasta [--type regular-thresholds|blocked-thresholds|sampled-thresholds|regular|blocked|sampled]\n"
-           "                  [--separators] [--color]\n";
+           "                  [--separators] [--color]\n"
+           "       movi build -i DIR -f REF --preprocessed [--type ...] [--device D]   (REF.bwt.heads + REF.bwt.len [+ REF.thr_pos] -> DIR/index.movi,\n"
+           "                  built on the GPU; --separators is recognised from the alphabet)\n"
+           "       movi rlbwt --bwt-file FILE   (FILE -> FILE.heads + FILE.len)\n";
 }
 
 Options parse_args(int argc, char **argv) {
@@ -278,6 +282,13 @@ Options parse_args(int argc, char **argv) {
         o.color = has("color");                                   // src/movi_parser.cpp:119-121
         refuse_color_modes(seen);
         if (has("device")) o.device = (int)to_int("device", val("device"));
+        o.preprocessed = has("preprocessed");                     // src/movi_parser.cpp:289-291
+        if (o.preprocessed && o.color)
+            throw UsageError("--color cannot be combined with --preprocessed: the document offsets come from the FASTA, which is not read");
+    } else if (o.command == "rlbwt") {
+        // src/movi_parser.cpp:440-446
+        if (seen["bwt-file"].size() != 1) throw UsageError("Please specify one bwt file.");
+        o.bwt_file = val("bwt-file");
     } else if (o.command == "color") {
         // src/movi_parser.cpp:193-199, handled at :319-330
         if (seen["index"].size() != 1) throw UsageError("Please specify the index directory file.");
@@ -303,7 +314,7 @@ Options parse_args(int argc, char **argv) {
         o.small_bpf = has("small-bpf");
         o.large_bpf = has("large-bpf");
     } else {
-        throw UsageError("The '" + o.command + "' action is not part of the MI355X engine (query, view, null, build, build-SA and color only); use "
+        throw UsageError("The '" + o.command + "' action is not part of the MI355X engine (query, view, null, build, rlbwt, build-SA and color only); use "
                          "the reference movi for inspect / ftab.");
     }
     return o;

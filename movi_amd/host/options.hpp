@@ -10,7 +10,7 @@
 namespace movi_host {
 
 struct Options {
-    std::string command;          // "query" | "view" | "null" | "plan" | "build" | "build-SA" | "color"
+    std::string command;          // "query" | "view" | "null" | "plan" | "build" | "rlbwt" | "build-SA" | "color"
     std::string index_dir;        // -i / --index
     std::string read_file;        // -r / --read ("-" = stdin)
     std::string out_file;         // -o / --out-file
@@ -18,6 +18,8 @@ struct Options {
     std::string ref_file;         // null --gen-reads -f/--fasta; build -f/--fasta
     std::string index_type = "regular-thresholds";   // build --type (DEFAULT_INDEX_TYPE, src/movi_launcher.cpp:17)
     bool separators = false;      // build --separators
+    bool preprocessed = false;    // build --preprocessed: REF.bwt.heads + REF.bwt.len (+ REF.thr_pos) instead of a FASTA, built on the GPU
+    std::string bwt_file;         // rlbwt --bwt-file
     bool gen_reads = false;       // null --gen-reads
     bool pml = true;              // default query type (movi_options.hpp:243)
     bool count = false;
@@ -70,6 +72,7 @@ struct UsageError : std::runtime_error {
 // Throws UsageError with the reference's message texts where they exist.
 Options parse_args(int argc, char **argv);
 std::string usage();
-int run_build(const Options &o);  // build_cmd.cpp (writes DIR/ref.fa.doc_offsets too when o.color)
+int run_build(const Options &o);  // build_cmd.cpp (writes DIR/ref.fa.doc_offsets too when o.color; --preprocessed: from a run-length BWT)
+int run_rlbwt(const Options &o);  // build_cmd.cpp
 
 }  // namespace movi_host

@@ -25,7 +25,35 @@
 #include <thread>
 #include <vector>
 
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 namespace movi_host {
+
+// A regular, non-empty file mapped read-only for one sequential pass (the read file of `movi query`; the BWT of `movi rlbwt`; the
+// run files of `movi build --preprocessed`).  map() is false, and nothing is mapped, for anything else.
+struct InputMapping {
+    void *p = MAP_FAILED;
+    size_t n = 0;
+    InputMapping() = default;
+    InputMapping(const InputMapping &) = delete;
+    InputMapping &operator=(const InputMapping &) = delete;
+    ~InputMapping() { if (p != MAP_FAILED) munmap(p, n); }
+    bool map(const std::string &path) {
+        const int fd = open(path.c_str(), O_RDONLY);
+        struct stat sb;
+        if (fd >= 0 && fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > 0) {
+            n = (size_t)sb.st_size;
+            p = mmap(nullptr, n, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (p != MAP_FAILED) madvise(p, n, MADV_SEQUENTIAL);
+        }
+        if (fd >= 0) close(fd);
+        return p != MAP_FAILED;
+    }
+    const uint8_t *bytes() const { return static_cast<const uint8_t *>(p); }
+};
 
 // A byte buffer that can grow WITHOUT initialising its bytes (std::vector value-initialises on resize: for a 1 GB chunk
 // that is one single-threaded pass of page faults before the parallel fill even starts).  Grow-only capacity.

@@ -23,6 +23,9 @@
 //            with substitutions)
 //        build_index reads <text.bin> <n_reads> <read_len> <sub_rate> <seed> <out_file>
 //        build_index pangenome <ancestor_len> <n_genomes> <snp_rate> <seed> <mode> <out_dir> text-only     (writes text.bin only)
+//        ... --emit-rlbwt PREFIX   (anywhere on a fasta / pangenome line: also writes PREFIX.bwt.heads, PREFIX.bwt.len and PREFIX.thr_pos,
+//            the run-length BWT and the per-run thresholds as `movi rlbwt` and pfp-thresholds write them: the input of
+//            `movi build --preprocessed`)
 #include <algorithm>
 #include <array>
 #include <cstdint>
@@ -147,7 +150,8 @@ static void append_clean(std::vector<uint8_t> &text, const std::string &seq, boo
 static void put64(std::vector<uint8_t> &o, uint64_t v) { for (int i = 0; i < 8; i++) o.push_back((uint8_t)(v >> (8 * i))); }
 
 // ------------------------------------------------------------------------------- text -> index.movi bytes
-static std::vector<uint8_t> build_index(std::vector<uint8_t> &text, int mode) {
+// emit_rlbwt (optional): the prefix of the run-length BWT files to write beside the index.
+static std::vector<uint8_t> build_index(std::vector<uint8_t> &text, int mode, const std::string *emit_rlbwt = nullptr) {
     const bool with_thresholds = mode != 5 && mode != 3 && mode != 2;     // sampled / regular / blocked: USE_THRESHOLDS is off
     text.push_back(0);                                                    // terminator
     const sa_t n = (sa_t)text.size();
@@ -197,6 +201,22 @@ static std::vector<uint8_t> build_index(std::vector<uint8_t> &text, int mode) {
             seen[c] = true;
             curmin[c] = INF;                                              // the range restarts after this position
         }
+    }
+    if (emit_rlbwt) {                                                     // one byte / five bytes / five bytes per run, little-endian
+        std::ofstream hf(*emit_rlbwt + ".bwt.heads", std::ios::binary), lf(*emit_rlbwt + ".bwt.len", std::ios::binary),
+            tf(*emit_rlbwt + ".thr_pos", std::ios::binary);
+        size_t k = 0;
+        for (sa_t i = 0; i < n;) {
+            sa_t j = i;
+            while (j < n && bwt[j] == bwt[i]) j++;
+            const uint64_t len = (uint64_t)(j - i), t = thr[k++];
+            hf.put((char)bwt[i]);
+            lf.write(reinterpret_cast<const char *>(&len), 5);
+            tf.write(reinterpret_cast<const char *>(&t), 5);
+            i = j;
+        }
+        hf.close(); lf.close(); tf.close();
+        if (!hf.good() || !lf.good() || !tf.good()) { fprintf(stderr, "cannot write %s.bwt.heads / .bwt.len / .thr_pos\n", emit_rlbwt->c_str()); exit(1); }
     }
     if (with_thresholds) for (uint64_t t : thr) hard[t] = true;           // rows split at thresholds (:733-746)
     std::vector<sa_t>().swap(lcp);
@@ -505,6 +525,14 @@ std::string movi_build_index_from_fasta(const std::string &fasta, int mode, cons
 
 #ifndef MOVI_BUILD_INDEX_NO_MAIN
 int main(int argc, char **argv) {
+    std::string emit_rlbwt;
+    for (int i = 1; i + 1 < argc; i++)
+        if (std::string(argv[i]) == "--emit-rlbwt") {                      // taken out of the line: the rest is positional
+            emit_rlbwt = argv[i + 1];
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2;
+            break;
+        }
     if (argc < 2) { fprintf(stderr, "usage: see the header of tools/build_index.cpp\n"); return 1; }
     const std::string cmd = argv[1];
     std::vector<uint8_t> text;
@@ -580,7 +608,7 @@ int main(int argc, char **argv) {
         draw_reads(text, reads, n_reads, read_len, sub_rate, seed * 31 + 99 + set);
         write_file(out_dir + (set ? "/reads2.bin" : "/reads.bin"), reads);
     }
-    const std::vector<uint8_t> img = build_index(text, mode);
+    const std::vector<uint8_t> img = build_index(text, mode, emit_rlbwt.empty() ? nullptr : &emit_rlbwt);
     write_file(out_dir + "/index.movi", img);
     return 0;
 }
