@@ -288,8 +288,10 @@ int movi_launch_log(char *buf, size_t cap, size_t *needed);
  * positions that reach their LF target without a fast-forward, tallied when the look-ahead rows are built: 0.83 on the
  * pangenome BWT, 0.51 on a uniformly random run sequence; -1 = not tallied yet), "device_scratch_bytes" (device scratch the
  * *_device calls hold: movi_pml_device's mask words -- retired buffers that captured graphs may still use included --, the u16 vector
- * of a movi_pml_mask_device call whose path has no mask output, the segment workspace), "host_staging_bytes" (the *_host calls'
- * device staging).  Unknown key: MOVI_ERR_ARG. */
+ * of a movi_pml_mask_device call whose path has no mask output, the segment workspace, the park queue), "host_staging_bytes" (the
+ * *_host calls' device staging), "park_lanes" (what the last PML call's mask walk parked at: 0 = it parked nothing) and "parked_reads"
+ * (reads the last movi_pml_device / movi_pml_mask_device call's first launch handed to its second; waits for the device, so not under a
+ * stream capture).  Unknown key: MOVI_ERR_ARG. */
 int movi_index_info(const movi_index_t *ix, const char *key, double *value);
 
 /* ---- PML as reset masks (round 6) ----------------------------------------------- */
@@ -734,7 +736,14 @@ int movi_host_unregister(void *p);
  * vector: 22.7 -> 33 - 34 Gbases/s on 1 M x 150 bp; 1 = every call; 2 = both ways down side by side, "host_mask_share" percent
  * (default 70) of the bases as masks, the rest as the vector itself by DMA into a page-locked vector; 0 = never masks: a caller whose
  * own threads are busy, like `movi query`),
- * "fused_expand" (1, the default; 0 = the expansion by kernels of their own behind the walk: A/B), "reserve_device_masks" (device scratch
+ * "fused_expand" (1, the default; 0 = the expansion by kernels of their own behind the walk: A/B),
+ * "park_lanes" (parked lanes of the mask walk, movi_pml_device / movi_pml_mask_device: a wavefront leaves its loop when at most N of its
+ * lanes still walk, parks their state in a queue in device scratch and retires its other reads; a second launch of the same kernel behind
+ * it on the same stream resumes the parked reads 64 to a wavefront.  -1, the default: the launch policy decides (plan_pml: big batches of
+ * short reads -- and picks 0 there: c2 is slower at every N from 2 to 16 although SIMT rises, profiles/park_lanes.txt); 0 = off; 1 .. 63 = N wherever the walk writes
+ * masks itself, and for the vector only on the fused route.  Same answers and counters either way.  The queue is reserved with the mask
+ * words by movi_index_prepare, or by this option on a handle that holds mask words; it never grows under a stream capture: a captured call
+ * whose queue does not fit parks nothing), "reserve_device_masks" (device scratch
  * for the mask words of movi_pml_device calls of up to this many bases, reserved now instead of inside the first such call; grow-only,
  * beside what movi_index_prepare reserves),
  * "host_threads" (worker threads of the host-side expansion, 0 = three quarters of the CPUs the process may use -- affinity mask capped by the cgroup's quota --, at most 24),

@@ -182,6 +182,11 @@ struct movi_index {
     size_t dmask_cap = 0;
     bool dmask_in_graph = false;
     std::vector<std::pair<void *, size_t>> dmask_retired;
+    // the park queue of the mask walk's parked lanes (DevIndex::park_q; "park_lanes"): records of kParkRecBytes, reserved with the mask words
+    // and grown, retired and freed by the same rules (a retired queue goes on dmask_retired)
+    void *dpark = nullptr;
+    size_t dpark_cap = 0;
+    bool dpark_in_graph = false;
 };
 
 static void release_scratch(movi_index *ix);
@@ -212,6 +217,25 @@ static hipError_t grow_dmask(movi_index *ix, size_t bytes) {
     ix->dmask_in_graph = false;
     return grow(&ix->dmask, &ix->dmask_cap, bytes);
 }
+// ... and the park queue, likewise
+static hipError_t grow_dpark(movi_index *ix, size_t bytes) {
+    if (ix->dpark_cap >= std::max<size_t>(bytes, 8)) return hipSuccess;
+    if (ix->dpark && ix->dpark_in_graph) {
+        ix->dmask_retired.emplace_back(ix->dpark, ix->dpark_cap);
+        ix->dpark = nullptr;
+        ix->dpark_cap = 0;
+    }
+    ix->dpark_in_graph = false;
+    return grow(&ix->dpark, &ix->dpark_cap, bytes);
+}
+// the lanes a wavefront of a call on this handle may park: what "park_lanes" asks for, or what plan_pml's own rule can pick
+static int park_lanes_wanted(const movi_index *ix) { return ix->cfg.park_lanes > 0 ? ix->cfg.park_lanes : (ix->cfg.park_lanes < 0 ? kParkLanesAuto : 0); }
+// bytes of the queue of a call of n_reads reads: one record per lane of the second launch's grid, as launch_pml counts them for any block
+// of up to 256 threads (blocks x wavefronts per block <= wavefronts of reads + 3; the grid is whole blocks)
+static size_t park_queue_bytes(uint64_t n_reads, int lanes) {
+    const uint64_t recs = (((n_reads + 63) / 64 + 3) * (uint64_t)lanes + 255) / 256 * 256;
+    return kParkHeadBytes + (size_t)recs * kParkRecBytes;
+}
 // Is `s` being captured into a graph?  A query that cannot tell (hipErrorStreamCaptureImplicit: the null stream while another stream
 // captures in global mode) answers yes: the callers then take the route that allocates nothing.
 static bool stream_capturing(hipStream_t s) {
@@ -221,6 +245,18 @@ static bool stream_capturing(hipStream_t s) {
         return true;
     }
     return st != hipStreamCaptureStatusNone;
+}
+// The queue of a mask walk of n_reads reads on `s`: grown outside a stream capture only; a call whose queue does not fit runs with parking off.
+static void lend_park_queue(movi_index *ix, uint64_t n_reads, hipStream_t s, MaskArgs &m) {
+    const int lanes = park_lanes_wanted(ix);
+    if (lanes <= 0) return;
+    const size_t need = park_queue_bytes(n_reads, lanes);
+    const bool capturing = stream_capturing(s);
+    if (!capturing && grow_dpark(ix, need) != hipSuccess) { (void)hipGetLastError(); return; }
+    if (need > ix->dpark_cap) return;
+    if (capturing) ix->dpark_in_graph = true;
+    m.park_q = ix->dpark;
+    m.park_cap = (ix->dpark_cap - kParkHeadBytes) / kParkRecBytes;
 }
 // The upload stream of the overlapped host paths.  Streams of one priority share a handful of hardware queues, and a chunk's stream that
 // landed on the upload stream's queue had its walk queued behind the copies' completion packets (every sixth chunk waited for uploads that
@@ -1176,7 +1212,16 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
         ix->cfg.fused_expand = (int)value;
         return MOVI_OK;
     }
-    if (!strcmp(key, "reserve_device_masks")) {              // device scratch for the mask words of movi_pml_device calls of up to `value` bases (and as many reads / 16)
+    if (!strcmp(key, "park_lanes")) {                        // the mask walk's parked lanes: -1 = the policy (plan_pml), 0 = off, 1 .. 63 = a wavefront stops at that many walking lanes (A/B)
+        if (value < -1 || value > 63) return fail(MOVI_ERR_ARG, "park_lanes must be -1 .. 63");
+        ix->cfg.park_lanes = (int)value;
+        if (ix->dmask_cap != 0 && park_lanes_wanted(ix) > 0) {   // where the mask words are reserved, so is the queue (no room: such calls park nothing)
+            HIP_TRY(hipSetDevice(ix->device));
+            if (grow_dpark(ix, park_queue_bytes(kPrepareMaskReads, park_lanes_wanted(ix))) != hipSuccess) (void)hipGetLastError();
+        }
+        return MOVI_OK;
+    }
+    if (!strcmp(key, "reserve_device_masks")) {             // device scratch for the mask words of movi_pml_device calls of up to `value` bases (and as many reads / 16)
         if (value < 0 || (uint64_t)value > (1ull << 40)) return fail(MOVI_ERR_ARG, "reserve_device_masks out of range");
         HIP_TRY(hipSetDevice(ix->device));
         HIP_TRY(grow_dmask(ix, (size_t)pml_mask_words((uint64_t)value / 16 + 1, (uint64_t)value, 0) * 4));
@@ -1365,6 +1410,7 @@ int movi_pml_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_
                 m.words = static_cast<uint32_t *>(ix->dmask);
                 m.phase = 0;
                 m.expand_out = d_out_pml;
+                lend_park_queue(ix, n_reads, s, m);
                 return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, nullptr, d_read_err, d_read_order, stream, ClsArgs(), nullptr,
                                  nullptr, -1, nullptr, &m, nullptr, nullptr, true);
             }
@@ -1388,6 +1434,10 @@ int movi_pml_mask_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_
     MaskArgs m;
     m.words = d_mask_words;
     m.phase = (uint32_t)(first_base & 31u);
+    if (ix && n_reads) {
+        if (hipSetDevice(ix->device) == hipSuccess) lend_park_queue(ix, n_reads, static_cast<hipStream_t>(stream), m);
+        else (void)hipGetLastError();                        // (ml_device reports it)
+    }
     return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, nullptr, d_read_err, d_read_order, stream, ClsArgs(), nullptr,
                      nullptr, -1, nullptr, &m);
 }
@@ -1456,11 +1506,19 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     else if (!strcmp(key, "derived_bytes")) *value = kmer + ftab + ahead + deep + ckpt + locate + color;
     else if (!strcmp(key, "ahead_no_ff")) *value = ix->ahead_tallied ? ix->ahead_no_ff : -1.0;
     else if (!strcmp(key, "device_scratch_bytes")) {         // device scratch the *_device calls hold: mask words (retired ones too), vector, segment workspace
-        double b = (double)ix->dmask_cap + (double)ix->scratch_cap[movi_index::kTmp] + (double)ix->seg_ws.cap + (double)ix->color_scratch_cap;
+        double b = (double)ix->dmask_cap + (double)ix->dpark_cap + (double)ix->scratch_cap[movi_index::kTmp] + (double)ix->seg_ws.cap + (double)ix->color_scratch_cap;
         for (const auto &r : ix->dmask_retired) b += (double)r.second;
         *value = b;
     }
-    else if (!strcmp(key, "host_staging_bytes")) {           // device staging the synchronous *_host calls hold at the moment
+    else if (!strcmp(key, "park_lanes")) *value = (double)ix->last_launch.park_lanes;   // what the last PML call's mask walk parked at (0 = it parked nothing)
+    else if (!strcmp(key, "parked_reads")) {                 // reads the last query call's first launch handed to its second (waits for the device; not under a stream capture)
+        unsigned long long parked = 0;
+        HIP_TRY(hipSetDevice(ix->device));
+        HIP_TRY(hipDeviceSynchronize());
+        if (ix->last_launch.park_lanes > 0 && ix->dpark) HIP_TRY(hipMemcpy(&parked, ix->dpark, sizeof(parked), hipMemcpyDeviceToHost));   // (the queue's head)
+        *value = (double)parked;
+    }
+    else if (!strcmp(key, "host_staging_bytes")) {          // device staging the synchronous *_host calls hold at the moment
         double b = 0.0;
         for (int k = 0; k < movi_index::kScratchSlots; k++) b += (double)ix->scratch_cap[k];
         *value = b;
@@ -1592,6 +1650,10 @@ static void release_scratch(movi_index *ix) {
     ix->dmask = nullptr;
     ix->dmask_cap = 0;
     ix->dmask_in_graph = false;
+    if (ix->dpark) (void)hipFree(ix->dpark);
+    ix->dpark = nullptr;
+    ix->dpark_cap = 0;
+    ix->dpark_in_graph = false;
     for (const auto &r : ix->dmask_retired) (void)hipFree(r.first);
     ix->dmask_retired.clear();
     if (ix->h_rel) (void)hipHostFree(ix->h_rel);
@@ -2562,6 +2624,8 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
         // movi_pml_device's mask words for a default batch (a bigger "reserve_device_masks" stays): its first call allocates nothing.
         // No room is no failure -- an uncaptured call grows them, a captured one takes the packer route
         if (grow_dmask(ix, (size_t)pml_mask_words(kPrepareMaskReads, kPrepareMaskBases, 0) * 4) != hipSuccess) (void)hipGetLastError();
+        // ... and the park queue of the same batch, where calls on this handle can park ("park_lanes"; no room: such calls park nothing)
+        if (park_lanes_wanted(ix) > 0 && grow_dpark(ix, park_queue_bytes(kPrepareMaskReads, park_lanes_wanted(ix))) != hipSuccess) (void)hipGetLastError();
     }
     if (what & MOVI_PREPARE_COUNT) {
         const int rc = ensure_count_tables(ix, s, true);

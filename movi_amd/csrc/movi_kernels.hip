@@ -1031,11 +1031,22 @@ bool pml_mask_needs_tmp(const DevIndex &ix, const LaunchCfg &cfg, uint64_t n_rea
     return P.seg_eligible || P.v != 14 || P.stage_lds == 0u;
 }
 
+// The park queue's counter, zeroed in front of the first launch of a mask walk that parks (launch_pml): by a kernel, so that what the
+// second launch resumes never depends on anything but stream order.  It clears the call's counters as well, which the caller's memset has
+// cleared already: captured into a graph (memset, walk, walk), that call was observed to report counters that did not start from zero
+// from the graph's second replay on, while (memset, walk) replayed clean (profiles/park_lanes.txt, section 4; the cause is not known).
+__global__ void park_reset_kernel(unsigned long long *count, DevStats *stats) {
+    if (threadIdx.x == 0) *count = 0ull;
+    unsigned long long *w = reinterpret_cast<unsigned long long *>(stats);
+    if (stats && threadIdx.x < sizeof(DevStats) / sizeof(unsigned long long)) w[threadIdx.x] = 0ull;
+}
+
 hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets,
                       uint64_t n_reads, uint64_t n_bases, uint16_t *d_out, uint8_t *d_err, DevStats *d_stats,
                       const uint32_t *d_order, const LaunchCfg &cfg, hipStream_t stream, const ClsArgs &cls,
                       SegWorkspace *seg_ws, int ragged_hint, int *seg_verdict, LaunchInfo *info, const MaskArgs &mask) {
     if (n_reads == 0) return hipSuccess;
+    if (info) info->park_lanes = 0;
     // 0 = PML vector only, 1 = vector + classification bins, 2 = bins only
     bool want_mask = mask.words != nullptr;                // reset masks out instead of the vector (MaskArgs)
     const bool logging0 = cls.log_ff != nullptr || cls.log_scan != nullptr;
@@ -1081,6 +1092,18 @@ hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
     const bool fused_expand = mask_native && mask.expand_out != nullptr && bt == 64 && d_order == nullptr &&
                               (reinterpret_cast<uintptr_t>(mask.expand_out) & 15u) == 0 && cfg.fused_expand != 0;
     ixl.expand_out = fused_expand ? mask.expand_out : nullptr;
+    // Parked lanes (DevIndex::park_at; the plan's park_lanes): where the walk writes the masks itself -- for the vector only on the fused
+    // route, whose resumed lanes expand their own reads -- the caller lent a queue of one record per lane that can park (park_lanes per
+    // wavefront: no read-back needed).  The queue's counter is zeroed by a kernel on the stream (park_reset_kernel), not by a memset.
+    const uint64_t waves = blocks * (uint64_t)(bt / 64);
+    int park_lanes = (mask_native && (mask.expand_out == nullptr || fused_expand) && mask.park_q != nullptr) ? P.park_lanes : 0;
+    // (room for every lane of the second launch's grid, whatever the counter says; slots are 32-bit)
+    const uint64_t park_grid_lanes = (waves * (uint64_t)(park_lanes > 0 ? park_lanes : 0) + (uint64_t)bt - 1) / (uint64_t)bt * (uint64_t)bt;
+    if (park_lanes > 0 && (park_grid_lanes > mask.park_cap || park_grid_lanes > 0x7FFFFFFFull)) park_lanes = 0;
+    ixl.park_at = (uint32_t)park_lanes;
+    ixl.resume = 0u;
+    ixl.park_count = static_cast<unsigned long long *>(mask.park_q);
+    ixl.park_q = reinterpret_cast<uint4 *>(static_cast<uint8_t *>(mask.park_q) + kParkHeadBytes);
     if (want_mask && !mask_native && !d_out) return hipErrorInvalidValue;     // (pml_mask_needs_tmp told the caller)
     hipError_t e = hipSuccess;
     if (v == 14) {
@@ -1091,7 +1114,20 @@ hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
         L.order = d_order; L.cls = cls;
         L.cls_mode = cm; L.sep = ix.sep ? 1 : 0; L.stg = ixl.stage_lds != 0u ? 1 : 0;
         L.ahd = P.use_deep ? 2 : (P.use_ahead ? 1 : 0); L.psh = P.use_pair ? 1 : 0; L.ring = mask_native ? 2 : (P.use_ring ? 1 : 0);
-        e = ix.idx32 ? launch_walk_u32(L, info) : launch_walk_u64(L, info);
+        if (park_lanes > 0) {
+            hipLaunchKernelGGL(park_reset_kernel, dim3(1), dim3(64), 0, stream, ixl.park_count, d_stats);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = ix.idx32 ? launch_walk_u32(L, info) : launch_walk_u64(L, info);
+        if (e == hipSuccess && park_lanes > 0) {
+            // the second launch: the same kernel resumes the parked reads, 64 to a wavefront -- a grid for every record the first can have
+            // written, the same dynamic LDS, the same stream (stream order is all the synchronisation there is); `info` names the first
+            L.grid = dim3((unsigned)(park_grid_lanes / (uint64_t)bt));
+            L.ix.park_at = 0u;
+            L.ix.resume = 1u;
+            L.order = nullptr;                             // (a record names its read)
+            e = ix.idx32 ? launch_walk_u32(L, nullptr) : launch_walk_u64(L, nullptr);
+        }
     } else {
         // the base-synchronous kernels (every one takes at most 64 KiB of dynamic LDS: the cap's padding)
         if (dyn_lds > 65536) dyn_lds = 65536 - 1024;
@@ -1109,6 +1145,7 @@ hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
         info->block_threads = bt; info->waves_per_cu = P.wpc; info->segmented = 0; info->idx64 = ix.idx32 ? 0 : 1;
         info->staged = (int)ixl.stage_lds;
         info->ahead = P.use_deep ? 2 : (P.use_ahead ? 1 : 0);
+        info->park_lanes = park_lanes;
     }
     if (e == hipSuccess && want_mask && !mask_native) e = launch_pml_to_mask(d_out, d_offsets, n_reads, n_bases, mask.phase, mask.words, stream);
     if (e == hipSuccess && mask_native && mask.expand_out != nullptr && !fused_expand)

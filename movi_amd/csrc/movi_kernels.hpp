@@ -107,7 +107,17 @@ struct DevIndex {
     // its reads' mask words into their u16 PML vectors here (through a tile in the LDS its reads were staged in: pml_kernel_flatp's tail)
     // -- the vector output at the mask walk's instruction count, the expansion hidden under the other wavefronts' gathers
     uint16_t *expand_out;
+    // set per launch, reset-mask output (RING = 2) -- PARKED LANES: a wavefront's iteration count is its slowest lane's (c2: the mean read
+    // takes 81 lane iterations, the mean wavefront 123), so a wavefront leaves its loop when at most `park_at` of its lanes still walk
+    // (0 = off: when none does), parks their state -- one record each, slots reserved by one atomicAdd on *park_count -- and retires its
+    // other reads.  A second launch of the same kernel behind the first on the same stream (`resume` = 1, park_at = 0) takes the records
+    // 64 to a wavefront and finishes those reads.  Stream order is the only synchronisation; launch_pml sizes the queue and both grids.
+    uint32_t park_at;
+    uint32_t resume;
+    uint4 *park_q;                // two uint4 per record: (read, k, row[31:0], row[63:32]), (offset, match length, partial mask word, fast-forward run | state << 30)
+    unsigned long long *park_count;   // the queue's head: records written by the first launch (zeroed on the stream in front of it: park_reset_kernel)
 };
+constexpr size_t kParkRecBytes = 32, kParkHeadBytes = 32;   // the queue: a head that holds the counter, then the records
 
 // Device counters of one query call.
 struct DevStats {
@@ -119,7 +129,7 @@ struct DevStats {
     unsigned long long lane_steps;
     unsigned long long wave_steps;
     unsigned long long pad0_;
-    unsigned long long segments;       // segment-parallel PML: segments walked, reads walked again
+    unsigned long long segments;      // segment-parallel PML: segments walked, reads walked again
     unsigned long long rewalked;
     unsigned long long pad_;
 };
@@ -136,6 +146,7 @@ struct LaunchInfo {
     int idx64 = 0;           // 1 = the 64-bit row-index instantiation
     int ahead = 0;           // 1 = the walk ran on the look-ahead rows (two bases per gather where the next base matches)
     int staged = 0;          // > 0: every lane keeps the next `staged` bases of its read in LDS (pml_kernel_flatp<..., STG = 1>)
+    int park_lanes = 0;      // > 0: the mask walk parked a wavefront's last `park_lanes` lanes and a second launch of the named kernel resumed them
 };
 
 // Classifier::classify bins (src/classifier.cpp:99-143) fused into the PML kernels: per read the number of
@@ -256,6 +267,9 @@ struct MaskArgs {
     // wavefronts' reads itself where it can (one-wavefront blocks, reads in order, a 16-byte aligned vector), pml_expand_* kernels do
     // it behind the walk otherwise; a batch whose path has no mask output of its own simply writes the vector (no masks at all)
     uint16_t *expand_out = nullptr;
+    // parked lanes (DevIndex::park_at): device scratch of kParkHeadBytes + park_cap records of kParkRecBytes; null = the walk parks nothing
+    void *park_q = nullptr;
+    uint64_t park_cap = 0;
 };
 uint64_t pml_mask_words(uint64_t n_reads, uint64_t n_bases, uint32_t phase);          // words a batch's masks take (gap words included)
 bool pml_mask_needs_tmp(const DevIndex &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, bool have_seg_ws);

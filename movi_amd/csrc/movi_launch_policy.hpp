@@ -17,6 +17,8 @@ constexpr uint64_t kOutRingReadLen = 1024;        // ... on by itself for batche
 constexpr size_t kZmlStageBytes = 10240;          // zml_kernel_flat: dynamic LDS per one-wavefront block for its staged reads (160 bases per lane; 16 wavefronts per CU)
 constexpr uint64_t kDeepReadLen = 1024;           // plan_pml: batches whose mean read length is below this walk on the deep rows (where the handle holds them)
 constexpr uint64_t kPairLoadBytes = 2ull << 30;   // walked tables of this size and more: pair-shared gathers (plan_pml)
+constexpr int kParkLanesAuto = 0;                 // parked lanes: what "park_lanes" -1 picks where plan_pml's rule holds; 0 = off -- on c2 every threshold from 2 to 16 is slower than none (84.8 / 81.0 / 75.7 Gbases/s at 2 / 8 / 16 against 88.1: profiles/park_lanes.txt)
+constexpr uint64_t kParkMinRounds = 2;            // ... and only for batches of at least this many rounds of resident wavefronts (unmeasured: with kParkLanesAuto 0 the rule picks nothing; it is where a non-zero default would start from)
 
 struct LaunchCfg {
     int block_threads = 0;   // 0 = auto: 64 for the PML and count kernels and the ZML state machine (finest dispatch grain), 256 for the base-synchronous ZML kernel
@@ -41,6 +43,7 @@ struct LaunchCfg {
     int zml_ahead = 0;     // 1: zml_kernel_flat<6, T, 0, 1> on the look-ahead rows where they exist (a third fewer iterations, no faster: opt-in)
     int fused_expand = 1;  // 1: a mask walk whose caller wants the vector expands its wavefronts' reads itself (DevIndex::expand_out); 0 = pml_expand_* kernels behind the walk: A/B
     int kmer_lookahead = -1; // kmer_kernel: -1 = hinted look-ahead with a split chosen by k and the text's length (kmer_look_step), 0 = every end searched from its own base, n >= 2 = split k / n (A/B)
+    int park_lanes = -1;   // parked lanes of the mask walk (DevIndex::park_at): -1 = plan_pml's rule, 0 never, 1 .. 63 = a wavefront stops at that many walking lanes, wherever the walk can park (A/B)
     int deep = -1;         // the PML walk on the deep rows (DevIndex::rows3) where the handle holds them: -1 = batches of short reads (mean length < kDeepReadLen), 0 never, 1 always
 };
 
@@ -71,6 +74,7 @@ struct PmlPlan {
     uint32_t stage_lds = 0;
     bool use_ring = false, use_ahead = false, use_pair = false;
     bool use_deep = false;           // the walk runs on the deep rows (DevIndex::rows3: three bases per gather)
+    int park_lanes = 0;              // > 0: a mask walk of this plan parks a wavefront's last lanes for a second launch (launch_pml still needs a queue and, for the vector, the fused expansion)
 };
 
 // Reads staged through LDS (pml_kernel_flatp<..., STG = 1>): the block's dynamic LDS holds the next stage_lds bases of each
@@ -160,6 +164,15 @@ inline PmlPlan plan_pml(const TableFacts &ix, const LaunchCfg &cfg, uint64_t n_r
     // copy (16 GB); below that the exchange costs about what the merged accesses give (random 25 / 50 / 100 M rows +4 / +5 / -2 %,
     // real 113 M rows +1.5 %, c2 -2.5 %, c3 -9 %: profiles/r04_pair_shared_gathers.txt).  "pair_loads" 1 / 0 forces it.
     P.use_pair = pair_wanted(cfg, ix.r * (P.use_ahead ? 16ull : 8ull)) && P.stage_lds != 0u && v == 14 && !P.use_deep;
+    // Parked lanes (DevIndex::park_at): only where the walk writes reset masks itself -- the staged default walk, whole reads, no bins.
+    // By itself ("park_lanes" -1) only for batches of kParkMinRounds rounds of wavefronts and more (a capped launch: `rounds` of wpc
+    // wavefronts per CU) and of short reads: long reads roll through their staged stretch and a resumed lane would stage again mid-read
+    // for every one of them.  "park_lanes" N forces it wherever the walk can park.
+    if (want_mask && cm == 0 && !logging && v == 14 && P.stage_lds != 0u && n_reads <= 0xFFFFFFFFull) {   // (a record holds the read in 32 bits)
+        const uint64_t per_round = (uint64_t)cfg.num_cus * (uint64_t)(wpc > 0 ? wpc : 32);
+        const bool auto_on = blocks >= kParkMinRounds * per_round && n_bases / n_reads < kOutRingReadLen;
+        P.park_lanes = cfg.park_lanes > 0 ? std::min(cfg.park_lanes, 63) : ((cfg.park_lanes < 0 && auto_on) ? kParkLanesAuto : 0);
+    }
     return P;
 }
 

@@ -72,8 +72,20 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
     const uint32_t off0 = row_n<MODE>(row_r1) - 1;
 
     // ---- the lane's current read
-    const bool valid = (SEG == 1 ? (*seg.go != 0u && t < *seg.n_seg) : (t < n_reads && (SEG != 2 || seg.read_fail[t] != 0)));
-    const uint64_t rid = (valid && order && SEG == 0) ? order[t] : t;
+    // PARKED LANES (RING == 2; DevIndex::park_at): the launch that resumes them (ix.resume, wave-uniform) takes lane t's read and state
+    // from record t of the queue instead; everything derived from the read id below is derived as a fresh lane derives it.
+    const bool resume = RING == 2 && ix.resume != 0u;
+    uint4 pr0 = make_uint4(0, 0, 0, 0), pr1 = pr0;
+    bool valid_ = (SEG == 1 ? (*seg.go != 0u && t < *seg.n_seg) : (t < n_reads && (SEG != 2 || seg.read_fail[t] != 0)));
+    if (RING == 2) {
+        if (resume) {
+            valid_ = t < *ix.park_count;
+            if (valid_) { pr0 = ix.park_q[2ull * t]; pr1 = ix.park_q[2ull * t + 1ull]; }
+            valid_ = valid_ && pr0.x < n_reads;           // (a record that names no read of this batch is not walked)
+        }
+    }
+    const bool valid = valid_;
+    const uint64_t rid = resume ? (uint64_t)pr0.x : ((valid && order && SEG == 0) ? order[t] : t);
     const uint64_t beg = valid ? (SEG == 1 ? seg.seg_in[rid] : offs[rid]) : 0;
     const uint32_t len = valid ? (SEG == 1 ? seg.seg_len[rid] : (uint32_t)(offs[rid + 1] - beg)) : 0;   // reads are shorter than 2^32 (checked on the host)
     const uint64_t obeg = (SEG == 1 && valid) ? seg.seg_out[rid] : beg;   // where the read's (segment's) PMLs go
@@ -199,6 +211,15 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
     uint32_t ml = 0, ff_run = 0;
     uint32_t off = off0;
     uint64_t rb = 0, rb2 = 0, nx0 = 0, nx1 = 0;           // current 8 bases, the 8 after them, and the next 16 (in flight)
+    if (msk) {
+        if (resume && valid) {                            // where the first launch left this read (its counters went into that launch's sums)
+            k = pr0.y;
+            need = (IdxT)((uint64_t)pr0.z | ((uint64_t)pr0.w << 32));
+            off = pr1.x; ml = pr1.y; mk = pr1.z;
+            ff_run = pr1.w & 0x3FFFFFFFu;
+            st = pr1.w >> 30;
+        }
+    }
     if (st != sDone) {
         load_pair_at(beg + len, rb, rb2);
         fix_pair(beg + len, rb, rb2);
@@ -282,7 +303,7 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
         const uint32_t q = slot < stage_cap ? slot : stage_cap - 1u;
         return s_code[s_stage[(q >> 2) * 256u + (threadIdx.x & 63u) * 4u + (q & 3u)]];
     };
-    if (STG) stage_from(0u, st != sDone);
+    if (STG) stage_from(msk ? k : 0u, st != sDone);       // (k = 0 but in a resumed lane, which stages from where it stands)
     // ---- top of the walk (DevIndex::kmer): the first K bases of the read (segment) by ONE table lookup.  Reads with an
     // illegal base among them, reads of K bases or fewer and K-mers whose walk throws take the ordinary walk.
     // cand: lanes whose K-mer `kidx` is to be looked up (k == 0 there); returns the lanes that took the entry.
@@ -336,7 +357,7 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
         }
         return use;
     };
-    if (ix.kmer_k != 0u) {                     // wave-uniform
+    if (ix.kmer_k != 0u && !resume) {          // wave-uniform (a resumed lane is past the top of its walk)
         const uint32_t K = ix.kmer_k;
         uint32_t kidx = 0, bad = 0;
         for (uint32_t i = 0; i < K; ++i) {
@@ -352,13 +373,19 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
     }
     // AHD: the code of the base after the current one (beyond the read's end: never looked at)
     uint32_t a1 = 0xFFu, a2 = 0xFFu;
-    if (AHD) a1 = staged_code(k + 1);
-    if (AHD == 2) a2 = staged_code(k + 2);
+    if (msk) {
+        if (resume) a = staged_code(0u);                  // the base of step k = kbase
+    }
+    if (AHD) a1 = staged_code(k + 1 - kbase);             // (kbase = 0 but in a resumed lane)
+    if (AHD == 2) a2 = staged_code(k + 2 - kbase);
     uint2 w[4];
     fetch(need, st != sDone, w);
 
+    // The loop runs while more than park_at lanes walk (parked lanes: 0 = off, and always 0 in the launch that resumes them); the lanes
+    // still walking when it ends are parked below.  Same ballot, a count instead of a test for zero: the body is untouched.
+    const uint32_t park_at = msk ? ix.park_at : 0u;
     uint32_t lane_steps = 0, wave_steps = 0;
-    while (wave_any(st != sDone)) {
+    while (msk ? (uint32_t)__popcll(__ballot(st != sDone)) > park_at : wave_any(st != sDone)) {
         const bool act = st < sDone;
         lane_steps += (uint32_t)act;
         wave_steps += 1;
@@ -767,7 +794,13 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
             const uint32_t out_of = (uint32_t)(st != sDone) &
                                     ((uint32_t)(ahead_of >= stage_cap) | ((uint32_t)(ahead_of + 1u >= stage_cap) & (uint32_t)(k + 1 < len)) |
                                      (AHD == 2 ? ((uint32_t)(ahead_of + 2u >= stage_cap) & (uint32_t)(k + 2 < len)) : 0u));
-            if (wave_any(out_of != 0u)) stage_from(k, st != sDone);
+            if (wave_any(out_of != 0u)) {
+                stage_from(k, st != sDone);
+                // (reset masks: every staging load has landed before the paths join again -- they were issued behind the gather, so
+                // this waits for nothing new -- or the loop's tail, whose temporaries may share their registers, gets a vmcnt(0) of
+                // its own in EVERY iteration, in front of the bookkeeping that is meant to run under the gather: seen in the ISA)
+                if (msk) __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0)
+            }
             a = staged_code(k - kbase);
             if (AHD) a1 = staged_code(k + 1 - kbase);
             if (AHD == 2) a2 = staged_code(k + 2 - kbase);
@@ -777,8 +810,56 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
         // in flight, i.e. on the row gather issued above
         if (want_nx) load_pair_at(nx_e, nx0, nx1);
     }
-    if (valid) finish_read();
-    if (msk && ix.expand_out != nullptr) {
+    // ---- parked lanes: whoever still walks hands its read to the launch behind this one.  One atomicAdd reserves the wavefront's slots
+    // (at most park_at of them: the grid of the second launch and the queue are sized by that bound).  The counters so far stay in this
+    // wavefront's sums; a parked read is neither finished nor expanded here.
+    const bool parked = msk && st != sDone;
+    if (msk && park_at != 0u) {                           // wave-uniform
+        const unsigned long long pb = __ballot(parked);
+        if (pb != 0ull) {
+            const uint32_t ln = threadIdx.x & 63u, lead = (uint32_t)__builtin_ctzll(pb);
+            uint32_t slot0 = 0;
+            if (ln == lead) slot0 = (uint32_t)atomicAdd(ix.park_count, (unsigned long long)__popcll(pb));
+            slot0 = __shfl(slot0, lead, 64);
+            if (parked) {
+                const uint32_t slot = slot0 + (uint32_t)__popcll(pb & ((1ull << ln) - 1ull));
+                ix.park_q[2ull * slot] = make_uint4((uint32_t)rid, k, (uint32_t)need, (uint32_t)((uint64_t)need >> 32));
+                ix.park_q[2ull * slot + 1ull] = make_uint4(off, ml, mk, ff_run | (st << 30));
+            }
+        }
+    }
+    if (valid && !parked) finish_read();
+    if (msk && resume && ix.expand_out != nullptr) {
+        // ---- a resumed wavefront's reads lie anywhere in the vector: every lane expands its own read from its own mask words straight
+        // into it -- 16-byte stores for the groups of 8 elements that are 16-byte aligned and wholly inside the read, 2-byte stores for
+        // the edges, never a byte outside [beg, beg + len).  (The first launch's tile may have left anything over this stretch.)
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");            // this lane's own word stores before its loads of them
+        if (valid && len) {
+            const uint32_t *Mx = M;
+            uint16_t *vec = ix.expand_out + beg;
+            uint32_t kx = 0, run = 0, wcur = 0, w0 = Mx[0], w1 = Mx[1];   // (the array has a spare word at its end)
+            auto one = [&]() {
+                if ((kx >> 5) != wcur) { wcur = kx >> 5; w0 = w1; w1 = Mx[wcur + 1]; }
+                run = ((w0 >> (kx & 31u)) & 1u) ? 0u : run + 1u;
+                vec[kx] = (uint16_t)(run > 65535u ? 65535u : run);
+                kx += 1;
+            };
+            while (kx < len && ((beg + kx) & 7u)) one();
+            while (kx + 8u <= len) {
+                if ((kx >> 5) != wcur) { wcur = kx >> 5; w0 = w1; w1 = Mx[wcur + 1]; }
+                const uint32_t bits = (uint32_t)((((uint64_t)w1 << 32) | w0) >> (kx & 31u)) & 0xFFu;
+                uint32_t v[8];
+#pragma unroll
+                for (uint32_t e = 0; e < 8u; ++e) {
+                    run = ((bits >> e) & 1u) ? 0u : run + 1u;
+                    v[e] = run > 65535u ? 65535u : run;
+                }
+                *reinterpret_cast<uint4 *>(vec + kx) = make_uint4(v[0] | (v[1] << 16), v[2] | (v[3] << 16), v[4] | (v[5] << 16), v[6] | (v[7] << 16));
+                kx += 8u;
+            }
+            while (kx < len) one();
+        }
+    } else if (msk && ix.expand_out != nullptr) {
         // ---- the wavefront's walks are over: its reads' reset masks -> their u16 PML vectors (round 6).  The 64 reads of a one-wavefront
         // block (reads in order) are ONE contiguous stretch of the vector: every lane expands its own read -- match_len carried in a register,
         // eight bases per step -- into a tile of the stretch in the LDS its bases were staged in, and the wavefront copies the tile out as
@@ -806,7 +887,7 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
             };
             for (uint64_t A = B0 & ~7ull; A < B1; A += tile_elems) {
                 const uint64_t hi = A + tile_elems < B1 ? A + tile_elems : B1;
-                if (valid && kx < len && beg + kx < hi) {
+                if (valid && !parked && kx < len && beg + kx < hi) {     // (a parked read's stretch of the tile stays as it is: the resuming launch rewrites the read)
                     uint32_t o = (uint32_t)(beg + kx - A);
                     const uint32_t stop = (uint32_t)((endx < hi ? endx : hi) - A);
                     while (o < stop && (o & 7u)) one(o++);

@@ -116,6 +116,44 @@ static uint32_t walk(const uint8_t *rd, uint32_t len, uint32_t top_k, const Desi
     return it;
 }
 
+// PARKED LANES (DevIndex::park_at): a wavefront of 64 consecutive reads stops when at most T of its lanes still walk -- at the
+// (T + 1)-th largest of its lanes' iteration counts -- and the lanes still walking are parked with what they have left; a second launch
+// walks the parked reads 64 to a wavefront, in the order they were parked.  Every wavefront launched is charged kParkWaveCost iterations
+// for its prologue and epilogue.  Printed per design: the share of reads parked, the wavefront iterations of both launches together
+// relative to one launch without parking, the SIMT efficiency of both together, and the longest resumed read.
+#define kParkWaveCost 4
+static int cmp_u32_desc(const void *a, const void *b) { const uint32_t x = *(const uint32_t *)a, y = *(const uint32_t *)b; return x < y ? 1 : x > y ? -1 : 0; }
+static void park_table(const uint32_t *its, uint64_t n_reads, uint64_t lane_iters) {
+    static const uint32_t Ts[] = {0, 2, 4, 8, 12, 16, 24};
+    uint64_t base_wave = 0;
+    uint32_t *left = malloc(n_reads * sizeof *left);
+    for (size_t ti = 0; ti < sizeof Ts / sizeof Ts[0]; ti++) {
+        const uint32_t T = Ts[ti];
+        uint64_t wave_iters = 0, parked = 0;
+        for (uint64_t w0 = 0; w0 < n_reads; w0 += 64) {
+            const uint32_t m = (uint32_t)(n_reads - w0 < 64 ? n_reads - w0 : 64);
+            uint32_t s[64];
+            memcpy(s, its + w0, m * sizeof *s);
+            qsort(s, m, sizeof *s, cmp_u32_desc);
+            const uint32_t stop = T < m ? s[T] : 0;          // the loop runs while more than T lanes walk
+            wave_iters += stop + kParkWaveCost;
+            for (uint32_t l = 0; l < m; l++)
+                if (its[w0 + l] > stop) left[parked++] = its[w0 + l] - stop;
+        }
+        uint32_t longest = 0;
+        for (uint64_t p0 = 0; p0 < parked; p0 += 64) {
+            uint32_t mx = 0;
+            for (uint64_t p = p0; p < parked && p < p0 + 64; p++) if (left[p] > mx) mx = left[p];
+            wave_iters += mx + kParkWaveCost;
+            if (mx > longest) longest = mx;
+        }
+        if (T == 0) base_wave = wave_iters;
+        printf("    park T=%-2u parked %5.1f %%  wave iterations vs T=0 %.3f  SIMT %.3f  longest resumed %u\n", T, 100.0 * parked / n_reads,
+               (double)wave_iters / base_wave, (double)lane_iters / (64.0 * wave_iters), longest);
+    }
+    free(left);
+}
+
 int main(int argc, char **argv) {
     if (argc < 4) { fprintf(stderr, "usage: iter_model index.movi reads.bin read_len [n_reads] [top_k]\n"); return 1; }
     FILE *f = fopen(argv[1], "rb");
@@ -152,11 +190,13 @@ int main(int argc, char **argv) {
     for (size_t di = 0; di < sizeof designs / sizeof designs[0]; di++) {
         Tally t; memset(&t, 0, sizeof t);
         uint32_t wave_max = 0;
+        uint32_t *its = malloc(n_reads * sizeof *its);   // lane iterations of every read (parked lanes, below)
         FILE *df = NULL;
         if (getenv("ITER_DUMP")) { char fn[256]; snprintf(fn, sizeof fn, "%s.%zu", getenv("ITER_DUMP"), di); df = fopen(fn, "wb"); }
         for (uint64_t i = 0; i < n_reads; i++) {
             const uint32_t it = walk(reads + i * L, L, top_k, &designs[di], &t);
             t.iters += it; t.bases += L;
+            its[i] = it;
             if (df) fwrite(&it, 4, 1, df);
             if (it > wave_max) wave_max = it;
             if ((i & 63) == 63 || i + 1 == n_reads) { t.waves_iters += (uint64_t)wave_max * 64; wave_max = 0; }
@@ -167,6 +207,8 @@ int main(int argc, char **argv) {
         const double b = (double)t.bases;
         printf("%-40s %9.4f %9.3f | %7.4f %7.4f %7.4f %7.4f | %7.4f | %6.3f %6.3f %6.4f | %7.4f\n", name, t.iters / b, (double)t.iters / t.waves_iters,
                t.it_arrive / b, t.it_ffwin / b, t.it_mism / b, t.it_scanwin / b, t.chained / b, t.ff_rows / b, t.scan_rows / b, t.repos / b, t.lines / b);
+        park_table(its, n_reads, t.iters);
+        free(its);
     }
     return 0;
 }
