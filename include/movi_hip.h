@@ -331,6 +331,60 @@ int movi_pml_mask_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t 
 int movi_pml_expand_host(const uint32_t *h_mask_words, const uint64_t *h_offsets, uint64_t n_reads,
                          uint16_t *h_out_pml, int n_threads);
 
+/* ---- 2-bit packed reads --------------------------------------------------------- */
+
+/* movi_pml_host and movi_pml_mask_host are bound by their upload: one byte per base over PCIe.  Callers that hold their reads
+ * packed -- or pack while they parse -- hand them over as they are, a quarter of the bytes, and the
+ * GPU unpacks them into the byte per base that every walk stages from.  unpack(pack(x)) == x for every byte value, so every
+ * query sees exactly the bytes it would have seen; check_alphabet's verdict on a byte stays where it is, in code_of.
+ *
+ * The format.  Two bits per base, four bases per byte: base b lives in byte b >> 2 at bits 2 * (b & 3).  The codes are fixed,
+ * A = 0, C = 1, G = 2, T = 3, whatever the index's alphabet is.  b is the ABSOLUTE base index, the numbering offsets[] uses:
+ * as with h_bases, a call whose offsets[0] is not 0 still indexes the packed buffer from its start.  Reads are not byte-aligned
+ * and there is no second offsets array.  Unused bits of the last byte are 0 when written and ignored when read.
+ * Every byte that is not upper-case 'A' / 'C' / 'G' / 'T' is an EXCEPTION -- 'N', lower case, '%', '#', bytes >= 128.  In the
+ * packed stream an exception has code 0; the sparse list says what it was: exc_pos[m], absolute base indexes, strictly
+ * ascending, and exc_byte[m], the original bytes.  The unpackers restore each one exactly.
+ * Cost: an exception takes 9 bytes (8 of position, 1 of value) against the 3/4 byte per base that packing saves: beyond about
+ * one exception per 36 bases, ASCII input is the smaller upload.
+ *
+ * movi_reads_packed_bytes: *bytes = (first_base + n_bases + 3) >> 2, what a packed buffer that holds bases [0, first_base +
+ * n_bases) takes.
+ * movi_reads_pack_host: h_bases[j] is base first_base + j; its code goes to the packed buffer at the absolute position.  Bits
+ * of the first byte that belong to bases before first_base are kept (batch after batch is appended to one buffer); bits of the
+ * last byte past the range are written 0.  At most exc_cap exceptions are written, *n_exc = how many there are: with more than
+ * exc_cap the call returns MOVI_ERR_ARG, *n_exc says what to allocate, and nothing past the caps was written.  Pure host code,
+ * n_threads workers on slices aligned to four bases (0 = the default of movi_pml_expand_host; inputs of less than 2^16 bases
+ * per worker use fewer).
+ * movi_reads_unpack_host: the exact inverse, h_bases_out[j] = base first_base + j.  Exceptions that are not strictly ascending
+ * inside [first_base, first_base + n_bases): MOVI_ERR_ARG.
+ * movi_reads_unpack_device: the same on the GPU -- the building block for every query: unpack into a buffer of the caller's,
+ * then call any *_device entry point on it.  d_packed is indexed like the host buffer, byte b >> 2 from its start, with no
+ * alignment asked of it: the kernel fetches the aligned 4-byte words the needed bytes lie in.  d_bases_out needs no alignment
+ * either (a 16-byte aligned one leaves in 16-byte stores throughout).  Two kernels on `stream` (a hipStream_t) and nothing
+ * else: the call allocates nothing, waits for nothing and can be captured into a graph (movi_index_prepare(MOVI_PREPARE_PML)
+ * loads the kernels' code object; otherwise the first call does).  The list lives on the device and is not checked: an
+ * exception outside the range is left alone. */
+int movi_reads_packed_bytes(uint64_t first_base, uint64_t n_bases, uint64_t *bytes);
+int movi_reads_pack_host(const uint8_t *h_bases, uint64_t first_base, uint64_t n_bases, uint8_t *h_packed, uint64_t *h_exc_pos,
+                         uint8_t *h_exc_byte, uint64_t exc_cap, uint64_t *n_exc, int n_threads);
+int movi_reads_unpack_host(const uint8_t *h_packed, uint64_t first_base, uint64_t n_bases, const uint64_t *h_exc_pos,
+                           const uint8_t *h_exc_byte, uint64_t n_exc, uint8_t *h_bases_out, int n_threads);
+int movi_reads_unpack_device(int device, const uint8_t *d_packed, uint64_t first_base, uint64_t n_bases, const uint64_t *d_exc_pos,
+                             const uint8_t *d_exc_byte, uint64_t n_exc, uint8_t *d_bases_out, void *stream);
+
+/* movi_pml_host / movi_pml_mask_host on packed reads: same chunks, same walks, same way down, same results word for word; only
+ * where a chunk's bases come from differs.  The packed bytes that cover a chunk go up -- overlapped when h_packed is page-locked,
+ * and big calls on pageable buffers page-lock it for their duration, as for h_bases --, the whole exception list goes up once,
+ * and the chunk's stream unpacks into the handle's staging ahead of its walk.  n_exc positions must be strictly ascending and
+ * inside [offsets[0], offsets[n_reads]) (MOVI_ERR_ARG, checked before the device is touched).  Other arguments as there. */
+int movi_pml_packed_host(movi_index_t *ix, const uint8_t *h_packed, const uint64_t *h_exc_pos, const uint8_t *h_exc_byte,
+                         uint64_t n_exc, const uint64_t *h_offsets, uint64_t n_reads, uint16_t *h_out_pml, uint8_t *h_read_err,
+                         movi_query_stats_t *stats);
+int movi_pml_mask_packed_host(movi_index_t *ix, const uint8_t *h_packed, const uint64_t *h_exc_pos, const uint8_t *h_exc_byte,
+                              uint64_t n_exc, const uint64_t *h_offsets, uint64_t n_reads, uint32_t *h_mask_words,
+                              uint8_t *h_read_err, movi_query_stats_t *stats);
+
 /* ---- binary classification bins ------------------------------------------------ */
 
 /* The per-read reduction of Classifier::classify (src/classifier.cpp:99-143) over PML vectors

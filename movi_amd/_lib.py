@@ -97,6 +97,17 @@ SYMBOLS = {
     "movi_pml_mask_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                      C.POINTER(QueryStatsC)]),
     "movi_pml_expand_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_int]),
+    "movi_reads_packed_bytes": (C.c_int, [C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "movi_reads_pack_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                       C.POINTER(C.c_uint64), C.c_int]),
+    "movi_reads_unpack_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.c_int]),
+    "movi_reads_unpack_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                           C.c_void_p, C.c_void_p]),
+    "movi_pml_packed_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                       C.c_void_p, C.c_void_p, C.POINTER(QueryStatsC)]),
+    "movi_pml_mask_packed_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                            C.c_void_p, C.c_void_p, C.POINTER(QueryStatsC)]),
     "movi_pml_logs_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.POINTER(QueryStatsC)]),
     "movi_zml_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,

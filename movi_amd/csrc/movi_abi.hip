@@ -5,6 +5,7 @@
 #include "../../include/movi_hip.h"
 #include "movi_kernels.hpp"
 #include "movi_expand_host.hpp"
+#include "movi_pack_host.hpp"
 #include "movi_build.hpp"
 
 #include <algorithm>
@@ -82,6 +83,9 @@ struct Reader {
 
 }  // namespace
 
+// the calling thread's message, for the entry points that live outside this file (movi_pack_host.cpp)
+int movi::set_last_error(int code, const char *msg) { return fail(code, msg); }
+
 struct movi_index {
     int device = 0;
     movi_index_desc_t desc{};
@@ -136,7 +140,7 @@ struct movi_index {
     LaunchCfg cfg;
     // device staging of the *_host entry points: grow-only, kept across calls (a hipMalloc / hipFree pair per call and
     // buffer cost more than the copies themselves); released by movi_index_destroy or movi_set_option("release_scratch")
-    enum { kBases = 0, kOffs, kErr, kOut, kA, kB, kS, kMask, kTmp, kScratchSlots };   // (kMask: a chunk's reset-mask words; kTmp: the u16 vector of a mask call whose path has no mask output of its own)
+    enum { kBases = 0, kOffs, kErr, kOut, kA, kB, kS, kMask, kTmp, kPacked, kExcPos, kExcByte, kScratchSlots };   // (kMask: a chunk's reset-mask words; kTmp: the u16 vector of a mask call whose path has no mask output of its own; kPacked: 2-bit packed reads on their way to kBases; kExcPos / kExcByte: their call's exception list, the handle's only)
     void *scratch[kScratchSlots] = {};
     size_t scratch_cap[kScratchSlots] = {};
     SegWorkspace seg_ws;             // segment-parallel long reads (launch_pml): device workspace of the handle's own calls
@@ -1347,6 +1351,11 @@ static int ml_device(bool zml, movi_index_t *ix, const uint8_t *d_bases, const u
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(DevStats), s));
+    // (under a capture the counters are cleared by a kernel as well: a memset NODE behind kernel nodes -- an unpack captured in front of
+    // this call -- was seen to replay with a stale pattern; an uncaptured call makes the HIP calls it always made)
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
+    if (capturing == hipStreamCaptureStatusActive) HIP_TRY(launch_stats_reset(d_stats, s));
     if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
     // the first PML query on a handle builds its derived tables -- unless movi_index_prepare did (--logs runs on the first
     // kernel, which uses none of them; tables_ready: the caller has asked already, once per call)
@@ -1582,6 +1591,34 @@ hipError_t grow(void **p, size_t *cap, size_t bytes) {
     return hipSuccess;
 }
 
+// Where a *_host call's bases come from: the caller's ASCII bytes (h_bases, indexed by offsets[]), or reads packed two bits per base
+// plus their exception list (include/movi_hip.h): those go up as they are, a quarter of the bytes, and every chunk is unpacked on the
+// device into the staging the ASCII bytes would have been copied to.  The ASCII form makes exactly the HIP calls it always made.
+struct ReadSource {
+    const uint8_t *ascii = nullptr;
+    bool two_bit = false;
+    const uint8_t *packed = nullptr;
+    const uint64_t *exc_pos = nullptr;
+    const uint8_t *exc_byte = nullptr;
+    uint64_t n_exc = 0;
+    ReadSource(const uint8_t *h_bases) : ascii(h_bases) {}
+    ReadSource(const uint8_t *h_packed, const uint64_t *h_exc_pos, const uint8_t *h_exc_byte, uint64_t n)
+        : two_bit(true), packed(h_packed), exc_pos(h_exc_pos), exc_byte(h_exc_byte), n_exc(n) {}
+    // what crosses the link for bases [b0, b0 + nb): where it starts in the caller's buffer and how long it is
+    const uint8_t *up_from(uint64_t b0) const { return two_bit ? packed + (b0 >> 2) : ascii + b0; }
+    size_t up_bytes(uint64_t b0, uint64_t nb) const { return two_bit ? (size_t)(((b0 + nb + 3) >> 2) - (b0 >> 2)) : (size_t)nb; }
+};
+// A chunk of a packed call: d_packed holds the caller's packed bytes from byte b0 >> 2 on; its slice of the exception list (already on the
+// device, the whole call's) is found on the host.  Two kernels on the chunk's stream (movi_walk_pack.hip).
+hipError_t unpack_chunk(const ReadSource &src, const void *d_exc_pos, const void *d_exc_byte, const void *d_packed, uint64_t b0, uint64_t nb,
+                        void *d_bases, hipStream_t s) {
+    const uint64_t *end = src.exc_pos + src.n_exc;
+    const uint64_t *lo = std::lower_bound(src.exc_pos, end, b0), *hi = std::lower_bound(lo, end, b0 + nb);
+    const size_t skip = (size_t)(lo - src.exc_pos);
+    return launch_unpack_reads(static_cast<const uint8_t *>(d_packed), b0 & 3u, nb, static_cast<const uint64_t *>(d_exc_pos) + skip,
+                               static_cast<const uint8_t *>(d_exc_byte) + skip, (uint64_t)(hi - lo), b0, static_cast<uint8_t *>(d_bases), s);
+}
+
 // Where one chunk of a *_host call lives: the stream it runs on, its counters, its device staging (the handle's in the
 // synchronous path, a pipeline slot's in the overlapped one) and, overlapped only, page-locked room for per-read results.
 struct ChunkCtx {
@@ -1718,9 +1755,15 @@ void add_stats(movi_query_stats_t *acc, uint64_t nb, const DevStats &h) {
 //                                                results from the page-locked block to the caller's arrays;
 //   small_bytes                                  page-locked bytes per read that fetch / harvest use.
 template <typename Launch, typename Fetch, typename Harvest>
-int run_chunked(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads,
+int run_chunked(movi_index *ix, const ReadSource &src, const uint64_t *h_offsets, uint64_t n_reads,
                 uint8_t *h_read_err, movi_query_stats_t *stats, Launch launch, Fetch fetch, Harvest, size_t, size_t) {
     if (stats) memset(stats, 0, sizeof(*stats));
+    if (src.two_bit && src.n_exc) {                           // the call's exception list, once
+        HIP_TRY(grow(&ix->scratch[movi_index::kExcPos], &ix->scratch_cap[movi_index::kExcPos], (size_t)src.n_exc * 8));
+        HIP_TRY(grow(&ix->scratch[movi_index::kExcByte], &ix->scratch_cap[movi_index::kExcByte], (size_t)src.n_exc));
+        HIP_TRY(hipMemcpy(ix->scratch[movi_index::kExcPos], src.exc_pos, (size_t)src.n_exc * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ix->scratch[movi_index::kExcByte], src.exc_byte, (size_t)src.n_exc, hipMemcpyHostToDevice));
+    }
     int seg_verdict = -1;
     ChunkCtx ctx;
     ctx.ix = ix;
@@ -1766,7 +1809,13 @@ int run_chunked(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offset
         // slightly SLOWER (31.1 vs 32.8 Gbases/s, log-normal lengths) -- the walk is bound by the
         // memory system, not by lane occupancy, and the dispatcher already refills whole blocks.
         stamp(1);
-        if (nb) HIP_TRY(hipMemcpy(d_bases.p, h_bases + b0, nb, hipMemcpyHostToDevice));
+        if (nb && !src.two_bit) HIP_TRY(hipMemcpy(d_bases.p, src.ascii + b0, nb, hipMemcpyHostToDevice));
+        if (nb && src.two_bit) {                              // a quarter of the bytes go up; the null stream unpacks them ahead of the walk
+            void *d_packed = nullptr;
+            HIP_TRY(ctx.alloc(movi_index::kPacked, src.up_bytes(b0, nb), &d_packed));
+            HIP_TRY(hipMemcpy(d_packed, src.up_from(b0), src.up_bytes(b0, nb), hipMemcpyHostToDevice));
+            HIP_TRY(unpack_chunk(src, ix->scratch[movi_index::kExcPos], ix->scratch[movi_index::kExcByte], d_packed, b0, nb, d_bases.p, nullptr));
+        }
         stamp(2);
         HIP_TRY(hipMemcpy(d_offs.p, rel, (nr + 1) * 8, hipMemcpyHostToDevice));
         stamp(3);
@@ -1896,7 +1945,7 @@ int run_compact(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offset
 // after it -- the next chunk's upload included.  Enqueued that way (the first version) the timeline was strictly serial,
 // chunk after chunk (rocprofv3 --memory-copy-trace), and the call no faster than the synchronous one.
 template <typename Launch, typename Fetch, typename Harvest>
-int run_pipelined(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads,
+int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offsets, uint64_t n_reads,
                   uint8_t *h_read_err, movi_query_stats_t *stats, Launch launch, Fetch fetch, Harvest harvest,
                   size_t small_bytes, size_t mask_word_bytes, bool vector_down) {
     if (stats) memset(stats, 0, sizeof(*stats));
@@ -1937,6 +1986,7 @@ int run_pipelined(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offs
         first = last;
     }
     uint8_t *all = nullptr;                                    // the call's reads in one device buffer (set below, ahead of the loop), or chunk by chunk
+    uint8_t *all_packed = nullptr;                             // packed calls: what went up ahead of the loop, from byte chunks[0].b0 >> 2 of the caller's buffer
     constexpr int S = movi_index::kPipeSlots;
     struct InFlight { int stage = 0; Chunk c{}; } fl[S];       // 0 free, 1 walking (upload + kernel enqueued), 2 coming down
     HostPool::Group grp[S];                                    // host-side work a slot's harvest has handed to the worker pool (it reads the slot's page-locked block)
@@ -2000,9 +2050,11 @@ int run_pipelined(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offs
         }
         fl[k].c = c;
         ChunkCtx ctx = ctx_of(k, c.nr);
-        struct { void *p; } d_bases{}, d_offs{}, d_err{};
+        struct { void *p; } d_bases{}, d_offs{}, d_err{}, d_packed{};
         if (all) d_bases.p = all + (c.b0 - chunks[0].b0);
         else HIP_TRY(ctx.alloc(movi_index::kBases, c.nb, &d_bases.p));
+        if (all_packed) d_packed.p = all_packed + ((c.b0 >> 2) - (chunks[0].b0 >> 2));
+        else if (src.two_bit) HIP_TRY(ctx.alloc(movi_index::kPacked, src.up_bytes(c.b0, c.nb), &d_packed.p));
         HIP_TRY(ctx.alloc(movi_index::kOffs, (c.nr + 1) * 8, &d_offs.p));
         HIP_TRY(ctx.alloc(movi_index::kErr, c.nr, &d_err.p));
         uint64_t *rel = reinterpret_cast<uint64_t *>(sl.h);
@@ -2017,7 +2069,7 @@ int run_pipelined(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offs
         // (the upload stream carries the bases alone, copy behind copy: with the chunk's offsets in between, every chunk left it idle for
         // ~40 us -- a fifth of a 9.4 MB copy; the offsets go up on the chunk's own stream, ahead of its walk: profiles/r06_host_path.txt)
         if (!all) {
-            if (c.nb) HIP_TRY(hipMemcpyAsync(d_bases.p, h_bases + c.b0, c.nb, hipMemcpyHostToDevice, ix->pipe_up));
+            if (c.nb) HIP_TRY(hipMemcpyAsync(src.two_bit ? d_packed.p : d_bases.p, src.up_from(c.b0), src.up_bytes(c.b0, c.nb), hipMemcpyHostToDevice, ix->pipe_up));
             HIP_TRY(hipEventRecord(sl.ev_up, ix->pipe_up));
             HIP_TRY(hipMemcpyAsync(d_offs.p, rel, (c.nr + 1) * 8, hipMemcpyHostToDevice, sl.s));
         } else {
@@ -2025,6 +2077,9 @@ int run_pipelined(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offs
             HIP_TRY(launch_copy_words(static_cast<uint64_t *>(d_offs.p), rel, c.nr + 1, sl.s));
         }
         HIP_TRY(hipStreamWaitEvent(sl.s, all ? ix->pipe_ev[ci] : sl.ev_up, 0));
+        // (packed calls: the chunk's own stream unpacks what has arrived into the place the ASCII copy lands in; the upload stream carries copies alone)
+        if (src.two_bit)
+            HIP_TRY(unpack_chunk(src, ix->scratch[movi_index::kExcPos], ix->scratch[movi_index::kExcByte], d_packed.p, c.b0, c.nb, d_bases.p, sl.s));
         if (int rc = launch(ctx, static_cast<const uint8_t *>(d_bases.p), static_cast<const uint64_t *>(d_offs.p), c.nr, c.nb,
                             static_cast<uint8_t *>(d_err.p)))
             return rc;
@@ -2065,10 +2120,24 @@ int run_pipelined(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offs
     // another, an event behind each, and a chunk's walk waits for its event.  Enqueued chunk by chunk from the loop -- three ahead of the
     // walk being waited for -- the upload stream ran dry two or three times per call (0.1 ms each), and the upload is what bounds the
     // call.  (The chunks' offsets then must not travel by the copy engine: they would queue behind the whole call's reads.)
+    if (src.two_bit && src.n_exc) {                           // the call's exception list, once, ahead of every chunk's bytes on the upload stream
+        hipError_t e = hipSuccess;
+        if (!ix->pipe_up) e = create_upload_stream(&ix->pipe_up);
+        if (e == hipSuccess) e = grow(&ix->scratch[movi_index::kExcPos], &ix->scratch_cap[movi_index::kExcPos], (size_t)src.n_exc * 8);
+        if (e == hipSuccess) e = grow(&ix->scratch[movi_index::kExcByte], &ix->scratch_cap[movi_index::kExcByte], (size_t)src.n_exc);
+        if (e == hipSuccess) e = hipMemcpyAsync(ix->scratch[movi_index::kExcPos], src.exc_pos, (size_t)src.n_exc * 8, hipMemcpyHostToDevice, ix->pipe_up);
+        if (e == hipSuccess) e = hipMemcpyAsync(ix->scratch[movi_index::kExcByte], src.exc_byte, (size_t)src.n_exc, hipMemcpyHostToDevice, ix->pipe_up);
+        if (e != hipSuccess) {
+            if (ix->pipe_up) (void)hipStreamSynchronize(ix->pipe_up);
+            return fail_hip(e, "uploading the exception list");
+        }
+    }
     if (n > 1 && total <= (1ull << 31) && !vector_down) {
         hipError_t e = hipSuccess;
         if (!ix->pipe_up) e = create_upload_stream(&ix->pipe_up);
         if (e == hipSuccess) e = grow(&ix->scratch[movi_index::kBases], &ix->scratch_cap[movi_index::kBases], total);
+        if (e == hipSuccess && src.two_bit)
+            e = grow(&ix->scratch[movi_index::kPacked], &ix->scratch_cap[movi_index::kPacked], src.up_bytes(chunks[0].b0, total));
         while (e == hipSuccess && ix->pipe_ev.size() < n) {
             hipEvent_t ev = nullptr;
             e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
@@ -2076,9 +2145,12 @@ int run_pipelined(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offs
         }
         if (e == hipSuccess) {
             all = static_cast<uint8_t *>(ix->scratch[movi_index::kBases]);
+            if (src.two_bit) all_packed = static_cast<uint8_t *>(ix->scratch[movi_index::kPacked]);
             for (size_t i = 0; i < n && e == hipSuccess; i++) {
                 const Chunk &c = chunks[i];
-                if (c.nb) e = hipMemcpyAsync(all + (c.b0 - chunks[0].b0), h_bases + c.b0, c.nb, hipMemcpyHostToDevice, ix->pipe_up);
+                // (packed: the bytes that cover the chunk; a byte that two chunks share goes up with both, to the same place)
+                if (c.nb) e = hipMemcpyAsync(src.two_bit ? all_packed + ((c.b0 >> 2) - (chunks[0].b0 >> 2)) : all + (c.b0 - chunks[0].b0), src.up_from(c.b0),
+                                             src.up_bytes(c.b0, c.nb), hipMemcpyHostToDevice, ix->pipe_up);
                 if (e == hipSuccess) e = hipEventRecord(ix->pipe_ev[i], ix->pipe_up);
             }
             if (e != hipSuccess) {                            // copies may be in flight: nothing reads the caller's buffers when the call returns
@@ -2120,13 +2192,13 @@ bool worth_overlapping_small_results(const uint64_t *h_offsets, uint64_t n_reads
 }
 
 template <typename Launch, typename Fetch, typename Harvest>
-int run_host(bool overlapped, movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads,
+int run_host(bool overlapped, movi_index *ix, const ReadSource &src, const uint64_t *h_offsets, uint64_t n_reads,
              uint8_t *h_read_err, movi_query_stats_t *stats, Launch launch, Fetch fetch, Harvest harvest,
              size_t small_bytes, size_t mask_word_bytes = 0, bool vector_down = false) {
     movi_query_stats_t local{};
     overlapped = overlapped && ix->host_overlap;
-    int rc = overlapped ? run_pipelined(ix, h_bases, h_offsets, n_reads, h_read_err, &local, launch, fetch, harvest, small_bytes, mask_word_bytes, vector_down)
-                        : run_chunked(ix, h_bases, h_offsets, n_reads, h_read_err, &local, launch, fetch, harvest, small_bytes, mask_word_bytes);
+    int rc = overlapped ? run_pipelined(ix, src, h_offsets, n_reads, h_read_err, &local, launch, fetch, harvest, small_bytes, mask_word_bytes, vector_down)
+                        : run_chunked(ix, src, h_offsets, n_reads, h_read_err, &local, launch, fetch, harvest, small_bytes, mask_word_bytes);
     if (stats) *stats = local;
     if (rc) return rc;
     if (local.errors)
@@ -2233,14 +2305,19 @@ static void deliver_on_stream(void *p) {
     delete a;
 }
 
-static int ml_host(bool zml, movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads,
+static int ml_host(bool zml, movi_index_t *ix, const ReadSource &src, const uint64_t *h_offsets, uint64_t n_reads,
                   uint16_t *h_out_pml, uint8_t *h_read_err, movi_query_stats_t *stats, uint32_t *h_mask_words = nullptr) {
     if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
     if (n_reads == 0) { if (stats) memset(stats, 0, sizeof(*stats)); return MOVI_OK; }
     // h_out_pml == NULL: the walk runs, error bytes and counters come back, the vectors stay on the device and are dropped
     // (`movi query --no-output`: the reference computes and discards)
-    if (!h_offsets || (h_offsets[n_reads] != h_offsets[0] && !h_bases)) return fail(MOVI_ERR_ARG, "NULL host buffer");
+    if (!h_offsets || (h_offsets[n_reads] != h_offsets[0] && !(src.two_bit ? src.packed : src.ascii))) return fail(MOVI_ERR_ARG, "NULL host buffer");
     if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
+    if (src.two_bit) {                                        // the exception list is the caller's too: all of it, before the device is touched
+        if (src.n_exc && (!src.exc_pos || !src.exc_byte)) return fail(MOVI_ERR_ARG, "NULL exception list");
+        if (!exceptions_in_order(src.exc_pos, src.n_exc, h_offsets[0], h_offsets[n_reads]))
+            return fail(MOVI_ERR_ARG, "exception positions are not strictly ascending inside [offsets[0], offsets[n_reads])");
+    }
     HIP_TRY(hipSetDevice(ix->device));
     const uint64_t o0 = h_offsets[0], span = h_offsets[n_reads] - o0;
     // The way down of the u16 vector, chunk by chunk: as it is (2 bytes per base over PCIe, no host work where the caller's vector is
@@ -2353,20 +2430,55 @@ static int ml_host(bool zml, movi_index_t *ix, const uint8_t *h_bases, const uin
         deliver(reinterpret_cast<const uint32_t *>(h_small), first, nr, w.phase, g);
     };
     // masks: only the reads have to be page-locked for the overlapped path (the vector is written by host threads)
-    bool overlapped = span != 0 && is_pinned(h_bases) && (route == kMasks || !h_out_pml || is_pinned(h_out_pml));
+    bool overlapped = span != 0 && is_pinned(src.two_bit ? src.packed : src.ascii) && (route == kMasks || !h_out_pml || is_pinned(h_out_pml));
     // A big call on PAGEABLE buffers (what a std::vector-holding caller passes: INTEGRATION.md's stub): page-lock them for the
     // duration of the call and take the overlapped path.  Registering touched memory runs at hundreds of GB/s (DESIGN.md section
     // 5), so on >= 2^27 bases it is paid back several times over (the synchronous path: 12.4 Gbases/s PCIe-inclusive).
     // "host_autopin" 0 turns it off; anything that fails here falls back to the synchronous path.
     AutoPin pin_bases, pin_out;
     if (!overlapped && autopin_worthwhile(ix, h_offsets, n_reads))
-        overlapped = pin_bases.pin(const_cast<uint8_t *>(h_bases) + h_offsets[0], span) &&
+        overlapped = pin_bases.pin(const_cast<uint8_t *>(src.up_from(o0)), src.up_bytes(o0, span)) &&
                      (route == kMasks || !h_out_pml || pin_out.pin(h_out_pml + h_offsets[0], span * 2));
     if (route == kMixed && !overlapped) route = kMasks;       // (the synchronous path: one way down for the whole call)
     // (vector_down: 2 bytes per base come down by DMA -- the way down bounds such a call, and with every read going up at once beside
     // it the downloads ran 8 % slower: those calls feed their uploads from the loop)
-    return run_host(overlapped, ix, h_bases, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest, 0, route != kVector ? 4 : 0,
+    return run_host(overlapped, ix, src, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest, 0, route != kVector ? 4 : 0,
                     route != kMasks && h_out_pml != nullptr);
+}
+
+// ------------------------------------------------------------- reads packed two bits per base (movi_pack_host.cpp, movi_walk_pack.hip)
+
+int movi_reads_packed_bytes(uint64_t first_base, uint64_t n_bases, uint64_t *bytes) {
+    if (!bytes) return fail(MOVI_ERR_ARG, "bytes is NULL");
+    if (first_base + n_bases < first_base || first_base + n_bases + 3 < 3) return fail(MOVI_ERR_ARG, "first_base + n_bases overflows");
+    *bytes = packed_bytes(first_base, n_bases);
+    return MOVI_OK;
+}
+
+// (movi_reads_pack_host / movi_reads_unpack_host: pure host code, exported by movi_pack_host.cpp itself; their messages come through set_last_error)
+
+// Two kernels on `stream` and nothing else: no allocation, no wait, capturable.  The exception list lives on the device, so it is
+// not validated here: the kernel leaves a position outside the range alone.
+int movi_reads_unpack_device(int device, const uint8_t *d_packed, uint64_t first_base, uint64_t n_bases, const uint64_t *d_exc_pos,
+                             const uint8_t *d_exc_byte, uint64_t n_exc, uint8_t *d_bases_out, void *stream) {
+    if ((n_bases && (!d_packed || !d_bases_out)) || (n_exc && (!d_exc_pos || !d_exc_byte))) return fail(MOVI_ERR_ARG, "NULL device buffer");
+    if (first_base + n_bases < first_base || first_base + n_bases + 3 < 3) return fail(MOVI_ERR_ARG, "first_base + n_bases overflows");
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_unpack_reads(d_packed, first_base, n_bases, d_exc_pos, d_exc_byte, n_exc, first_base, d_bases_out, static_cast<hipStream_t>(stream)));
+    return MOVI_OK;
+}
+
+int movi_pml_packed_host(movi_index_t *ix, const uint8_t *h_packed, const uint64_t *h_exc_pos, const uint8_t *h_exc_byte, uint64_t n_exc,
+                         const uint64_t *h_offsets, uint64_t n_reads, uint16_t *h_out_pml, uint8_t *h_read_err, movi_query_stats_t *stats) {
+    return ml_host(false, ix, ReadSource(h_packed, h_exc_pos, h_exc_byte, n_exc), h_offsets, n_reads, h_out_pml, h_read_err, stats);
+}
+
+int movi_pml_mask_packed_host(movi_index_t *ix, const uint8_t *h_packed, const uint64_t *h_exc_pos, const uint8_t *h_exc_byte, uint64_t n_exc,
+                              const uint64_t *h_offsets, uint64_t n_reads, uint32_t *h_mask_words, uint8_t *h_read_err,
+                              movi_query_stats_t *stats) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (n_reads && !h_mask_words) return fail(MOVI_ERR_ARG, "NULL host buffer");
+    return ml_host(false, ix, ReadSource(h_packed, h_exc_pos, h_exc_byte, n_exc), h_offsets, n_reads, nullptr, h_read_err, stats, h_mask_words);
 }
 
 int movi_pml_mask_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads,
@@ -2620,6 +2732,7 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
         // the walk kernels live in translation units of their own: their code objects are loaded here, not by the first walk
         (void)(ix->dev.idx32 ? preload_walk_u32() : preload_walk_u64());
         (void)(ix->dev.idx32 ? preload_walkseg_u32() : preload_walkseg_u64());
+        (void)preload_pack();                                         // (movi_reads_unpack_device in front of a captured walk)
         (void)hipGetLastError();
         // movi_pml_device's mask words for a default batch (a bigger "reserve_device_masks" stays): its first call allocates nothing.
         // No room is no failure -- an uncaptured call grows them, a captured one takes the packer route

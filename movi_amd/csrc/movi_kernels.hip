@@ -1036,9 +1036,16 @@ bool pml_mask_needs_tmp(const DevIndex &ix, const LaunchCfg &cfg, uint64_t n_rea
 // cleared already: captured into a graph (memset, walk, walk), that call was observed to report counters that did not start from zero
 // from the graph's second replay on, while (memset, walk) replayed clean (profiles/park_lanes.txt, section 4; the cause is not known).
 __global__ void park_reset_kernel(unsigned long long *count, DevStats *stats) {
-    if (threadIdx.x == 0) *count = 0ull;
+    if (count && threadIdx.x == 0) *count = 0ull;
     unsigned long long *w = reinterpret_cast<unsigned long long *>(stats);
     if (stats && threadIdx.x < sizeof(DevStats) / sizeof(unsigned long long)) w[threadIdx.x] = 0ull;
+}
+// The call's counters alone, by the same kernel: what a PML / ZML call that is being CAPTURED puts behind its memset of them.  A memset
+// node that follows kernel nodes in a graph -- movi_reads_unpack_device captured in front of movi_pml_device -- was observed to fill the
+// counters with the 16 bytes that begin the preceding kernel's arguments instead of zeros (the cause is not known, as above).
+hipError_t launch_stats_reset(DevStats *d_stats, hipStream_t stream) {
+    hipLaunchKernelGGL(park_reset_kernel, dim3(1), dim3(64), 0, stream, static_cast<unsigned long long *>(nullptr), d_stats);
+    return hipGetLastError();
 }
 
 hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets,

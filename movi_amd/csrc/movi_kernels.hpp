@@ -280,6 +280,13 @@ hipError_t launch_pml_expand(const uint32_t *d_words, const uint64_t *d_offsets,
 // n 8-byte words from page-locked host memory (or anywhere the device can read) to the device by a kernel on `stream`: small blocks that
 // must not queue behind bulk transfers on the copy engine (run_pipelined's per-chunk offsets)
 hipError_t launch_copy_words(uint64_t *d_dst, const uint64_t *src, uint64_t n, hipStream_t stream);
+// Reads packed two bits per base (include/movi_hip.h) -> one byte per base (movi_walk_pack.hip): d_out[j] = base first_base + j, whose code is
+// bits 2 * ((first_base + j) & 3) of d_packed[(first_base + j) >> 2]; exception i then puts d_exc_byte[i] at d_out[d_exc_pos[i] - exc_origin]
+// (positions outside [exc_origin, exc_origin + n_bases) are left alone).  Two kernels on `stream`, nothing else: allocates nothing, capturable.
+hipError_t launch_unpack_reads(const uint8_t *d_packed, uint64_t first_base, uint64_t n_bases, const uint64_t *d_exc_pos,
+                               const uint8_t *d_exc_byte, uint64_t n_exc, uint64_t exc_origin, uint8_t *d_out, hipStream_t stream);
+hipError_t launch_stats_reset(DevStats *d_stats, hipStream_t stream);   // a call's counters zeroed by a kernel (calls under a stream capture: movi_kernels.hip says why)
+hipError_t preload_pack();                // load the translation unit's code object now (movi_index_prepare)
 hipError_t launch_pml_to_mask(const uint16_t *d_pml, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t phase,
                               uint32_t *d_words, hipStream_t stream);
 

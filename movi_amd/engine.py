@@ -152,6 +152,46 @@ def masks_of_pml(pml, offs, first_base=0):
     return words, valid
 
 
+def packed_bytes(first_base, n_bases):
+    """movi_reads_packed_bytes: bytes of a 2-bit packed buffer that holds bases [0, first_base + n_bases)."""
+    n = C.c_uint64(0)
+    check(lib().movi_reads_packed_bytes(int(first_base), int(n_bases), C.byref(n)))
+    return int(n.value)
+
+
+def pack_reads(bases, first_base=0, threads=0, packed=None, exc_cap=None):
+    """movi_reads_pack_host: uint8 bases (bases[j] = base first_base + j) -> (packed uint8, exc_pos uint64, exc_byte uint8), the
+    2-bit format of include/movi_hip.h: four bases per byte at their ABSOLUTE position, every byte that is not upper-case ACGT in the
+    sparse exception list.  `packed`: a buffer to append to (e.g. pinned_empty(packed_bytes(...), np.uint8)); a fresh one otherwise.
+    `exc_cap`: room for the exceptions (default: a first guess, grown once if it does not fit)."""
+    bases = np.ascontiguousarray(np.frombuffer(bases, np.uint8) if isinstance(bases, (bytes, bytearray)) else bases, np.uint8)
+    if packed is None:
+        packed = np.zeros(packed_bytes(first_base, bases.size), np.uint8)
+    assert packed.dtype == np.uint8 and packed.size >= packed_bytes(first_base, bases.size) and packed.flags.c_contiguous
+    cap = int(exc_cap) if exc_cap is not None else max(16, bases.size // 64)
+    while True:
+        pos, byte, n = np.zeros(max(cap, 1), np.uint64), np.zeros(max(cap, 1), np.uint8), C.c_uint64(0)
+        rc = lib().movi_reads_pack_host(bases.ctypes.data, int(first_base), bases.size, packed.ctypes.data, pos.ctypes.data,
+                                        byte.ctypes.data, cap, C.byref(n), int(threads))
+        if rc == -1 and n.value > cap and exc_cap is None:   # (MOVI_ERR_ARG with the needed count: once more with that much room)
+            cap = int(n.value)
+            continue
+        check(rc)
+        return packed, pos[:n.value], byte[:n.value]
+
+
+def unpack_reads(packed, first_base, n_bases, exc_pos=None, exc_byte=None, threads=0):
+    """movi_reads_unpack_host: the exact inverse of pack_reads, on the host -> uint8[n_bases]."""
+    packed = np.ascontiguousarray(packed, np.uint8)
+    pos = np.ascontiguousarray(exc_pos if exc_pos is not None else [], np.uint64)
+    byte = np.ascontiguousarray(exc_byte if exc_byte is not None else [], np.uint8)
+    assert pos.size == byte.size
+    out = np.zeros(int(n_bases), np.uint8)
+    check(lib().movi_reads_unpack_host(packed.ctypes.data, int(first_base), int(n_bases), pos.ctypes.data, byte.ctypes.data, pos.size,
+                                       out.ctypes.data, int(threads)))
+    return out
+
+
 class QueryStats:
     def __init__(self, c):
         self.bases = int(c.bases)
@@ -271,6 +311,42 @@ class MoveIndex:
         st = QueryStatsC()
         rc = lib().movi_pml_mask_host(self._h, bases.ctypes.data, offs.ctypes.data, n, words.ctypes.data, err.ctypes.data,
                                       C.byref(st))
+        if want_err:
+            return words, QueryStats(st), err[:n], rc
+        check(rc)
+        return words, QueryStats(st)
+
+    def query_pml_packed2(self, packed, exc_pos, exc_byte, offs, want_err=False, out=None):
+        """movi_pml_packed_host: query_pml_packed on reads packed TWO BITS per base (pack_reads; "packed" in the neighbouring
+        methods' names means "concatenated") -> (u16 PMLs in emission order, QueryStats[, err, rc])."""
+        packed = np.ascontiguousarray(packed, np.uint8)
+        pos, byte = np.ascontiguousarray(exc_pos, np.uint64), np.ascontiguousarray(exc_byte, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        n = offs.size - 1
+        if out is None:
+            out = np.zeros(int(offs[-1]), np.uint16)
+        assert out.dtype == np.uint16 and out.size >= int(offs[-1]) and out.flags.c_contiguous and pos.size == byte.size
+        err = np.zeros(max(n, 1), np.uint8)
+        st = QueryStatsC()
+        rc = lib().movi_pml_packed_host(self._h, packed.ctypes.data, pos.ctypes.data, byte.ctypes.data, pos.size, offs.ctypes.data, n,
+                                        out.ctypes.data, err.ctypes.data, C.byref(st))
+        if want_err:
+            return out, QueryStats(st), err[:n], rc
+        check(rc)
+        return out, QueryStats(st)
+
+    def query_pml_mask_packed2(self, packed, exc_pos, exc_byte, offs, want_err=False):
+        """movi_pml_mask_packed_host: query_pml_mask_packed on reads packed two bits per base -> (u32 words, QueryStats[, err, rc])."""
+        packed = np.ascontiguousarray(packed, np.uint8)
+        pos, byte = np.ascontiguousarray(exc_pos, np.uint64), np.ascontiguousarray(exc_byte, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        n = offs.size - 1
+        assert pos.size == byte.size
+        words = np.zeros(mask_words(n, int(offs[-1] - offs[0])), np.uint32)
+        err = np.zeros(max(n, 1), np.uint8)
+        st = QueryStatsC()
+        rc = lib().movi_pml_mask_packed_host(self._h, packed.ctypes.data, pos.ctypes.data, byte.ctypes.data, pos.size, offs.ctypes.data,
+                                             n, words.ctypes.data, err.ctypes.data, C.byref(st))
         if want_err:
             return words, QueryStats(st), err[:n], rc
         check(rc)
@@ -537,6 +613,12 @@ class MoveIndex:
                                     C.c_void_p(d_out), C.c_void_p(d_err) if d_err else None,
                                     C.c_void_p(d_order) if d_order else None,
                                     C.c_void_p(stream) if stream else None))
+
+    def unpack_reads_device(self, d_packed, first_base, n_bases, d_out, d_exc_pos=0, d_exc_byte=0, n_exc=0, stream=0):
+        """movi_reads_unpack_device on this handle's GPU: 2-bit packed reads -> one byte per base at d_out, for any *_device query."""
+        check(lib().movi_reads_unpack_device(self.device, C.c_void_p(d_packed), int(first_base), int(n_bases),
+                                             C.c_void_p(d_exc_pos) if d_exc_pos else None, C.c_void_p(d_exc_byte) if d_exc_byte else None,
+                                             int(n_exc), C.c_void_p(d_out), C.c_void_p(stream) if stream else None))
 
     def pml_mask_device(self, d_bases, d_offs, n_reads, n_bases, d_words, first_base=0, d_err=0, stream=0, d_order=0):
         check(lib().movi_pml_mask_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offs), n_reads, n_bases, int(first_base),
