@@ -94,20 +94,18 @@ struct movi_index {
     std::vector<uint64_t> sep_vals_host;         //   their ThresholdsRow (4 x u16 in one u64)
     std::vector<uint16_t> sep_thr_raw;           //   the file's two tables, kept for movi_index_get_desc-style round trips
     std::vector<uint64_t> sep_map_raw;
-    uint64_t *d_sep_rows = nullptr;
-    uint64_t *d_sep_vals = nullptr;
+    DevPtr<uint64_t> d_sep_rows, d_sep_vals;
     std::vector<uint64_t> tally_host;            // mode 7: tally_ids widened to u64, [alphabet][n_tally]
-    uint64_t *d_tally = nullptr;
-    uint8_t *d_rows = nullptr;
-    bool owns_rows = false;
+    DevPtr<uint64_t> d_tally;
+    DevPtr<uint8_t> d_rows;          // the resident table: the handle's, or borrowed (caller rows adopted by movi_index_create_from_device_rows)
     size_t rows_bytes = 0;
-    uint8_t *d_code_of = nullptr;
-    uint32_t *d_id_blocks = nullptr;
-    uint64_t *d_ckpt = nullptr;      // built lazily by the first count query
-    uint4 *d_kmer = nullptr;         // top-of-walk table ("kmer_k" option), 16 << 2K bytes
+    DevPtr<uint8_t> d_code_of;
+    DevPtr<uint32_t> d_id_blocks;
+    DevPtr<uint64_t> d_ckpt;         // built lazily by the first count query
+    DevPtr<uint4> d_kmer;            // top-of-walk table ("kmer_k" option), 16 << 2K bytes
     int kmer_auto = 12;              // K of the table the first PML query builds by itself (0 = none: "kmer_k" 0)
-    uint8_t *d_rows2 = nullptr;      // look-ahead rows ("ahead_rows" option), 16 bytes per row
-    uint8_t *d_rows3 = nullptr;      // deep rows ("deep_rows" option), 21.33 bytes per row: what the PML walk runs on where the policy builds them
+    DevPtr<uint8_t> d_rows2;         // look-ahead rows ("ahead_rows" option), 16 bytes per row
+    DevPtr<uint8_t> d_rows3;         // deep rows ("deep_rows" option), 21.33 bytes per row: what the PML walk runs on where the policy builds them
     int deep_auto = 1;               // 1: the first PML query builds them for tables of at most kDeepAutoRows rows (instead of the look-ahead rows)
     double ahead_no_ff = 0.0;        // share of the table's positions that arrive at their LF target without a fast-forward (build_ahead)
     bool ahead_tallied = false;
@@ -115,22 +113,21 @@ struct movi_index {
     int ahead_auto = 1;              // 1: the first PML query builds them when the device has room for them (ahead_wanted)
     int ahead_retry_in = 0;          // the copy was declined for lack of device memory: calls until the device is asked again (not every call)
     bool prepared = false;           // movi_index_prepare has run: query calls build and allocate nothing any more (a declined copy is retried by movi_index_prepare only)
-    uint4 *d_ftab = nullptr;         // the count query's interval table ("ftab_k" option), 16 << 2K bytes
+    DevPtr<uint4> d_ftab;            // the count query's interval table ("ftab_k" option), 16 << 2K bytes
     int ftab_auto = 12;              // K of the table the first count query builds by itself (0 = none)
-    DevStats *d_stats = nullptr;
+    DevPtr<DevStats> d_stats;
     // locate: the attached sampled suffix array (movi_ssa_build / movi_ssa_load) and the locate rows derived from the table for its rate
-    uint4 *d_loc = nullptr;          // 16 bytes per row (movi_sa.hpp)
-    uint64_t *d_samples = nullptr;   // length / sa_rate + 1 entries
+    DevPtr<uint4> d_loc;             // 16 bytes per row (movi_sa.hpp)
+    DevPtr<uint64_t> d_samples;      // length / sa_rate + 1 entries
     uint64_t sa_rate = 0;            // 0 = no sampled suffix array attached
     // Movi Color: the attached colour tables (movi_color_build / movi_color_load), on the host as the file holds them and on the device
     std::vector<uint16_t> color_flat;            // flat_colors
     std::vector<uint64_t> color_inds;            // doc_set_flat_inds, r entries (empty = no tables attached)
     std::vector<uint32_t> color_taxa;            // to_taxon_id of the build (empty after a load)
     uint32_t color_species = 0;
-    uint16_t *d_color_flat = nullptr;
-    uint64_t *d_color_inds = nullptr;
-    uint32_t *d_color_scratch = nullptr;         // the counters of movi_multi_classify_device calls that ask for no counter rows
-    size_t color_scratch_cap = 0;
+    DevPtr<uint16_t> d_color_flat;
+    DevPtr<uint64_t> d_color_inds;
+    DevBuf color_scratch;                        // the counters of movi_multi_classify_device calls that ask for no counter rows
     uint64_t color_scratch_bytes = 256ull << 20; // "color_scratch_bytes": what movi_index_prepare(MOVI_PREPARE_COLOR) reserves
     uint64_t color_chunk_keys = 0;               // "color_chunk_keys": BWT positions per chunk of the builder (0 = by the device's free memory)
     uint32_t color_chunks = 0;                   // what the last build took
@@ -141,11 +138,10 @@ struct movi_index {
     // device staging of the *_host entry points: grow-only, kept across calls (a hipMalloc / hipFree pair per call and
     // buffer cost more than the copies themselves); released by movi_index_destroy or movi_set_option("release_scratch")
     enum { kBases = 0, kOffs, kErr, kOut, kA, kB, kS, kMask, kTmp, kPacked, kExcPos, kExcByte, kScratchSlots };   // (kMask: a chunk's reset-mask words; kTmp: the u16 vector of a mask call whose path has no mask output of its own; kPacked: 2-bit packed reads on their way to kBases; kExcPos / kExcByte: their call's exception list, the handle's only)
-    void *scratch[kScratchSlots] = {};
-    size_t scratch_cap[kScratchSlots] = {};
+    DevBuf scratch[kScratchSlots];
     SegWorkspace seg_ws;             // segment-parallel long reads (launch_pml): device workspace of the handle's own calls
-    uint64_t *h_rel = nullptr;       // synchronous path: a chunk's relative offsets, page-locked and kept (a fresh 2 MB vector per call was page
-    size_t h_rel_cap = 0;            // faults + a staged copy: ~0.3 ms of a 2 ms call); entries
+    PinnedBuf h_rel;                 // synchronous path: a chunk's relative offsets (u64 entries), page-locked and kept (a fresh 2 MB vector per
+                                     // call was page faults + a staged copy: ~0.3 ms of a 2 ms call)
     // the overlapped form of the *_host entry points (page-locked caller buffers, movi_host_alloc): kPipeSlots chunks in
     // flight, each on its own stream with its own device staging, counters and a small page-locked block for what
     // travels with a chunk (relative offsets up; error bytes, per-read results and counters down)
@@ -153,12 +149,22 @@ struct movi_index {
         hipStream_t s = nullptr;
         hipEvent_t ev = nullptr;                 // the slot's walk has finished
         hipEvent_t ev_up = nullptr;              // the slot's chunk has arrived
-        void *d[kScratchSlots] = {};
-        size_t cap[kScratchSlots] = {};
-        DevStats *d_stats = nullptr;
+        DevBuf d[kScratchSlots];
+        DevPtr<DevStats> d_stats;
         SegWorkspace seg_ws;                     // segment-parallel long reads: this slot's device workspace
-        uint8_t *h = nullptr;
-        size_t h_cap = 0;
+        PinnedBuf h;
+        void release() {                         // the slot's stream drains, then what it may touch goes
+            if (s) (void)hipStreamSynchronize(s);
+            seg_ws.release();
+            for (DevBuf &b : d) b.release();
+            d_stats.reset();
+            h.release();
+            if (ev) (void)hipEventDestroy(ev);
+            if (ev_up) (void)hipEventDestroy(ev_up);
+            if (s) (void)hipStreamDestroy(s);
+            ev = ev_up = nullptr;
+            s = nullptr;
+        }
     };
     enum { kPipeSlots = 6, kPipeAhead = 3 };   // slots; chunks going up or being walked while one comes down (2: -14 %, 4: the same)
     PipeSlot pipe[kPipeSlots];
@@ -181,16 +187,17 @@ struct movi_index {
     // movi_pml_device's reset-mask words (its default route for batches of short reads), apart from the *_host staging: reserved by
     // movi_index_prepare(MOVI_PREPARE_PML) for kPrepareMaskBases bases in kPrepareMaskReads reads, by "reserve_device_masks", and grown
     // by a bigger call outside a stream capture.  A graph captured over a call keeps the buffer's address, so a buffer a captured call
-    // has used is never freed by a growth: it is retired and kept until release_scratch / movi_index_destroy.
-    void *dmask = nullptr;
-    size_t dmask_cap = 0;
-    bool dmask_in_graph = false;
-    std::vector<std::pair<void *, size_t>> dmask_retired;
+    // has used is never freed by a growth: it is retired and kept until release_scratch / movi_index_destroy (GraphSafeBuf).
+    GraphDevBuf::Retired graph_retired;
+    GraphDevBuf dmask{&graph_retired};
     // the park queue of the mask walk's parked lanes (DevIndex::park_q; "park_lanes"): records of kParkRecBytes, reserved with the mask words
-    // and grown, retired and freed by the same rules (a retired queue goes on dmask_retired)
-    void *dpark = nullptr;
-    size_t dpark_cap = 0;
-    bool dpark_in_graph = false;
+    // and grown, retired and freed by the same rules (a retired queue goes on the same list)
+    GraphDevBuf dpark{&graph_retired};
+private:
+    // The members free device memory: the handle dies under its own device (movi_index_replicate makes handles on several devices
+    // from one thread), which movi_index_destroy sets -- the only way out.
+    ~movi_index() = default;
+    friend int movi_index_destroy(movi_index_t *ix);
 };
 
 static void release_scratch(movi_index *ix);
@@ -198,40 +205,12 @@ static const char *const kNoSsa = "no sampled suffix array is attached to this i
                                   "load ssa.movi with movi_ssa_load";
 static const char *const kNoColor = "no colour tables are attached to this index: build them with movi_color_build (`movi color`) or load "
                                     "doc_sets_flat.bin with movi_color_load";
-namespace { hipError_t grow(void **p, size_t *cap, size_t bytes); }
 // The counters of one chunk of reads of movi_multi_classify_device: at least one read's row
-static hipError_t grow_color_scratch(movi_index *ix) {
-    const size_t want = std::max<size_t>((size_t)ix->color_scratch_bytes, (size_t)ix->color_species * 4);
-    if (ix->color_scratch_cap >= want) return hipSuccess;
-    void *p = ix->d_color_scratch;
-    const hipError_t e = grow(&p, &ix->color_scratch_cap, want);
-    ix->d_color_scratch = static_cast<uint32_t *>(p);
-    return e;
+static hipError_t reserve_color_scratch(movi_index *ix) {
+    return grow(ix->color_scratch, std::max<size_t>((size_t)ix->color_scratch_bytes, (size_t)ix->color_species * 4));
 }
 constexpr uint64_t kPrepareMaskBases = 1ull << 28;   // movi_index_prepare's reservation of movi_pml_device's mask words (1 M x 150 bp fits)
 constexpr uint64_t kPrepareMaskReads = 1ull << 22;
-// movi_pml_device's mask words for `bytes`: grow-only; a buffer that a captured call used is retired, not freed
-static hipError_t grow_dmask(movi_index *ix, size_t bytes) {
-    if (ix->dmask_cap >= std::max<size_t>(bytes, 8)) return hipSuccess;
-    if (ix->dmask && ix->dmask_in_graph) {
-        ix->dmask_retired.emplace_back(ix->dmask, ix->dmask_cap);
-        ix->dmask = nullptr;
-        ix->dmask_cap = 0;
-    }
-    ix->dmask_in_graph = false;
-    return grow(&ix->dmask, &ix->dmask_cap, bytes);
-}
-// ... and the park queue, likewise
-static hipError_t grow_dpark(movi_index *ix, size_t bytes) {
-    if (ix->dpark_cap >= std::max<size_t>(bytes, 8)) return hipSuccess;
-    if (ix->dpark && ix->dpark_in_graph) {
-        ix->dmask_retired.emplace_back(ix->dpark, ix->dpark_cap);
-        ix->dpark = nullptr;
-        ix->dpark_cap = 0;
-    }
-    ix->dpark_in_graph = false;
-    return grow(&ix->dpark, &ix->dpark_cap, bytes);
-}
 // the lanes a wavefront of a call on this handle may park: what "park_lanes" asks for, or what plan_pml's own rule can pick
 static int park_lanes_wanted(const movi_index *ix) { return ix->cfg.park_lanes > 0 ? ix->cfg.park_lanes : (ix->cfg.park_lanes < 0 ? kParkLanesAuto : 0); }
 // bytes of the queue of a call of n_reads reads: one record per lane of the second launch's grid, as launch_pml counts them for any block
@@ -256,11 +235,11 @@ static void lend_park_queue(movi_index *ix, uint64_t n_reads, hipStream_t s, Mas
     if (lanes <= 0) return;
     const size_t need = park_queue_bytes(n_reads, lanes);
     const bool capturing = stream_capturing(s);
-    if (!capturing && grow_dpark(ix, need) != hipSuccess) { (void)hipGetLastError(); return; }
-    if (need > ix->dpark_cap) return;
-    if (capturing) ix->dpark_in_graph = true;
-    m.park_q = ix->dpark;
-    m.park_cap = (ix->dpark_cap - kParkHeadBytes) / kParkRecBytes;
+    if (!capturing && grow(ix->dpark, need) != hipSuccess) { (void)hipGetLastError(); return; }
+    if (need > ix->dpark.cap()) return;
+    if (capturing) ix->dpark.mark_in_graph();
+    m.park_q = ix->dpark.ptr();
+    m.park_cap = (ix->dpark.cap() - kParkHeadBytes) / kParkRecBytes;
 }
 // The upload stream of the overlapped host paths.  Streams of one priority share a handful of hardware queues, and a chunk's stream that
 // landed on the upload stream's queue had its walk queued behind the copies' completion packets (every sixth chunk waited for uploads that
@@ -272,7 +251,7 @@ static hipError_t create_upload_stream(hipStream_t *s) {
         if (hipStreamCreateWithPriority(s, hipStreamNonBlocking, greatest) == hipSuccess) return hipSuccess;
     (void)hipGetLastError();
     return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
-}   // grow-only device staging (defined with the host paths)
+}
 
 extern "C" {
 
@@ -391,37 +370,37 @@ int movi_index_parse(const void *h_image, size_t image_bytes, movi_index_desc_t 
 
 static int finish_create(movi_index *ix) {
     const movi_index_desc_t &d = ix->desc;
-    HIP_TRY(hipMalloc(&ix->d_code_of, 256));
-    HIP_TRY(hipMemcpy(ix->d_code_of, d.code_of, 256, hipMemcpyHostToDevice));
+    HIP_TRY(dev_alloc(ix->d_code_of, 256));
+    HIP_TRY(hipMemcpy(ix->d_code_of.get(), d.code_of, 256, hipMemcpyHostToDevice));
     if (mode_blocked(d.mode)) {
         const size_t nb = (size_t)d.n_blocks * d.alphabet_size;
         if (nb == 0 || ix->id_blocks_host.size() != nb) return fail(MOVI_ERR_ARG, "the blocked modes need id_blocks");
-        HIP_TRY(hipMalloc(&ix->d_id_blocks, nb * 4));
-        HIP_TRY(hipMemcpy(ix->d_id_blocks, ix->id_blocks_host.data(), nb * 4, hipMemcpyHostToDevice));
+        HIP_TRY(dev_alloc(ix->d_id_blocks, nb * 4));
+        HIP_TRY(hipMemcpy(ix->d_id_blocks.get(), ix->id_blocks_host.data(), nb * 4, hipMemcpyHostToDevice));
     }
     const bool sep = d.alphabet_size == 5;
     if (sep && !ix->sep_rows_host.empty()) {
         const size_t ns = ix->sep_rows_host.size();
-        HIP_TRY(hipMalloc(&ix->d_sep_rows, ns * 8));
-        HIP_TRY(hipMalloc(&ix->d_sep_vals, ns * 8));
-        HIP_TRY(hipMemcpy(ix->d_sep_rows, ix->sep_rows_host.data(), ns * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ix->d_sep_vals, ix->sep_vals_host.data(), ns * 8, hipMemcpyHostToDevice));
+        HIP_TRY(dev_alloc(ix->d_sep_rows, ns * 8));
+        HIP_TRY(dev_alloc(ix->d_sep_vals, ns * 8));
+        HIP_TRY(hipMemcpy(ix->d_sep_rows.get(), ix->sep_rows_host.data(), ns * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ix->d_sep_vals.get(), ix->sep_vals_host.data(), ns * 8, hipMemcpyHostToDevice));
     }
     if (mode_sampled(d.mode)) {
         if (ix->tally_host.empty()) return fail(MOVI_ERR_ARG, "the sampled modes need tally_ids");
-        HIP_TRY(hipMalloc(&ix->d_tally, ix->tally_host.size() * 8));
-        HIP_TRY(hipMemcpy(ix->d_tally, ix->tally_host.data(), ix->tally_host.size() * 8, hipMemcpyHostToDevice));
+        HIP_TRY(dev_alloc(ix->d_tally, ix->tally_host.size() * 8));
+        HIP_TRY(hipMemcpy(ix->d_tally.get(), ix->tally_host.data(), ix->tally_host.size() * 8, hipMemcpyHostToDevice));
     }
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, ix->device));
     ix->cfg.num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     if (const char *pl = getenv("MOVI_PAIR_LOADS")) ix->cfg.pair_loads = atoi(pl) > 0 ? 1 : (atoi(pl) < 0 ? -1 : 0);   // A/B and test hook: every handle's default for "pair_loads"
-    HIP_TRY(hipMalloc(&ix->d_stats, sizeof(DevStats)));
-    HIP_TRY(hipMemset(ix->d_stats, 0, sizeof(DevStats)));
+    HIP_TRY(dev_alloc(ix->d_stats, sizeof(DevStats)));
+    HIP_TRY(hipMemset(ix->d_stats.get(), 0, sizeof(DevStats)));
     DevIndex &v = ix->dev;
-    v.rows = ix->d_rows;
-    v.id_blocks = ix->d_id_blocks;
-    v.code_of = ix->d_code_of;
+    v.rows = ix->d_rows.get();
+    v.id_blocks = ix->d_id_blocks.get();
+    v.code_of = ix->d_code_of.get();
     v.row_start_ckpt = nullptr;
     v.r = d.r;
     v.end_bwt_idx = d.end_bwt_idx;
@@ -435,9 +414,9 @@ static int finish_create(movi_index *ix) {
     v.sigma = d.alphabet_size;
     v.sep = sep ? 1u : 0u;
     v.n_sep = (uint32_t)ix->sep_rows_host.size();
-    v.sep_rows = ix->d_sep_rows;
-    v.sep_vals = reinterpret_cast<const uint2 *>(ix->d_sep_vals);
-    v.tally = ix->d_tally;
+    v.sep_rows = ix->d_sep_rows.get();
+    v.sep_vals = reinterpret_cast<const uint2 *>(ix->d_sep_vals.get());
+    v.tally = ix->d_tally.get();
     v.tally_len = d.n_tally;
     v.tally_cp = d.tally_checkpoints ? d.tally_checkpoints : 1;
     v.idx32 = d.r < 0xFFFFFFFFull ? 1u : 0u;
@@ -456,18 +435,15 @@ static int finish_create(movi_index *ix) {
     ix->kmode = (int)d.mode;
     if (d.mode != MOVI_MODE_REGULAR_THRESHOLDS && d.mode != MOVI_MODE_REGULAR) {
         const bool blocked = mode_blocked(d.mode);
-        uint8_t *rows6 = nullptr;
-        HIP_TRY(hipMalloc(&rows6, (size_t)d.r * 8 + 16));
-        hipError_t e = hipMemset(rows6, 0, (size_t)d.r * 8 + 16);
-        if (e == hipSuccess) e = blocked ? expand_blocked_rows((int)d.mode, v, rows6, nullptr) : expand_sampled_rows((int)d.mode, v, rows6, nullptr);
+        DevPtr<uint8_t> rows6;
+        HIP_TRY(dev_alloc(rows6, (size_t)d.r * 8 + 16));
+        hipError_t e = hipMemset(rows6.get(), 0, (size_t)d.r * 8 + 16);
+        if (e == hipSuccess) e = blocked ? expand_blocked_rows((int)d.mode, v, rows6.get(), nullptr) : expand_sampled_rows((int)d.mode, v, rows6.get(), nullptr);
         if (e == hipSuccess) e = hipDeviceSynchronize();
-        if (e != hipSuccess) { (void)hipFree(rows6); return fail_hip(e, "expanding the rows to the resident layout"); }
-        if (ix->owns_rows && ix->d_rows) (void)hipFree(ix->d_rows);       // the file-format copy (an adopted buffer stays the caller's)
-        if (ix->d_tally) (void)hipFree(ix->d_tally);                      // sampled: only get_id needed the checkpoints
-        ix->d_tally = nullptr;
-        ix->d_rows = rows6;
-        ix->owns_rows = true;
-        v.rows = rows6;
+        if (e != hipSuccess) return fail_hip(e, "expanding the rows to the resident layout");
+        ix->d_rows = std::move(rows6);                                    // the file-format copy goes (an adopted buffer stays the caller's)
+        ix->d_tally.reset();                                              // sampled: only get_id needed the checkpoints
+        v.rows = ix->d_rows.get();
         v.tally = nullptr;
         ix->kmode = d.mode == MOVI_MODE_BLOCKED ? MOVI_MODE_REGULAR : MOVI_MODE_REGULAR_THRESHOLDS;
     }
@@ -545,15 +521,14 @@ static movi_index *new_handle(int device, const movi_index_desc_t *desc) {
 // Mode 7: the resident table is the file's 3-byte rows widened to one aligned dword each (kernels: load_row<7>);
 // `packed` is a device buffer with the file bytes.  The handle owns the widened copy.
 static hipError_t adopt_widened(movi_index *ix, const uint8_t *d_packed) {
-    uint32_t *wide = nullptr;
-    hipError_t e = hipMalloc(&wide, (size_t)ix->desc.r * 4 + 16);
+    DevPtr<uint32_t> wide;
+    hipError_t e = dev_alloc(wide, (size_t)ix->desc.r * 4 + 16);
     if (e != hipSuccess) return e;
-    e = hipMemset(wide, 0, (size_t)ix->desc.r * 4 + 16);
-    if (e == hipSuccess) e = widen_rows(d_packed, ix->desc.r, wide, nullptr);
+    e = hipMemset(wide.get(), 0, (size_t)ix->desc.r * 4 + 16);
+    if (e == hipSuccess) e = widen_rows(d_packed, ix->desc.r, wide.get(), nullptr);
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { (void)hipFree(wide); return e; }
-    ix->d_rows = reinterpret_cast<uint8_t *>(wide);
-    ix->owns_rows = true;
+    if (e != hipSuccess) return e;
+    ix->d_rows = DevPtr<uint8_t>(reinterpret_cast<uint8_t *>(wide.release()));
     return hipSuccess;
 }
 
@@ -629,17 +604,14 @@ static int index_create(int device, const movi_index_desc_t *desc, const void *h
     if (rc) return rc;
     HIP_TRY(hipSetDevice(device));
     movi_index *ix = new_handle(device, desc);
-    hipError_t e = hipMalloc(&ix->d_rows, ix->rows_bytes + 16);
+    hipError_t e = dev_alloc(ix->d_rows, ix->rows_bytes + 16);
     if (e == hipSuccess)
-        e = from_mapping ? upload_from_mapping(ix->d_rows, static_cast<const uint8_t *>(h_rows), ix->rows_bytes)
-                         : hipMemcpy(ix->d_rows, h_rows, ix->rows_bytes, hipMemcpyHostToDevice);
+        e = from_mapping ? upload_from_mapping(ix->d_rows.get(), static_cast<const uint8_t *>(h_rows), ix->rows_bytes)
+                         : hipMemcpy(ix->d_rows.get(), h_rows, ix->rows_bytes, hipMemcpyHostToDevice);
     if (e != hipSuccess) { movi_index_destroy(ix); return fail_hip(e, "uploading the move rows"); }
-    ix->owns_rows = true;
     if (mode_sampled(desc->mode)) {
-        uint8_t *packed = ix->d_rows;
-        ix->d_rows = nullptr;
-        e = adopt_widened(ix, packed);
-        (void)hipFree(packed);
+        const DevPtr<uint8_t> packed = std::move(ix->d_rows);
+        e = adopt_widened(ix, packed.get());
         if (e != hipSuccess) { movi_index_destroy(ix); return fail_hip(e, "widening the 3-byte rows"); }
     }
     rc = finish_create(ix);
@@ -661,10 +633,8 @@ int movi_index_create_from_device_rows(int device, const movi_index_desc_t *desc
     if ((reinterpret_cast<uintptr_t>(d_rows) & 7u) != 0) return fail(MOVI_ERR_ARG, "d_rows must be 8-byte aligned");
     HIP_TRY(hipSetDevice(device));
     movi_index *ix = new_handle(device, desc);
-    ix->d_rows = const_cast<uint8_t *>(static_cast<const uint8_t *>(d_rows));
-    ix->owns_rows = false;
+    ix->d_rows = borrowed<uint8_t, DeviceMem>(const_cast<uint8_t *>(static_cast<const uint8_t *>(d_rows)));
     if (mode_sampled(desc->mode)) {   // private copy; the caller's buffer is not kept
-        ix->d_rows = nullptr;
         hipError_t e = adopt_widened(ix, static_cast<const uint8_t *>(d_rows));
         if (e != hipSuccess) { movi_index_destroy(ix); return fail_hip(e, "widening the 3-byte rows"); }
     }
@@ -748,7 +718,7 @@ int replicate(const movi_index_desc_t *desc, const void *h_rows, const int *devi
     const bool have_rccl = g_rccl.load();
     if (!have_rccl && n > 1) return fail(MOVI_ERR_HIP, g_rccl.err);
     const size_t rows_bytes = (size_t)desc->r * mode_row_bytes(desc->mode);
-    std::vector<uint8_t *> d_rows((size_t)n, nullptr);
+    std::vector<DevPtr<uint8_t>> d_rows((size_t)n);
     std::vector<hipStream_t> streams((size_t)n, nullptr);
     std::vector<ncclComm_t> comms((size_t)n, nullptr);
     bool comms_up = false;
@@ -758,7 +728,7 @@ int replicate(const movi_index_desc_t *desc, const void *h_rows, const int *devi
             (void)hipSetDevice(devices[i]);
             if (streams[i]) (void)hipStreamDestroy(streams[i]);
             if (comms_up && comms[i]) (void)g_rccl.CommDestroy(comms[i]);
-            if (!keep_rows && d_rows[i]) (void)hipFree(d_rows[i]);
+            if (!keep_rows) d_rows[i].reset();
         }
         g_err = keep;
     };
@@ -771,15 +741,15 @@ int replicate(const movi_index_desc_t *desc, const void *h_rows, const int *devi
     // the table's only trip over PCIe: host (or file mapping) -> devices[0]
     for (int i = 0; i < n; i++) {
         hipError_t e = hipSetDevice(devices[i]);
-        if (e == hipSuccess) e = hipMalloc(&d_rows[i], rows_bytes + 16);
+        if (e == hipSuccess) e = dev_alloc(d_rows[i], rows_bytes + 16);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&streams[i], hipStreamNonBlocking);
         if (e != hipSuccess) return hip_fail(e, "allocating the move rows");
     }
     {
         hipError_t e = hipSetDevice(devices[0]);
         if (e == hipSuccess)
-            e = from_mapping ? upload_from_mapping(d_rows[0], static_cast<const uint8_t *>(h_rows), rows_bytes)
-                             : hipMemcpy(d_rows[0], h_rows, rows_bytes, hipMemcpyHostToDevice);
+            e = from_mapping ? upload_from_mapping(d_rows[0].get(), static_cast<const uint8_t *>(h_rows), rows_bytes)
+                             : hipMemcpy(d_rows[0].get(), h_rows, rows_bytes, hipMemcpyHostToDevice);
         if (e != hipSuccess) return hip_fail(e, "uploading the move rows");
     }
     // ... and from there to every other GPU: one broadcast over xGMI, all ranks driven by this process.
@@ -802,7 +772,7 @@ int replicate(const movi_index_desc_t *desc, const void *h_rows, const int *devi
         if (r != ncclSuccess) return nccl_fail(r, "ncclGroupStart");
         for (int i = 0; i < n && r == ncclSuccess; i++) {
             (void)hipSetDevice(devices[i]);
-            r = g_rccl.Broadcast(d_rows[i], d_rows[i], rows_bytes, ncclUint8, 0, comms[i], streams[i]);
+            r = g_rccl.Broadcast(d_rows[i].get(), d_rows[i].get(), rows_bytes, ncclUint8, 0, comms[i], streams[i]);
         }
         const ncclResult_t rg = g_rccl.GroupEnd();
         if (r != ncclSuccess) return nccl_fail(r, "ncclBroadcast");
@@ -816,17 +786,13 @@ int replicate(const movi_index_desc_t *desc, const void *h_rows, const int *devi
     // every GPU builds its own resident layout from the file-format rows it now holds
     for (int i = 0; i < n; i++) {
         hipError_t e = hipSetDevice(devices[i]);
-        if (e != hipSuccess) { for (int j = 0; j < i; j++) { movi_index_destroy(out[j]); out[j] = nullptr; d_rows[j] = nullptr; } return hip_fail(e, "hipSetDevice"); }
+        if (e != hipSuccess) { for (int j = 0; j < i; j++) { movi_index_destroy(out[j]); out[j] = nullptr; } return hip_fail(e, "hipSetDevice"); }
         movi_index *ix = new_handle(devices[i], desc);
-        ix->d_rows = d_rows[i];
-        ix->owns_rows = true;
-        d_rows[i] = nullptr;                                   // the handle's from here on
+        ix->d_rows = std::move(d_rows[i]);                     // the handle's from here on
         int rci = MOVI_OK;
         if (mode_sampled(desc->mode)) {
-            uint8_t *packed = ix->d_rows;
-            ix->d_rows = nullptr;
-            e = adopt_widened(ix, packed);
-            (void)hipFree(packed);
+            const DevPtr<uint8_t> packed = std::move(ix->d_rows);
+            e = adopt_widened(ix, packed.get());
             if (e != hipSuccess) rci = fail_hip(e, "widening the 3-byte rows");
         }
         if (rci == MOVI_OK) rci = finish_create(ix);
@@ -868,22 +834,6 @@ int movi_index_load_replicated(const char *path, const int *devices, int n, movi
 int movi_index_destroy(movi_index_t *ix) {
     if (!ix) return MOVI_OK;
     (void)hipSetDevice(ix->device);
-    if (ix->owns_rows && ix->d_rows) (void)hipFree(ix->d_rows);
-    if (ix->d_code_of) (void)hipFree(ix->d_code_of);
-    if (ix->d_id_blocks) (void)hipFree(ix->d_id_blocks);
-    if (ix->d_sep_rows) (void)hipFree(ix->d_sep_rows);
-    if (ix->d_sep_vals) (void)hipFree(ix->d_sep_vals);
-    if (ix->d_tally) (void)hipFree(ix->d_tally);
-    if (ix->d_ckpt) (void)hipFree(ix->d_ckpt);
-    if (ix->d_kmer) (void)hipFree(ix->d_kmer);
-    if (ix->d_ftab) (void)hipFree(ix->d_ftab);
-    if (ix->d_rows2) (void)hipFree(ix->d_rows2);
-    if (ix->d_rows3) (void)hipFree(ix->d_rows3);
-    if (ix->d_stats) (void)hipFree(ix->d_stats);
-    if (ix->d_loc) (void)hipFree(ix->d_loc);
-    if (ix->d_samples) (void)hipFree(ix->d_samples);
-    if (ix->d_color_flat) (void)hipFree(ix->d_color_flat);
-    if (ix->d_color_inds) (void)hipFree(ix->d_color_inds);
     release_scratch(ix);
     delete ix;
     return MOVI_OK;
@@ -896,13 +846,19 @@ int movi_index_destroy(movi_index_t *ix) {
 static bool kmer_eligible(const movi_index *ix) {
     return ix->kmode == MOVI_MODE_REGULAR_THRESHOLDS && ix->dev.sigma - ix->dev.sep == 4 && ix->desc.r >= 8;
 }
+static void drop_kmer(movi_index *ix) {
+    ix->dev.kmer_k = 0;
+    ix->dev.kmer = nullptr;
+    ix->d_kmer.reset();
+}
 static int build_kmer(movi_index *ix, uint32_t K, hipStream_t s) {
-    const size_t bytes = (size_t)16 << (2 * K);
-    HIP_TRY(hipMalloc(&ix->d_kmer, bytes));
-    hipError_t e = build_kmer_table(ix->dev, K, ix->d_kmer, s);
+    DevPtr<uint4> table;
+    HIP_TRY(dev_alloc(table, (size_t)16 << (2 * K)));
+    hipError_t e = build_kmer_table(ix->dev, K, table.get(), s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { (void)hipFree(ix->d_kmer); ix->d_kmer = nullptr; return fail_hip(e, "building the top-of-walk table"); }
-    ix->dev.kmer = ix->d_kmer;
+    if (e != hipSuccess) return fail_hip(e, "building the top-of-walk table");
+    ix->d_kmer = std::move(table);
+    ix->dev.kmer = ix->d_kmer.get();
     ix->dev.kmer_k = K;
     return MOVI_OK;
 }
@@ -935,12 +891,12 @@ static hipError_t read_tally(const unsigned long long *d_tally, unsigned long lo
 // The statistic over a sample of the table's rows (every 16th), before anything is built.
 static void sample_no_ff(movi_index *ix, hipStream_t s) {
     if (ix->ahead_tallied) return;
-    unsigned long long *d_tally = nullptr, h_tally[2] = {0, 0};
-    hipError_t e = hipMalloc(&d_tally, kTallyBytes);
-    if (e == hipSuccess) e = hipMemsetAsync(d_tally, 0, kTallyBytes, s);
-    if (e == hipSuccess) e = tally_no_ff_share(ix->kmode, ix->dev, 16, d_tally, s);
-    if (e == hipSuccess) e = read_tally(d_tally, h_tally, s);
-    if (d_tally) (void)hipFree(d_tally);
+    DevPtr<unsigned long long> tally;
+    unsigned long long h_tally[2] = {0, 0};
+    hipError_t e = dev_alloc(tally, kTallyBytes);
+    if (e == hipSuccess) e = hipMemsetAsync(tally.get(), 0, kTallyBytes, s);
+    if (e == hipSuccess) e = tally_no_ff_share(ix->kmode, ix->dev, 16, tally.get(), s);
+    if (e == hipSuccess) e = read_tally(tally.get(), h_tally, s);
     if (e != hipSuccess) { (void)hipGetLastError(); return; }
     ix->ahead_no_ff = h_tally[1] ? (double)h_tally[0] / (double)h_tally[1] : 0.0;
     ix->ahead_tallied = true;
@@ -957,17 +913,26 @@ static bool ahead_wanted(movi_index *ix) {
 // by_itself: built by the size policy, not on request -- then the count query uses the copy only where the table's own
 // statistic says it pays (DevIndex::rows2_count)
 constexpr double kAheadCountRatio = 0.67;
+static void drop_ahead(movi_index *ix) {
+    ix->dev.rows2 = nullptr;
+    ix->dev.rows2_tail = 0;
+    ix->dev.rows2_count = 0;
+    ix->dev.hints = 0;
+    ix->d_rows2.reset();
+}
 static int build_ahead(movi_index *ix, hipStream_t s, bool by_itself) {
-    HIP_TRY(hipMalloc(&ix->d_rows2, ahead_rows_bytes(ix->desc.r)));
+    DevPtr<uint8_t> rows2;
+    HIP_TRY(dev_alloc(rows2, ahead_rows_bytes(ix->desc.r)));
     uint64_t tail = 0;
-    unsigned long long *d_tally = nullptr, h_tally[2] = {0, 0};
-    hipError_t e = hipMalloc(&d_tally, kTallyBytes);
-    if (e == hipSuccess) e = hipMemsetAsync(d_tally, 0, kTallyBytes, s);
-    if (e == hipSuccess) e = build_ahead_rows(ix->kmode, ix->dev, ix->d_rows2, &tail, s, d_tally);
-    if (e == hipSuccess) e = read_tally(d_tally, h_tally, s);
-    if (d_tally) (void)hipFree(d_tally);
-    if (e != hipSuccess) { (void)hipFree(ix->d_rows2); ix->d_rows2 = nullptr; return fail_hip(e, "building the look-ahead rows"); }
-    ix->dev.rows2 = ix->d_rows2;
+    DevPtr<unsigned long long> tally;
+    unsigned long long h_tally[2] = {0, 0};
+    hipError_t e = dev_alloc(tally, kTallyBytes);
+    if (e == hipSuccess) e = hipMemsetAsync(tally.get(), 0, kTallyBytes, s);
+    if (e == hipSuccess) e = build_ahead_rows(ix->kmode, ix->dev, rows2.get(), &tail, s, tally.get());
+    if (e == hipSuccess) e = read_tally(tally.get(), h_tally, s);
+    if (e != hipSuccess) return fail_hip(e, "building the look-ahead rows");
+    ix->d_rows2 = std::move(rows2);
+    ix->dev.rows2 = ix->d_rows2.get();
     ix->dev.rows2_tail = tail;
     ix->dev.hints = ahead_rows_hinted(ix->desc.r) ? 1u : 0u;   // (the copy's ids are 32 bits wide and its spare bits hold reposition hints)
     ix->ahead_no_ff = h_tally[1] ? (double)h_tally[0] / (double)h_tally[1] : 0.0;
@@ -984,12 +949,18 @@ constexpr uint64_t kDeepAutoRows = 48ull << 20;             // 50 M rows: a copy
 static bool deep_eligible(const movi_index *ix) {
     return ix->kmode == MOVI_MODE_REGULAR_THRESHOLDS && deep_rows_eligible(ix->desc.r);
 }
+static void drop_deep(movi_index *ix) {
+    ix->dev.rows3 = nullptr;
+    ix->d_rows3.reset();
+}
 static int build_deep(movi_index *ix, hipStream_t s) {
-    HIP_TRY(hipMalloc(&ix->d_rows3, deep_rows_bytes(ix->desc.r)));
-    hipError_t e = build_deep_rows(ix->kmode, ix->dev, ix->d_rows3, s);
+    DevPtr<uint8_t> rows3;
+    HIP_TRY(dev_alloc(rows3, deep_rows_bytes(ix->desc.r)));
+    hipError_t e = build_deep_rows(ix->kmode, ix->dev, rows3.get(), s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { (void)hipFree(ix->d_rows3); ix->d_rows3 = nullptr; return fail_hip(e, "building the deep rows"); }
-    ix->dev.rows3 = ix->d_rows3;
+    if (e != hipSuccess) return fail_hip(e, "building the deep rows");
+    ix->d_rows3 = std::move(rows3);
+    ix->dev.rows3 = ix->d_rows3.get();
     return MOVI_OK;
 }
 
@@ -997,13 +968,19 @@ static int build_deep(movi_index *ix, hipStream_t s) {
 static bool ftab_eligible(const movi_index *ix) {
     return (ix->kmode == MOVI_MODE_REGULAR_THRESHOLDS || ix->kmode == MOVI_MODE_REGULAR) && ix->dev.sigma - ix->dev.sep == 4;
 }
+static void drop_ftab(movi_index *ix) {
+    ix->dev.ftab_k = 0;
+    ix->dev.ftab = nullptr;
+    ix->d_ftab.reset();
+}
 static int build_ftab_table(movi_index *ix, uint32_t K, hipStream_t s) {
-    const size_t bytes = (size_t)16 << (2 * K);
-    HIP_TRY(hipMalloc(&ix->d_ftab, bytes));
-    hipError_t e = build_ftab(ix->kmode, ix->dev, K, ix->d_ftab, s);
+    DevPtr<uint4> table;
+    HIP_TRY(dev_alloc(table, (size_t)16 << (2 * K)));
+    hipError_t e = build_ftab(ix->kmode, ix->dev, K, table.get(), s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) { (void)hipFree(ix->d_ftab); ix->d_ftab = nullptr; return fail_hip(e, "building the count query's interval table"); }
-    ix->dev.ftab = ix->d_ftab;
+    if (e != hipSuccess) return fail_hip(e, "building the count query's interval table");
+    ix->d_ftab = std::move(table);
+    ix->dev.ftab = ix->d_ftab.get();
     ix->dev.ftab_k = K;
     return MOVI_OK;
 }
@@ -1062,7 +1039,7 @@ int movi_index_get_desc(const movi_index_t *ix, movi_index_desc_t *desc) {
 
 int movi_index_device_rows(const movi_index_t *ix, const void **d_rows, size_t *bytes) {
     if (!ix || !d_rows || !bytes) return fail(MOVI_ERR_ARG, "NULL argument");
-    *d_rows = ix->d_rows;
+    *d_rows = ix->d_rows.get();
     // blocked- / sampled-thresholds: the resident table is the EXPANDED one (r rows of the 8-byte regular-thresholds layout)
     *bytes = ix->kmode != (int)ix->desc.mode ? (size_t)ix->desc.r * 8 : ix->rows_bytes;
     return MOVI_OK;
@@ -1151,27 +1128,19 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
         HIP_TRY(hipSetDevice(ix->device));
         const size_t v = (size_t)value;
         if (!strcmp(key, "reserve_host_bases")) {
-            HIP_TRY(grow(&ix->scratch[movi_index::kBases], &ix->scratch_cap[movi_index::kBases], v));
+            HIP_TRY(grow(ix->scratch[movi_index::kBases], v));
         } else if (!strcmp(key, "reserve_host_results")) {
-            HIP_TRY(grow(&ix->scratch[movi_index::kOut], &ix->scratch_cap[movi_index::kOut], v * 2));
+            HIP_TRY(grow(ix->scratch[movi_index::kOut], v * 2));
             // (round 6: a PML vector is written through reset masks on the device -- their words, for as many reads as "reserve_host_reads" says)
             ix->reserved_result_bases = std::max<uint64_t>(ix->reserved_result_bases, v);
-            HIP_TRY(grow(&ix->scratch[movi_index::kMask], &ix->scratch_cap[movi_index::kMask],
-                         (size_t)pml_mask_words(ix->reserved_reads, ix->reserved_result_bases, 31u) * 4));
+            HIP_TRY(grow(ix->scratch[movi_index::kMask], (size_t)pml_mask_words(ix->reserved_reads, ix->reserved_result_bases, 31u) * 4));
         } else {                                             // "reserve_host_reads"
             ix->reserved_reads = std::max<uint64_t>(ix->reserved_reads, v);
             if (ix->reserved_result_bases)
-                HIP_TRY(grow(&ix->scratch[movi_index::kMask], &ix->scratch_cap[movi_index::kMask],
-                             (size_t)pml_mask_words(ix->reserved_reads, ix->reserved_result_bases, 31u) * 4));
-            HIP_TRY(grow(&ix->scratch[movi_index::kOffs], &ix->scratch_cap[movi_index::kOffs], (v + 1) * 8));
-            HIP_TRY(grow(&ix->scratch[movi_index::kErr], &ix->scratch_cap[movi_index::kErr], v));
-            if (ix->h_rel_cap < v + 1) {
-                if (ix->h_rel) (void)hipHostFree(ix->h_rel);
-                ix->h_rel = nullptr;
-                ix->h_rel_cap = 0;
-                HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ix->h_rel), (v + 1) * 8, hipHostMallocDefault));
-                ix->h_rel_cap = v + 1;
-            }
+                HIP_TRY(grow(ix->scratch[movi_index::kMask], (size_t)pml_mask_words(ix->reserved_reads, ix->reserved_result_bases, 31u) * 4));
+            HIP_TRY(grow(ix->scratch[movi_index::kOffs], (v + 1) * 8));
+            HIP_TRY(grow(ix->scratch[movi_index::kErr], v));
+            HIP_TRY(ix->h_rel.reserve((v + 1) * 8, (v + 1) * 8));   // (a reservation: exactly what was asked for)
         }
         return MOVI_OK;
     }
@@ -1219,16 +1188,16 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
     if (!strcmp(key, "park_lanes")) {                        // the mask walk's parked lanes: -1 = the policy (plan_pml), 0 = off, 1 .. 63 = a wavefront stops at that many walking lanes (A/B)
         if (value < -1 || value > 63) return fail(MOVI_ERR_ARG, "park_lanes must be -1 .. 63");
         ix->cfg.park_lanes = (int)value;
-        if (ix->dmask_cap != 0 && park_lanes_wanted(ix) > 0) {   // where the mask words are reserved, so is the queue (no room: such calls park nothing)
+        if (ix->dmask.cap() != 0 && park_lanes_wanted(ix) > 0) {   // where the mask words are reserved, so is the queue (no room: such calls park nothing)
             HIP_TRY(hipSetDevice(ix->device));
-            if (grow_dpark(ix, park_queue_bytes(kPrepareMaskReads, park_lanes_wanted(ix))) != hipSuccess) (void)hipGetLastError();
+            if (grow(ix->dpark, park_queue_bytes(kPrepareMaskReads, park_lanes_wanted(ix))) != hipSuccess) (void)hipGetLastError();
         }
         return MOVI_OK;
     }
     if (!strcmp(key, "reserve_device_masks")) {             // device scratch for the mask words of movi_pml_device calls of up to `value` bases (and as many reads / 16)
         if (value < 0 || (uint64_t)value > (1ull << 40)) return fail(MOVI_ERR_ARG, "reserve_device_masks out of range");
         HIP_TRY(hipSetDevice(ix->device));
-        HIP_TRY(grow_dmask(ix, (size_t)pml_mask_words((uint64_t)value / 16 + 1, (uint64_t)value, 0) * 4));
+        HIP_TRY(grow(ix->dmask, (size_t)pml_mask_words((uint64_t)value / 16 + 1, (uint64_t)value, 0) * 4));
         return MOVI_OK;
     }
     if (!strcmp(key, "host_threads")) {                      // workers of the host-side mask expansion (0 = as many as the process may run on)
@@ -1255,10 +1224,7 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
         if (value < 0 || value > 12) return fail(MOVI_ERR_ARG, "kmer_k must be in [0, 12]");
         HIP_TRY(hipSetDevice(ix->device));
         HIP_TRY(hipDeviceSynchronize());                     // no walk may be reading the table that goes away
-        ix->dev.kmer_k = 0;
-        ix->dev.kmer = nullptr;
-        if (ix->d_kmer) (void)hipFree(ix->d_kmer);
-        ix->d_kmer = nullptr;
+        drop_kmer(ix);
         ix->kmer_auto = 0;                                   // the caller's choice from here on
         if (value == 0) return MOVI_OK;
         if (!kmer_eligible(ix))
@@ -1269,17 +1235,10 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
         if (value < 0 || value > 1) return fail(MOVI_ERR_ARG, "ahead_rows must be 0 or 1");
         HIP_TRY(hipSetDevice(ix->device));
         HIP_TRY(hipDeviceSynchronize());                     // no walk may be reading the copy that goes away
-        ix->dev.rows2 = nullptr;
-        ix->dev.rows2_tail = 0;
-        ix->dev.rows2_count = 0;
-        ix->dev.hints = 0;
-        if (ix->d_rows2) (void)hipFree(ix->d_rows2);
-        ix->d_rows2 = nullptr;
+        drop_ahead(ix);
         ix->ahead_auto = 0;                                  // the caller's choice from here on ...
-        ix->dev.rows3 = nullptr;                             // ... and it is about what the PML walk runs on: the deep rows, which would take
-        if (ix->d_rows3) (void)hipFree(ix->d_rows3);         // precedence over either answer, go (and are not built by themselves any more;
-        ix->d_rows3 = nullptr;                               // "deep_rows" 1 brings them back)
-        ix->deep_auto = 0;
+        drop_deep(ix);                                       // ... and it is about what the PML walk runs on: the deep rows, which would take precedence
+        ix->deep_auto = 0;                                   // over either answer, go (and are not built by themselves any more; "deep_rows" 1 brings them back)
         if (value == 0) return MOVI_OK;
         if (!ahead_eligible(ix)) return fail(MOVI_ERR_ARG, "look-ahead rows serve PML walks on *-thresholds indexes only");
         return build_ahead(ix, nullptr, false);
@@ -1288,9 +1247,7 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
         if (value < 0 || value > 1) return fail(MOVI_ERR_ARG, "deep_rows must be 0 or 1");
         HIP_TRY(hipSetDevice(ix->device));
         HIP_TRY(hipDeviceSynchronize());                     // no walk may be reading the copy that goes away
-        ix->dev.rows3 = nullptr;
-        if (ix->d_rows3) (void)hipFree(ix->d_rows3);
-        ix->d_rows3 = nullptr;
+        drop_deep(ix);
         ix->deep_auto = 0;                                   // the caller's choice from here on
         if (value == 0) return MOVI_OK;
         if (!deep_eligible(ix)) return fail(MOVI_ERR_ARG, "deep rows serve PML walks on *-thresholds indexes of fewer than 2^28 - 1 rows only");
@@ -1305,10 +1262,7 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
         if (value < 0 || value > 12) return fail(MOVI_ERR_ARG, "ftab_k must be in [0, 12]");
         HIP_TRY(hipSetDevice(ix->device));
         HIP_TRY(hipDeviceSynchronize());
-        ix->dev.ftab_k = 0;
-        ix->dev.ftab = nullptr;
-        if (ix->d_ftab) (void)hipFree(ix->d_ftab);
-        ix->d_ftab = nullptr;
+        drop_ftab(ix);
         ix->ftab_auto = 0;
         if (value == 0) return MOVI_OK;
         if (!ftab_eligible(ix)) return fail(MOVI_ERR_ARG, "the count query's interval table serves DNA (ACGT) indexes only");
@@ -1330,14 +1284,14 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
 // ---------------------------------------------------------------------------- PML
 
 // mask (optional; PML only): reset masks out instead of the vector -- mask->words / phase from the caller; a path without a mask output
-// of its own writes its vector to *tmp_p first (grow-only device scratch: the handle's, or a pipeline slot's).
+// of its own writes its vector to *tmp first (grow-only device scratch: the handle's, or a pipeline slot's).
 static int ml_device(bool zml, movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
                      uint64_t n_bases, uint16_t *d_out, uint8_t *d_read_err, const uint32_t *d_read_order, void *stream,
                      const ClsArgs &cls = ClsArgs(), DevStats *d_stats = nullptr, SegWorkspace *seg_ws = nullptr,
-                     int ragged_hint = -1, int *seg_verdict = nullptr, const MaskArgs *mask = nullptr, void **tmp_p = nullptr,
-                     size_t *tmp_cap = nullptr, bool tables_ready = false) {
+                     int ragged_hint = -1, int *seg_verdict = nullptr, const MaskArgs *mask = nullptr, DevBuf *tmp = nullptr,
+                     bool tables_ready = false) {
     if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
-    if (!d_stats) d_stats = ix->d_stats;                     // (the pipelined host path counts per chunk in flight ...
+    if (!d_stats) d_stats = ix->d_stats.get();               // (the pipelined host path counts per chunk in flight ...
     if (!seg_ws) seg_ws = &ix->seg_ws;                       //  ... and keeps a segment workspace per chunk in flight)
     if (!zml && !mode_has_thresholds(ix->desc.mode))
         return fail(MOVI_ERR_ARG, "PML needs thresholds: on a `regular`, `blocked` or `sampled` index the reference repositions "
@@ -1368,9 +1322,9 @@ static int ml_device(bool zml, movi_index_t *ix, const uint8_t *d_bases, const u
         if (masks) {
             m = *mask;
             if (!m.expand_out && pml_mask_needs_tmp(ix->dev, ix->cfg, n_reads, n_bases, seg_ws != nullptr)) {   // (expand_out: such a batch writes the vector itself)
-                if (!tmp_p) { tmp_p = &ix->scratch[movi_index::kTmp]; tmp_cap = &ix->scratch_cap[movi_index::kTmp]; }
-                HIP_TRY(grow(tmp_p, tmp_cap, n_bases * 2));
-                m.tmp_pml = static_cast<uint16_t *>(*tmp_p);
+                if (!tmp) tmp = &ix->scratch[movi_index::kTmp];
+                HIP_TRY(grow(*tmp, n_bases * 2));
+                m.tmp_pml = tmp->as<uint16_t>();
             }
         }
         // (device-pointer calls: the probe's verdict is remembered for the next 15 calls on batches of the same shape -- mean read length
@@ -1403,7 +1357,7 @@ int movi_pml_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_
         // the ring in LDS, which is as good there (c3: 16.76 against 16.66 ms).  The mask words live in device scratch of the handle
         // (ix->dmask, grow-only): movi_index_prepare reserves them for kPrepareMaskBases bases, "reserve_device_masks" for more.  A bigger
         // batch grows them -- but never under a stream capture: a captured call whose words do not fit takes the packer route, which
-        // needs no scratch, and a buffer a captured call has used is retired on growth, not freed (grow_dmask).
+        // needs no scratch, and a buffer a captured call has used is retired on growth, not freed (GraphSafeBuf).
         // The vector of a fused expansion leaves in aligned 16-byte stores: launch_pml fuses it only into a 16-byte aligned d_out_pml
         // and hands any other to launch_pml_expand behind the walk.
         HIP_TRY(hipSetDevice(ix->device));
@@ -1412,20 +1366,20 @@ int movi_pml_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_
         if (ix->pml_via_mask > 0 || pml_vector_via_masks(ix->dev, ix->cfg, n_reads, n_bases, true, d_read_order != nullptr)) {
             const size_t need = (size_t)pml_mask_words(n_reads, n_bases, 0) * 4;
             const bool capturing = stream_capturing(s);
-            if (!capturing || need <= ix->dmask_cap) {
-                HIP_TRY(grow_dmask(ix, need));
-                if (capturing) ix->dmask_in_graph = true;
+            if (!capturing || need <= ix->dmask.cap()) {
+                HIP_TRY(grow(ix->dmask, need));
+                if (capturing) ix->dmask.mark_in_graph();
                 MaskArgs m;
-                m.words = static_cast<uint32_t *>(ix->dmask);
+                m.words = ix->dmask.as<uint32_t>();
                 m.phase = 0;
                 m.expand_out = d_out_pml;
                 lend_park_queue(ix, n_reads, s, m);
                 return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, nullptr, d_read_err, d_read_order, stream, ClsArgs(), nullptr,
-                                 nullptr, -1, nullptr, &m, nullptr, nullptr, true);
+                                 nullptr, -1, nullptr, &m, nullptr, true);
             }
         }
         return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, d_out_pml, d_read_err, d_read_order, stream, ClsArgs(), nullptr,
-                         nullptr, -1, nullptr, nullptr, nullptr, nullptr, true);
+                         nullptr, -1, nullptr, nullptr, nullptr, true);
     }
     return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, d_out_pml, d_read_err, d_read_order, stream);
 }
@@ -1515,21 +1469,20 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     else if (!strcmp(key, "derived_bytes")) *value = kmer + ftab + ahead + deep + ckpt + locate + color;
     else if (!strcmp(key, "ahead_no_ff")) *value = ix->ahead_tallied ? ix->ahead_no_ff : -1.0;
     else if (!strcmp(key, "device_scratch_bytes")) {         // device scratch the *_device calls hold: mask words (retired ones too), vector, segment workspace
-        double b = (double)ix->dmask_cap + (double)ix->dpark_cap + (double)ix->scratch_cap[movi_index::kTmp] + (double)ix->seg_ws.cap + (double)ix->color_scratch_cap;
-        for (const auto &r : ix->dmask_retired) b += (double)r.second;
-        *value = b;
+        *value = (double)ix->dmask.held_bytes() + (double)ix->dpark.cap() + (double)ix->scratch[movi_index::kTmp].cap() + (double)ix->seg_ws.cap() +
+                 (double)ix->color_scratch.cap();      // (held_bytes: the live words and the handle's retired blocks, queues among them)
     }
     else if (!strcmp(key, "park_lanes")) *value = (double)ix->last_launch.park_lanes;   // what the last PML call's mask walk parked at (0 = it parked nothing)
     else if (!strcmp(key, "parked_reads")) {                 // reads the last query call's first launch handed to its second (waits for the device; not under a stream capture)
         unsigned long long parked = 0;
         HIP_TRY(hipSetDevice(ix->device));
         HIP_TRY(hipDeviceSynchronize());
-        if (ix->last_launch.park_lanes > 0 && ix->dpark) HIP_TRY(hipMemcpy(&parked, ix->dpark, sizeof(parked), hipMemcpyDeviceToHost));   // (the queue's head)
+        if (ix->last_launch.park_lanes > 0 && ix->dpark.ptr()) HIP_TRY(hipMemcpy(&parked, ix->dpark.ptr(), sizeof(parked), hipMemcpyDeviceToHost));   // (the queue's head)
         *value = (double)parked;
     }
     else if (!strcmp(key, "host_staging_bytes")) {          // device staging the synchronous *_host calls hold at the moment
         double b = 0.0;
-        for (int k = 0; k < movi_index::kScratchSlots; k++) b += (double)ix->scratch_cap[k];
+        for (const DevBuf &buf : ix->scratch) b += (double)buf.cap();
         *value = b;
     }
     else return fail(MOVI_ERR_ARG, std::string("unknown info key: ") + key);
@@ -1541,7 +1494,7 @@ int movi_last_stats(movi_index_t *ix, void *stream, movi_query_stats_t *stats) {
     HIP_TRY(hipSetDevice(ix->device));
     HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
     DevStats h{};
-    HIP_TRY(hipMemcpy(&h, ix->d_stats, sizeof(h), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&h, ix->d_stats.get(), sizeof(h), hipMemcpyDeviceToHost));
     stats->bases = 0;                      // not tracked on the device: the *_host entry points fill it in
     stats->fast_forwards = h.fast_forwards;
     stats->scans = h.scans;
@@ -1577,20 +1530,6 @@ constexpr uint64_t kPipeMinReads = 1ull << 15;
 constexpr uint64_t kPipeTargetChunks = 8;
 constexpr uint64_t kPipeMaskChunks = 16;
 
-hipError_t grow(void **p, size_t *cap, size_t bytes) {
-    if (bytes < 8) bytes = 8;
-    if (*cap < bytes) {
-        if (*p) (void)hipFree(*p);
-        *p = nullptr;
-        *cap = 0;
-        const size_t want = bytes + (bytes >> 3);
-        hipError_t e = hipMalloc(p, want);
-        if (e != hipSuccess) return e;
-        *cap = want;
-    }
-    return hipSuccess;
-}
-
 // Where a *_host call's bases come from: the caller's ASCII bytes (h_bases, indexed by offsets[]), or reads packed two bits per base
 // plus their exception list (include/movi_hip.h): those go up as they are, a quarter of the bytes, and every chunk is unpacked on the
 // device into the staging the ASCII bytes would have been copied to.  The ASCII form makes exactly the HIP calls it always made.
@@ -1625,8 +1564,7 @@ struct ChunkCtx {
     movi_index *ix = nullptr;
     hipStream_t s = nullptr;
     DevStats *d_stats = nullptr;
-    void **d = nullptr;
-    size_t *cap = nullptr;
+    DevBuf *d = nullptr;             // kScratchSlots of them
     uint8_t *h_small = nullptr;
     SegWorkspace *seg_ws = nullptr;
     int ragged_hint = -1;            // the chunk's longest read is (1) / is not (0) more than 1.5 x its mean: launch_pml's segment policy
@@ -1634,9 +1572,10 @@ struct ChunkCtx {
     uint64_t first = 0, b0 = 0;      // the chunk: its first read and the position of its first base in the caller's arrays
     HostPool::Group *grp = nullptr;  // overlapped path: the slot's group of worker-pool tasks (what reads the slot's page-locked block)
     bool async = false;
-    hipError_t alloc(int slot, size_t bytes, void **out) {
-        hipError_t e = grow(&d[slot], &cap[slot], bytes);
-        *out = d[slot];
+    template <typename T>
+    hipError_t alloc(int slot, size_t bytes, T **out) {
+        hipError_t e = grow(d[slot], bytes);
+        *out = d[slot].template as<T>();
         return e;
     }
     // device -> host: straight into the caller's buffer (synchronous path, or a page-locked destination) ...
@@ -1665,12 +1604,8 @@ bool is_pinned(const void *p) {
 
 }  // namespace
 
+// Every stream of the handle -- the upload stream here, a slot's in PipeSlot::release -- drains before a buffer it may touch goes.
 static void release_scratch(movi_index *ix) {
-    for (int k = 0; k < movi_index::kScratchSlots; k++) {
-        if (ix->scratch[k]) (void)hipFree(ix->scratch[k]);
-        ix->scratch[k] = nullptr;
-        ix->scratch_cap[k] = 0;
-    }
     if (ix->pipe_up) {
         (void)hipStreamSynchronize(ix->pipe_up);
         (void)hipStreamDestroy(ix->pipe_up);
@@ -1678,45 +1613,13 @@ static void release_scratch(movi_index *ix) {
     }
     for (hipEvent_t e : ix->pipe_ev) (void)hipEventDestroy(e);
     ix->pipe_ev.clear();
-    if (ix->seg_ws.buf) (void)hipFree(ix->seg_ws.buf);
-    ix->seg_ws = SegWorkspace();
-    if (ix->d_color_scratch) (void)hipFree(ix->d_color_scratch);
-    ix->d_color_scratch = nullptr;
-    ix->color_scratch_cap = 0;
-    if (ix->dmask) (void)hipFree(ix->dmask);               // (graphs captured over movi_pml_device on this handle are invalid from here on)
-    ix->dmask = nullptr;
-    ix->dmask_cap = 0;
-    ix->dmask_in_graph = false;
-    if (ix->dpark) (void)hipFree(ix->dpark);
-    ix->dpark = nullptr;
-    ix->dpark_cap = 0;
-    ix->dpark_in_graph = false;
-    for (const auto &r : ix->dmask_retired) (void)hipFree(r.first);
-    ix->dmask_retired.clear();
-    if (ix->h_rel) (void)hipHostFree(ix->h_rel);
-    ix->h_rel = nullptr;
-    ix->h_rel_cap = 0;
-    for (auto &sl : ix->pipe) {
-        if (sl.s) (void)hipStreamSynchronize(sl.s);
-        if (sl.seg_ws.buf) (void)hipFree(sl.seg_ws.buf);
-        sl.seg_ws = SegWorkspace();
-        for (int k = 0; k < movi_index::kScratchSlots; k++) {
-            if (sl.d[k]) (void)hipFree(sl.d[k]);
-            sl.d[k] = nullptr;
-            sl.cap[k] = 0;
-        }
-        if (sl.d_stats) (void)hipFree(sl.d_stats);
-        sl.d_stats = nullptr;
-        if (sl.h) (void)hipHostFree(sl.h);
-        sl.h = nullptr;
-        sl.h_cap = 0;
-        if (sl.ev) (void)hipEventDestroy(sl.ev);
-        sl.ev = nullptr;
-        if (sl.ev_up) (void)hipEventDestroy(sl.ev_up);
-        sl.ev_up = nullptr;
-        if (sl.s) (void)hipStreamDestroy(sl.s);
-        sl.s = nullptr;
-    }
+    for (auto &sl : ix->pipe) sl.release();
+    for (DevBuf &b : ix->scratch) b.release();
+    ix->seg_ws.release();
+    ix->color_scratch.release();
+    ix->dmask.release();                                   // (graphs captured over movi_pml_device on this handle are invalid from here on)
+    ix->dpark.release();
+    ix->h_rel.release();
 }
 
 namespace {
@@ -1759,18 +1662,17 @@ int run_chunked(movi_index *ix, const ReadSource &src, const uint64_t *h_offsets
                 uint8_t *h_read_err, movi_query_stats_t *stats, Launch launch, Fetch fetch, Harvest, size_t, size_t) {
     if (stats) memset(stats, 0, sizeof(*stats));
     if (src.two_bit && src.n_exc) {                           // the call's exception list, once
-        HIP_TRY(grow(&ix->scratch[movi_index::kExcPos], &ix->scratch_cap[movi_index::kExcPos], (size_t)src.n_exc * 8));
-        HIP_TRY(grow(&ix->scratch[movi_index::kExcByte], &ix->scratch_cap[movi_index::kExcByte], (size_t)src.n_exc));
-        HIP_TRY(hipMemcpy(ix->scratch[movi_index::kExcPos], src.exc_pos, (size_t)src.n_exc * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ix->scratch[movi_index::kExcByte], src.exc_byte, (size_t)src.n_exc, hipMemcpyHostToDevice));
+        HIP_TRY(grow(ix->scratch[movi_index::kExcPos], (size_t)src.n_exc * 8));
+        HIP_TRY(grow(ix->scratch[movi_index::kExcByte], (size_t)src.n_exc));
+        HIP_TRY(hipMemcpy(ix->scratch[movi_index::kExcPos].ptr(), src.exc_pos, (size_t)src.n_exc * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(ix->scratch[movi_index::kExcByte].ptr(), src.exc_byte, (size_t)src.n_exc, hipMemcpyHostToDevice));
     }
     int seg_verdict = -1;
     ChunkCtx ctx;
     ctx.ix = ix;
     ctx.seg_verdict = &seg_verdict;
-    ctx.d_stats = ix->d_stats;
+    ctx.d_stats = ix->d_stats.get();
     ctx.d = ix->scratch;
-    ctx.cap = ix->scratch_cap;
     ctx.seg_ws = &ix->seg_ws;
     uint64_t first = 0;
     while (first < n_reads) {
@@ -1782,23 +1684,17 @@ int run_chunked(movi_index *ix, const ReadSource &src, const uint64_t *h_offsets
         }
         const uint64_t nr = last - first;
         const uint64_t b0 = h_offsets[first], nb = h_offsets[last] - b0;
-        struct { void *p; } d_bases{}, d_offs{}, d_err{};
+        uint8_t *d_bases = nullptr, *d_err = nullptr;
+        uint64_t *d_offs = nullptr;
         static const bool trace = getenv("MOVI_TRACE_HOST_CALLS") != nullptr;   // diagnostic: where a synchronous host call's time goes, to stderr
         double tr[8] = {0};
         auto stamp = [&](int k) { if (trace) tr[k] = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         stamp(0);
-        HIP_TRY(ctx.alloc(movi_index::kBases, nb, &d_bases.p));
-        HIP_TRY(ctx.alloc(movi_index::kOffs, (nr + 1) * 8, &d_offs.p));
-        HIP_TRY(ctx.alloc(movi_index::kErr, nr, &d_err.p));
-        if (ix->h_rel_cap < nr + 1) {
-            if (ix->h_rel) (void)hipHostFree(ix->h_rel);
-            ix->h_rel = nullptr;
-            ix->h_rel_cap = 0;
-            const size_t want = (size_t)(nr + 1) + (size_t)((nr + 1) >> 3);
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&ix->h_rel), want * 8, hipHostMallocDefault));
-            ix->h_rel_cap = want;
-        }
-        uint64_t *rel = ix->h_rel;                            // (read by the copy below before the call returns: hipMemcpy is synchronous)
+        HIP_TRY(ctx.alloc(movi_index::kBases, nb, &d_bases));
+        HIP_TRY(ctx.alloc(movi_index::kOffs, (nr + 1) * 8, &d_offs));
+        HIP_TRY(ctx.alloc(movi_index::kErr, nr, &d_err));
+        HIP_TRY(grow_entries(ix->h_rel, (size_t)(nr + 1)));
+        uint64_t *rel = ix->h_rel.as<uint64_t>();             // (read by the copy below before the call returns: hipMemcpy is synchronous)
         uint64_t longest = 0;
         for (uint64_t i = 0; i <= nr; i++) {
             rel[i] = h_offsets[first + i] - b0;
@@ -1809,20 +1705,19 @@ int run_chunked(movi_index *ix, const ReadSource &src, const uint64_t *h_offsets
         // slightly SLOWER (31.1 vs 32.8 Gbases/s, log-normal lengths) -- the walk is bound by the
         // memory system, not by lane occupancy, and the dispatcher already refills whole blocks.
         stamp(1);
-        if (nb && !src.two_bit) HIP_TRY(hipMemcpy(d_bases.p, src.ascii + b0, nb, hipMemcpyHostToDevice));
+        if (nb && !src.two_bit) HIP_TRY(hipMemcpy(d_bases, src.ascii + b0, nb, hipMemcpyHostToDevice));
         if (nb && src.two_bit) {                              // a quarter of the bytes go up; the null stream unpacks them ahead of the walk
             void *d_packed = nullptr;
             HIP_TRY(ctx.alloc(movi_index::kPacked, src.up_bytes(b0, nb), &d_packed));
             HIP_TRY(hipMemcpy(d_packed, src.up_from(b0), src.up_bytes(b0, nb), hipMemcpyHostToDevice));
-            HIP_TRY(unpack_chunk(src, ix->scratch[movi_index::kExcPos], ix->scratch[movi_index::kExcByte], d_packed, b0, nb, d_bases.p, nullptr));
+            HIP_TRY(unpack_chunk(src, ix->scratch[movi_index::kExcPos].ptr(), ix->scratch[movi_index::kExcByte].ptr(), d_packed, b0, nb, d_bases, nullptr));
         }
         stamp(2);
-        HIP_TRY(hipMemcpy(d_offs.p, rel, (nr + 1) * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_offs, rel, (nr + 1) * 8, hipMemcpyHostToDevice));
         stamp(3);
         ctx.first = first;
         ctx.b0 = b0;
-        int rc = launch(ctx, static_cast<const uint8_t *>(d_bases.p), static_cast<const uint64_t *>(d_offs.p), nr, nb,
-                        static_cast<uint8_t *>(d_err.p));
+        int rc = launch(ctx, d_bases, d_offs, nr, nb, d_err);
         if (rc) return rc;
         stamp(4);
         movi_query_stats_t st{};
@@ -1832,7 +1727,7 @@ int run_chunked(movi_index *ix, const ReadSource &src, const uint64_t *h_offsets
         rc = fetch(ctx, first, nr, b0, nb);
         if (rc) return rc;
         stamp(6);
-        if (h_read_err) HIP_TRY(hipMemcpy(h_read_err + first, d_err.p, nr, hipMemcpyDeviceToHost));
+        if (h_read_err) HIP_TRY(hipMemcpy(h_read_err + first, d_err, nr, hipMemcpyDeviceToHost));
         stamp(7);
         if (trace)
             fprintf(stderr, "[movi_hip] host call: %llu reads %llu bases | staging + offsets %.3f | bases up %.3f | offsets up %.3f | launch %.3f | walk + counters %.3f | "
@@ -1878,8 +1773,7 @@ int run_compact(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offset
                 movi_query_stats_t *stats, Device device) {
     if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
     HIP_TRY(hipSetDevice(ix->device));
-    void **d = ix->scratch;
-    size_t *cap = ix->scratch_cap;
+    DevBuf *d = ix->scratch;
     std::vector<uint64_t> rel;
     uint64_t total = 0, errors = 0;
     bool overflow = false;
@@ -1892,38 +1786,37 @@ int run_compact(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offset
             else break;
         }
         const uint64_t nr = last - first, b0 = h_offsets[first], nb = h_offsets[last] - b0;
-        HIP_TRY(grow(&d[movi_index::kBases], &cap[movi_index::kBases], nb));
-        HIP_TRY(grow(&d[movi_index::kOffs], &cap[movi_index::kOffs], (nr + 1) * 8));
-        HIP_TRY(grow(&d[movi_index::kErr], &cap[movi_index::kErr], nr));
-        HIP_TRY(grow(&d[movi_index::kOut], &cap[movi_index::kOut], nb * o.elem_bytes));
-        HIP_TRY(grow(&d[movi_index::kA], &cap[movi_index::kA], nr * (o.second ? 8 : 4)));
-        HIP_TRY(grow(&d[movi_index::kB], &cap[movi_index::kB], (nr + 1) * 8));
+        HIP_TRY(grow(d[movi_index::kBases], nb));
+        HIP_TRY(grow(d[movi_index::kOffs], (nr + 1) * 8));
+        HIP_TRY(grow(d[movi_index::kErr], nr));
+        HIP_TRY(grow(d[movi_index::kOut], nb * o.elem_bytes));
+        HIP_TRY(grow(d[movi_index::kA], nr * (o.second ? 8 : 4)));
+        HIP_TRY(grow(d[movi_index::kB], (nr + 1) * 8));
         rel.resize(nr + 1);
         for (uint64_t i = 0; i <= nr; i++) rel[i] = h_offsets[first + i] - b0;
-        if (nb) HIP_TRY(hipMemcpy(d[movi_index::kBases], h_bases + b0, nb, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d[movi_index::kOffs], rel.data(), (nr + 1) * 8, hipMemcpyHostToDevice));
-        const uint64_t *d_offs = static_cast<const uint64_t *>(d[movi_index::kOffs]);
-        uint32_t *d_n = static_cast<uint32_t *>(d[movi_index::kA]);
-        uint64_t *d_first = static_cast<uint64_t *>(d[movi_index::kB]);
-        int rc = device(static_cast<const uint8_t *>(d[movi_index::kBases]), d_offs, nr, nb, d[movi_index::kOut], d_n,
-                        static_cast<uint8_t *>(d[movi_index::kErr]));
+        if (nb) HIP_TRY(hipMemcpy(d[movi_index::kBases].ptr(), h_bases + b0, nb, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d[movi_index::kOffs].ptr(), rel.data(), (nr + 1) * 8, hipMemcpyHostToDevice));
+        const uint64_t *d_offs = d[movi_index::kOffs].as<uint64_t>();
+        uint32_t *d_n = d[movi_index::kA].as<uint32_t>();
+        uint64_t *d_first = d[movi_index::kB].as<uint64_t>();
+        int rc = device(d[movi_index::kBases].as<uint8_t>(), d_offs, nr, nb, d[movi_index::kOut].ptr(), d_n, d[movi_index::kErr].as<uint8_t>());
         if (rc) return rc;
         // compaction on the device: the per-read counts' prefix, then only the results found come down
         HIP_TRY(launch_count_scan(d_n, nr, d_first, nullptr));
         DevStats h{};
-        HIP_TRY(hipMemcpy(&h, ix->d_stats, sizeof(h), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&h, ix->d_stats.get(), sizeof(h), hipMemcpyDeviceToHost));
         uint64_t found = 0;
         HIP_TRY(hipMemcpy(o.h_n + first, d_n, nr * 4, hipMemcpyDeviceToHost));
         if (o.h_second) HIP_TRY(hipMemcpy(o.h_second + first, d_n + nr, nr * 4, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(&found, d_first + nr, 8, hipMemcpyDeviceToHost));
         if (!overflow && total + found <= o.cap) {
             if (found) {
-                HIP_TRY(grow(&d[movi_index::kS], &cap[movi_index::kS], found * o.elem_bytes));
-                HIP_TRY(launch_gather(d[movi_index::kOut], o.elem_bytes, d_offs, d_n, nr, d_first, d[movi_index::kS], nullptr));
-                HIP_TRY(hipMemcpy(static_cast<uint8_t *>(o.h_out) + total * o.elem_bytes, d[movi_index::kS], found * o.elem_bytes, hipMemcpyDeviceToHost));
+                HIP_TRY(grow(d[movi_index::kS], found * o.elem_bytes));
+                HIP_TRY(launch_gather(d[movi_index::kOut].ptr(), o.elem_bytes, d_offs, d_n, nr, d_first, d[movi_index::kS].ptr(), nullptr));
+                HIP_TRY(hipMemcpy(static_cast<uint8_t *>(o.h_out) + total * o.elem_bytes, d[movi_index::kS].ptr(), found * o.elem_bytes, hipMemcpyDeviceToHost));
             }
         } else overflow = true;
-        if (o.h_read_err) HIP_TRY(hipMemcpy(o.h_read_err + first, d[movi_index::kErr], nr, hipMemcpyDeviceToHost));
+        if (o.h_read_err) HIP_TRY(hipMemcpy(o.h_read_err + first, d[movi_index::kErr].ptr(), nr, hipMemcpyDeviceToHost));
         total += found;
         errors += h.errors;
         if (stats) add_stats(stats, nb, h);
@@ -2004,10 +1897,9 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
         ctx.ix = ix;
         ctx.seg_verdict = &seg_verdict;
         ctx.s = sl.s;
-        ctx.d_stats = sl.d_stats;
+        ctx.d_stats = sl.d_stats.get();
         ctx.d = sl.d;
-        ctx.cap = sl.cap;
-        ctx.h_small = sl.h + off_small(nr);
+        ctx.h_small = sl.h.as<uint8_t>() + off_small(nr);
         ctx.seg_ws = &sl.seg_ws;
         ctx.async = true;
         ctx.first = fl[k].c.first;
@@ -2023,10 +1915,11 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
         f.stage = 0;
         HIP_TRY(hipStreamSynchronize(sl.s));
         DevStats h;
-        memcpy(&h, sl.h + off_stats(f.c.nr, f.c.nb), sizeof(h));
+        const uint8_t *blk = sl.h.as<uint8_t>();
+        memcpy(&h, blk + off_stats(f.c.nr, f.c.nb), sizeof(h));
         add_stats(&acc, f.c.nb, h);
-        if (h_read_err) memcpy(h_read_err + f.c.first, sl.h + off_err(f.c.nr), f.c.nr);
-        harvest(sl.h + off_small(f.c.nr), f.c.first, f.c.nr, &grp[k]);
+        if (h_read_err) memcpy(h_read_err + f.c.first, blk + off_err(f.c.nr), f.c.nr);
+        harvest(blk + off_small(f.c.nr), f.c.first, f.c.nr, &grp[k]);
         return MOVI_OK;
     };
     // chunk c goes up into slot k and is walked
@@ -2038,26 +1931,19 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
         if (!sl.ev) HIP_TRY(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
         if (!sl.ev_up) HIP_TRY(hipEventCreateWithFlags(&sl.ev_up, hipEventDisableTiming));
         if (!ix->pipe_up) HIP_TRY(create_upload_stream(&ix->pipe_up));
-        if (!sl.d_stats) HIP_TRY(hipMalloc(&sl.d_stats, sizeof(DevStats)));
-        const size_t hb = off_stats(c.nr, c.nb) + sizeof(DevStats);
-        if (sl.h_cap < hb) {
-            if (sl.h) (void)hipHostFree(sl.h);
-            sl.h = nullptr;
-            sl.h_cap = 0;
-            const size_t want = hb + (hb >> 2);
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&sl.h), want, hipHostMallocDefault));
-            sl.h_cap = want;
-        }
+        if (!sl.d_stats) HIP_TRY(dev_alloc(sl.d_stats, sizeof(DevStats)));
+        HIP_TRY(grow_block(sl.h, off_stats(c.nr, c.nb) + sizeof(DevStats)));
         fl[k].c = c;
         ChunkCtx ctx = ctx_of(k, c.nr);
-        struct { void *p; } d_bases{}, d_offs{}, d_err{}, d_packed{};
-        if (all) d_bases.p = all + (c.b0 - chunks[0].b0);
-        else HIP_TRY(ctx.alloc(movi_index::kBases, c.nb, &d_bases.p));
-        if (all_packed) d_packed.p = all_packed + ((c.b0 >> 2) - (chunks[0].b0 >> 2));
-        else if (src.two_bit) HIP_TRY(ctx.alloc(movi_index::kPacked, src.up_bytes(c.b0, c.nb), &d_packed.p));
-        HIP_TRY(ctx.alloc(movi_index::kOffs, (c.nr + 1) * 8, &d_offs.p));
-        HIP_TRY(ctx.alloc(movi_index::kErr, c.nr, &d_err.p));
-        uint64_t *rel = reinterpret_cast<uint64_t *>(sl.h);
+        uint8_t *d_bases = nullptr, *d_err = nullptr, *d_packed = nullptr;
+        uint64_t *d_offs = nullptr;
+        if (all) d_bases = all + (c.b0 - chunks[0].b0);
+        else HIP_TRY(ctx.alloc(movi_index::kBases, c.nb, &d_bases));
+        if (all_packed) d_packed = all_packed + ((c.b0 >> 2) - (chunks[0].b0 >> 2));
+        else if (src.two_bit) HIP_TRY(ctx.alloc(movi_index::kPacked, src.up_bytes(c.b0, c.nb), &d_packed));
+        HIP_TRY(ctx.alloc(movi_index::kOffs, (c.nr + 1) * 8, &d_offs));
+        HIP_TRY(ctx.alloc(movi_index::kErr, c.nr, &d_err));
+        uint64_t *rel = sl.h.as<uint64_t>();
         uint64_t longest = 0;
         for (uint64_t i = 0; i <= c.nr; i++) {
             rel[i] = h_offsets[c.first + i] - c.b0;
@@ -2069,20 +1955,18 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
         // (the upload stream carries the bases alone, copy behind copy: with the chunk's offsets in between, every chunk left it idle for
         // ~40 us -- a fifth of a 9.4 MB copy; the offsets go up on the chunk's own stream, ahead of its walk: profiles/r06_host_path.txt)
         if (!all) {
-            if (c.nb) HIP_TRY(hipMemcpyAsync(src.two_bit ? d_packed.p : d_bases.p, src.up_from(c.b0), src.up_bytes(c.b0, c.nb), hipMemcpyHostToDevice, ix->pipe_up));
+            if (c.nb) HIP_TRY(hipMemcpyAsync(src.two_bit ? d_packed : d_bases, src.up_from(c.b0), src.up_bytes(c.b0, c.nb), hipMemcpyHostToDevice, ix->pipe_up));
             HIP_TRY(hipEventRecord(sl.ev_up, ix->pipe_up));
-            HIP_TRY(hipMemcpyAsync(d_offs.p, rel, (c.nr + 1) * 8, hipMemcpyHostToDevice, sl.s));
+            HIP_TRY(hipMemcpyAsync(d_offs, rel, (c.nr + 1) * 8, hipMemcpyHostToDevice, sl.s));
         } else {
             // (by a kernel that reads the slot's page-locked block, not by the copy engine: that one has the whole call's reads queued)
-            HIP_TRY(launch_copy_words(static_cast<uint64_t *>(d_offs.p), rel, c.nr + 1, sl.s));
+            HIP_TRY(launch_copy_words(d_offs, rel, c.nr + 1, sl.s));
         }
         HIP_TRY(hipStreamWaitEvent(sl.s, all ? ix->pipe_ev[ci] : sl.ev_up, 0));
         // (packed calls: the chunk's own stream unpacks what has arrived into the place the ASCII copy lands in; the upload stream carries copies alone)
         if (src.two_bit)
-            HIP_TRY(unpack_chunk(src, ix->scratch[movi_index::kExcPos], ix->scratch[movi_index::kExcByte], d_packed.p, c.b0, c.nb, d_bases.p, sl.s));
-        if (int rc = launch(ctx, static_cast<const uint8_t *>(d_bases.p), static_cast<const uint64_t *>(d_offs.p), c.nr, c.nb,
-                            static_cast<uint8_t *>(d_err.p)))
-            return rc;
+            HIP_TRY(unpack_chunk(src, ix->scratch[movi_index::kExcPos].ptr(), ix->scratch[movi_index::kExcByte].ptr(), d_packed, c.b0, c.nb, d_bases, sl.s));
+        if (int rc = launch(ctx, d_bases, d_offs, c.nr, c.nb, d_err)) return rc;
         HIP_TRY(hipEventRecord(sl.ev, sl.s));
         return MOVI_OK;
     };
@@ -2093,8 +1977,8 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
         HIP_TRY(hipEventSynchronize(sl.ev));
         ChunkCtx ctx = ctx_of(k, c.nr);
         if (int rc = fetch(ctx, c.first, c.nr, c.b0, c.nb)) return rc;
-        HIP_TRY(hipMemcpyAsync(sl.h + off_err(c.nr), sl.d[movi_index::kErr], c.nr, hipMemcpyDeviceToHost, sl.s));
-        HIP_TRY(hipMemcpyAsync(sl.h + off_stats(c.nr, c.nb), sl.d_stats, sizeof(DevStats), hipMemcpyDeviceToHost, sl.s));
+        HIP_TRY(hipMemcpyAsync(sl.h.as<uint8_t>() + off_err(c.nr), sl.d[movi_index::kErr].ptr(), c.nr, hipMemcpyDeviceToHost, sl.s));
+        HIP_TRY(hipMemcpyAsync(sl.h.as<uint8_t>() + off_stats(c.nr, c.nb), sl.d_stats.get(), sizeof(DevStats), hipMemcpyDeviceToHost, sl.s));
         fl[k].stage = 2;
         return MOVI_OK;
     };
@@ -2123,10 +2007,10 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
     if (src.two_bit && src.n_exc) {                           // the call's exception list, once, ahead of every chunk's bytes on the upload stream
         hipError_t e = hipSuccess;
         if (!ix->pipe_up) e = create_upload_stream(&ix->pipe_up);
-        if (e == hipSuccess) e = grow(&ix->scratch[movi_index::kExcPos], &ix->scratch_cap[movi_index::kExcPos], (size_t)src.n_exc * 8);
-        if (e == hipSuccess) e = grow(&ix->scratch[movi_index::kExcByte], &ix->scratch_cap[movi_index::kExcByte], (size_t)src.n_exc);
-        if (e == hipSuccess) e = hipMemcpyAsync(ix->scratch[movi_index::kExcPos], src.exc_pos, (size_t)src.n_exc * 8, hipMemcpyHostToDevice, ix->pipe_up);
-        if (e == hipSuccess) e = hipMemcpyAsync(ix->scratch[movi_index::kExcByte], src.exc_byte, (size_t)src.n_exc, hipMemcpyHostToDevice, ix->pipe_up);
+        if (e == hipSuccess) e = grow(ix->scratch[movi_index::kExcPos], (size_t)src.n_exc * 8);
+        if (e == hipSuccess) e = grow(ix->scratch[movi_index::kExcByte], (size_t)src.n_exc);
+        if (e == hipSuccess) e = hipMemcpyAsync(ix->scratch[movi_index::kExcPos].ptr(), src.exc_pos, (size_t)src.n_exc * 8, hipMemcpyHostToDevice, ix->pipe_up);
+        if (e == hipSuccess) e = hipMemcpyAsync(ix->scratch[movi_index::kExcByte].ptr(), src.exc_byte, (size_t)src.n_exc, hipMemcpyHostToDevice, ix->pipe_up);
         if (e != hipSuccess) {
             if (ix->pipe_up) (void)hipStreamSynchronize(ix->pipe_up);
             return fail_hip(e, "uploading the exception list");
@@ -2135,17 +2019,16 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
     if (n > 1 && total <= (1ull << 31) && !vector_down) {
         hipError_t e = hipSuccess;
         if (!ix->pipe_up) e = create_upload_stream(&ix->pipe_up);
-        if (e == hipSuccess) e = grow(&ix->scratch[movi_index::kBases], &ix->scratch_cap[movi_index::kBases], total);
-        if (e == hipSuccess && src.two_bit)
-            e = grow(&ix->scratch[movi_index::kPacked], &ix->scratch_cap[movi_index::kPacked], src.up_bytes(chunks[0].b0, total));
+        if (e == hipSuccess) e = grow(ix->scratch[movi_index::kBases], total);
+        if (e == hipSuccess && src.two_bit) e = grow(ix->scratch[movi_index::kPacked], src.up_bytes(chunks[0].b0, total));
         while (e == hipSuccess && ix->pipe_ev.size() < n) {
             hipEvent_t ev = nullptr;
             e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
             if (e == hipSuccess) ix->pipe_ev.push_back(ev);
         }
         if (e == hipSuccess) {
-            all = static_cast<uint8_t *>(ix->scratch[movi_index::kBases]);
-            if (src.two_bit) all_packed = static_cast<uint8_t *>(ix->scratch[movi_index::kPacked]);
+            all = ix->scratch[movi_index::kBases].as<uint8_t>();
+            if (src.two_bit) all_packed = ix->scratch[movi_index::kPacked].as<uint8_t>();
             for (size_t i = 0; i < n && e == hipSuccess; i++) {
                 const Chunk &c = chunks[i];
                 // (packed: the bytes that cover the chunk; a byte that two chunks share goes up with both, to the same place)
@@ -2341,7 +2224,7 @@ static int ml_host(bool zml, movi_index_t *ix, const ReadSource &src, const uint
     uint64_t acc_all = 0, acc_mask = 0;                       // bases launched so far / of them by the mask route
     std::unordered_map<uint64_t, Way> way_of;                 // first read of a chunk -> its way (launch, fetch and harvest run on the calling thread)
     const int threads = ix->host_threads > 0 ? ix->host_threads : host_threads_default();
-    struct { void *p; } d_out{};
+    uint16_t *d_out = nullptr;
     auto phase_of = [&](uint64_t b0) { return (uint32_t)((b0 - o0) & 31u); };
     auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
         Way w;
@@ -2357,24 +2240,20 @@ static int ml_host(bool zml, movi_index_t *ix, const ReadSource &src, const uint
         if (w.masks) {
             MaskArgs m;
             m.phase = w.phase;
-            HIP_TRY(c.alloc(movi_index::kMask, (size_t)pml_mask_words(nr, nb, m.phase) * 4, &d_out.p));
-            m.words = static_cast<uint32_t *>(d_out.p);
+            HIP_TRY(c.alloc(movi_index::kMask, (size_t)pml_mask_words(nr, nb, m.phase) * 4, &m.words));
             return ml_device(false, ix, db, dof, nr, nb, nullptr, derr, nullptr, c.s, ClsArgs(), c.d_stats, c.seg_ws, c.ragged_hint,
-                             c.seg_verdict, &m, &c.d[movi_index::kTmp], &c.cap[movi_index::kTmp]);
+                             c.seg_verdict, &m, &c.d[movi_index::kTmp]);
         }
-        HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_out.p));
+        HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_out));
         // (the vector itself comes down: on the device it is written through reset masks where movi_pml_device's policy says so)
         if (through_masks || (!zml && ix->pml_via_mask > 0)) {
-            void *mw = nullptr;
-            HIP_TRY(c.alloc(movi_index::kMask, (size_t)pml_mask_words(nr, nb, 0) * 4, &mw));
             MaskArgs m;
-            m.words = static_cast<uint32_t *>(mw);
-            m.expand_out = static_cast<uint16_t *>(d_out.p);
+            HIP_TRY(c.alloc(movi_index::kMask, (size_t)pml_mask_words(nr, nb, 0) * 4, &m.words));
+            m.expand_out = d_out;
             return ml_device(false, ix, db, dof, nr, nb, nullptr, derr, nullptr, c.s, ClsArgs(), c.d_stats, c.seg_ws, c.ragged_hint,
                              c.seg_verdict, &m);
         }
-        return ml_device(zml, ix, db, dof, nr, nb, static_cast<uint16_t *>(d_out.p), derr, nullptr, c.s, ClsArgs(), c.d_stats,
-                         c.seg_ws, c.ragged_hint, c.seg_verdict);
+        return ml_device(zml, ix, db, dof, nr, nb, d_out, derr, nullptr, c.s, ClsArgs(), c.d_stats, c.seg_ws, c.ragged_hint, c.seg_verdict);
     };
     // what a chunk's masks are to the host: the words land in `words`; they are the result, or the vector is expanded from them
     auto deliver = [&](const uint32_t *words, uint64_t first, uint64_t nr, uint32_t ph, HostPool::Group *g) {
@@ -2397,7 +2276,7 @@ static int ml_host(bool zml, movi_index_t *ix, const ReadSource &src, const uint
             if (c.async) {
                 // into the slot's page-locked block, and on to the worker pool by a host function on the chunk's stream -- the moment the
                 // words have arrived, not when the calling thread's loop next comes by (with 8 chunks per call the pool ran at 2/3 duty)
-                HIP_TRY(c.down_small(nullptr, 0, c.d[movi_index::kMask], nw * 4));
+                HIP_TRY(c.down_small(nullptr, 0, c.d[movi_index::kMask].ptr(), nw * 4));
                 DeliverArg *a = new DeliverArg;
                 a->words = reinterpret_cast<const uint32_t *>(c.h_small);
                 a->mask_dst = h_mask_words ? h_mask_words + ((b0 - o0) >> 5) + first : nullptr;
@@ -2413,15 +2292,15 @@ static int ml_host(bool zml, movi_index_t *ix, const ReadSource &src, const uint
                 return MOVI_OK;
             }
             if (h_mask_words && !h_out_pml) {                 // straight to where they belong
-                HIP_TRY(hipMemcpy(h_mask_words + ((b0 - o0) >> 5) + first, c.d[movi_index::kMask], nw * 4, hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(h_mask_words + ((b0 - o0) >> 5) + first, c.d[movi_index::kMask].ptr(), nw * 4, hipMemcpyDeviceToHost));
                 return MOVI_OK;
             }
             sync_words.resize(nw);
-            HIP_TRY(hipMemcpy(sync_words.data(), c.d[movi_index::kMask], nw * 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(sync_words.data(), c.d[movi_index::kMask].ptr(), nw * 4, hipMemcpyDeviceToHost));
             deliver(sync_words.data(), first, nr, w.phase, nullptr);
             return MOVI_OK;
         }
-        if (h_out_pml) HIP_TRY(c.down(h_out_pml + b0, c.d[movi_index::kOut], nb * 2));
+        if (h_out_pml) HIP_TRY(c.down(h_out_pml + b0, c.d[movi_index::kOut].ptr(), nb * 2));
         return MOVI_OK;
     };
     auto harvest = [&](const uint8_t *h_small, uint64_t first, uint64_t nr, HostPool::Group *g) {
@@ -2516,22 +2395,22 @@ int movi_pml_logs_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t 
         return fail(MOVI_ERR_ARG, "NULL host buffer");
     if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
     HIP_TRY(hipSetDevice(ix->device));
-    struct { void *p; } d_out{}, d_ff{}, d_sc{};
+    uint16_t *d_out = nullptr, *d_ff = nullptr, *d_sc = nullptr;
     auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
-        HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_out.p));
-        HIP_TRY(c.alloc(movi_index::kA, nb * 2, &d_ff.p));
-        HIP_TRY(c.alloc(movi_index::kS, nb * 2, &d_sc.p));
-        HIP_TRY(hipMemsetAsync(d_ff.p, 0, nb * 2, c.s));               // a read of one base has no LF: its entry stays 0
-        HIP_TRY(hipMemsetAsync(d_sc.p, 0, nb * 2, c.s));
+        HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_out));
+        HIP_TRY(c.alloc(movi_index::kA, nb * 2, &d_ff));
+        HIP_TRY(c.alloc(movi_index::kS, nb * 2, &d_sc));
+        HIP_TRY(hipMemsetAsync(d_ff, 0, nb * 2, c.s));                 // a read of one base has no LF: its entry stays 0
+        HIP_TRY(hipMemsetAsync(d_sc, 0, nb * 2, c.s));
         ClsArgs logs;
-        logs.log_ff = static_cast<uint16_t *>(d_ff.p);
-        logs.log_scan = static_cast<uint16_t *>(d_sc.p);
-        return ml_device(false, ix, db, dof, nr, nb, static_cast<uint16_t *>(d_out.p), derr, nullptr, c.s, logs, c.d_stats);
+        logs.log_ff = d_ff;
+        logs.log_scan = d_sc;
+        return ml_device(false, ix, db, dof, nr, nb, d_out, derr, nullptr, c.s, logs, c.d_stats);
     };
     auto fetch = [&](ChunkCtx &c, uint64_t, uint64_t, uint64_t b0, uint64_t nb) -> int {
-        HIP_TRY(c.down(h_out_pml + b0, c.d[movi_index::kOut], nb * 2));
-        HIP_TRY(c.down(h_fastforwards + b0, c.d[movi_index::kA], nb * 2));
-        HIP_TRY(c.down(h_scans + b0, c.d[movi_index::kS], nb * 2));
+        HIP_TRY(c.down(h_out_pml + b0, c.d[movi_index::kOut].ptr(), nb * 2));
+        HIP_TRY(c.down(h_fastforwards + b0, c.d[movi_index::kA].ptr(), nb * 2));
+        HIP_TRY(c.down(h_scans + b0, c.d[movi_index::kS].ptr(), nb * 2));
         return MOVI_OK;
     };
     auto harvest = [](const uint8_t *, uint64_t, uint64_t, HostPool::Group *) {};
@@ -2613,21 +2492,21 @@ int movi_pml_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uint6
     if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
     if (bin_width == 0) return fail(MOVI_ERR_ARG, "bin_width must be > 0");
     HIP_TRY(hipSetDevice(ix->device));
-    struct { void *p; } d_a{}, d_b{}, d_s{};
+    uint32_t *d_a = nullptr, *d_b = nullptr;
+    uint64_t *d_s = nullptr;
     auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
-        HIP_TRY(c.alloc(movi_index::kA, nr * 4, &d_a.p));
-        HIP_TRY(c.alloc(movi_index::kB, nr * 4, &d_b.p));
-        HIP_TRY(c.alloc(movi_index::kS, nr * 8, &d_s.p));
+        HIP_TRY(c.alloc(movi_index::kA, nr * 4, &d_a));
+        HIP_TRY(c.alloc(movi_index::kB, nr * 4, &d_b));
+        HIP_TRY(c.alloc(movi_index::kS, nr * 8, &d_s));
         // bins reduced inside the PML kernel; no PML vector is written at all
-        return pml_classify_device(ix, db, dof, nr, nb, bin_width, max_value_thr, nullptr, static_cast<uint32_t *>(d_a.p),
-                                   static_cast<uint32_t *>(d_b.p), static_cast<uint64_t *>(d_s.p), derr, nullptr, c.s,
+        return pml_classify_device(ix, db, dof, nr, nb, bin_width, max_value_thr, nullptr, d_a, d_b, d_s, derr, nullptr, c.s,
                                    c.d_stats, c.seg_ws, c.ragged_hint, c.seg_verdict);
     };
     // page-locked block of a chunk in flight: sum_max[nr] | above[nr] | below[nr]
     auto fetch = [&](ChunkCtx &c, uint64_t first, uint64_t nr, uint64_t, uint64_t) -> int {
-        HIP_TRY(c.down_small(h_sum_max + first, 0, c.d[movi_index::kS], nr * 8));
-        HIP_TRY(c.down_small(h_bins_above + first, nr * 8, c.d[movi_index::kA], nr * 4));
-        HIP_TRY(c.down_small(h_bins_below + first, nr * 12, c.d[movi_index::kB], nr * 4));
+        HIP_TRY(c.down_small(h_sum_max + first, 0, c.d[movi_index::kS].ptr(), nr * 8));
+        HIP_TRY(c.down_small(h_bins_above + first, nr * 8, c.d[movi_index::kA].ptr(), nr * 4));
+        HIP_TRY(c.down_small(h_bins_below + first, nr * 12, c.d[movi_index::kB].ptr(), nr * 4));
         return MOVI_OK;
     };
     auto harvest = [&](const uint8_t *h, uint64_t first, uint64_t nr, HostPool::Group *) {
@@ -2647,15 +2526,13 @@ int movi_pml_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uint6
 static int ensure_ckpt(movi_index *ix, hipStream_t s) {
     if (ix->d_ckpt) return MOVI_OK;
     const uint64_t n_chunks = (ix->desc.r + (1ull << kPrefixShift) - 1) >> kPrefixShift;
-    HIP_TRY(hipMalloc(&ix->d_ckpt, (n_chunks + 1) * sizeof(uint64_t)));
-    hipError_t e = build_row_start_ckpt(ix->kmode, ix->d_rows, ix->desc.r, ix->d_ckpt, s);
+    DevPtr<uint64_t> ckpt;
+    HIP_TRY(dev_alloc(ckpt, (n_chunks + 1) * sizeof(uint64_t)));
+    hipError_t e = build_row_start_ckpt(ix->kmode, ix->d_rows.get(), ix->desc.r, ckpt.get(), s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);        // other streams (the overlapped host path) may use it next
-    if (e != hipSuccess) {
-        (void)hipFree(ix->d_ckpt);
-        ix->d_ckpt = nullptr;
-        return fail_hip(e, "building the row-start checkpoints");
-    }
-    ix->dev.row_start_ckpt = ix->d_ckpt;
+    if (e != hipSuccess) return fail_hip(e, "building the row-start checkpoints");
+    ix->d_ckpt = std::move(ckpt);
+    ix->dev.row_start_ckpt = ix->d_ckpt.get();
     return MOVI_OK;
 }
 
@@ -2682,11 +2559,7 @@ static int ensure_count_tables(movi_index *ix, hipStream_t s, bool from_prepare 
         else if (ix->dev.rows2_count == 0u) {
             // (the copy's own tally -- every row, not a sample -- says the count query is better off on the plain rows: the copy
             // is not kept for a caller who may never ask for PMLs; the first PML query builds it again, 85 us per 14 M rows)
-            ix->dev.rows2 = nullptr;
-            ix->dev.rows2_tail = 0;
-            ix->dev.hints = 0;
-            (void)hipFree(ix->d_rows2);
-            ix->d_rows2 = nullptr;
+            drop_ahead(ix);
             ix->count_declined_ahead = true;
         }
     }
@@ -2699,7 +2572,7 @@ static int count_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t
     if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
     if (n_reads == 0) return MOVI_OK;
     if (!d_offsets || !d_matched || !d_count || (n_bases && !d_bases)) return fail(MOVI_ERR_ARG, "NULL device buffer");
-    if (!d_stats) d_stats = ix->d_stats;
+    if (!d_stats) d_stats = ix->d_stats.get();
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc = ensure_count_tables(ix, s);
@@ -2736,9 +2609,9 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
         (void)hipGetLastError();
         // movi_pml_device's mask words for a default batch (a bigger "reserve_device_masks" stays): its first call allocates nothing.
         // No room is no failure -- an uncaptured call grows them, a captured one takes the packer route
-        if (grow_dmask(ix, (size_t)pml_mask_words(kPrepareMaskReads, kPrepareMaskBases, 0) * 4) != hipSuccess) (void)hipGetLastError();
+        if (grow(ix->dmask, (size_t)pml_mask_words(kPrepareMaskReads, kPrepareMaskBases, 0) * 4) != hipSuccess) (void)hipGetLastError();
         // ... and the park queue of the same batch, where calls on this handle can park ("park_lanes"; no room: such calls park nothing)
-        if (park_lanes_wanted(ix) > 0 && grow_dpark(ix, park_queue_bytes(kPrepareMaskReads, park_lanes_wanted(ix))) != hipSuccess) (void)hipGetLastError();
+        if (park_lanes_wanted(ix) > 0 && grow(ix->dpark, park_queue_bytes(kPrepareMaskReads, park_lanes_wanted(ix))) != hipSuccess) (void)hipGetLastError();
     }
     if (what & MOVI_PREPARE_COUNT) {
         const int rc = ensure_count_tables(ix, s, true);
@@ -2751,7 +2624,7 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
     }
     if (what & MOVI_PREPARE_COLOR) {
         // the counter scratch of movi_multi_classify_device and its kernel's code object: the call then allocates nothing
-        if (hipError_t e = grow_color_scratch(ix); e != hipSuccess) return fail_hip(e, "reserving the counter scratch of --multi-classify");
+        if (hipError_t e = reserve_color_scratch(ix); e != hipSuccess) return fail_hip(e, "reserving the counter scratch of --multi-classify");
         (void)preload_color(ix->kmode, ix->dev.idx32 != 0);
         (void)hipGetLastError();
     }
@@ -2774,17 +2647,16 @@ int movi_count_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_
         return fail(MOVI_ERR_ARG, "NULL host buffer");
     if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
     HIP_TRY(hipSetDevice(ix->device));
-    struct { void *p; } d_m{}, d_c{};
+    uint64_t *d_m = nullptr, *d_c = nullptr;
     auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
-        HIP_TRY(c.alloc(movi_index::kA, nr * 8, &d_m.p));
-        HIP_TRY(c.alloc(movi_index::kS, nr * 8, &d_c.p));
-        return count_device(ix, db, dof, nr, nb, static_cast<uint64_t *>(d_m.p), static_cast<uint64_t *>(d_c.p), derr,
-                            nullptr, c.s, c.d_stats);
+        HIP_TRY(c.alloc(movi_index::kA, nr * 8, &d_m));
+        HIP_TRY(c.alloc(movi_index::kS, nr * 8, &d_c));
+        return count_device(ix, db, dof, nr, nb, d_m, d_c, derr, nullptr, c.s, c.d_stats);
     };
     // page-locked block of a chunk in flight: matched[nr] | count[nr]
     auto fetch = [&](ChunkCtx &c, uint64_t first, uint64_t nr, uint64_t, uint64_t) -> int {
-        HIP_TRY(c.down_small(h_matched + first, 0, c.d[movi_index::kA], nr * 8));
-        HIP_TRY(c.down_small(h_count + first, nr * 8, c.d[movi_index::kS], nr * 8));
+        HIP_TRY(c.down_small(h_matched + first, 0, c.d[movi_index::kA].ptr(), nr * 8));
+        HIP_TRY(c.down_small(h_count + first, nr * 8, c.d[movi_index::kS].ptr(), nr * 8));
         return MOVI_OK;
     };
     auto harvest = [&](const uint8_t *h, uint64_t first, uint64_t nr, HostPool::Group *) {
@@ -2829,12 +2701,12 @@ int mem_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_offsets
     HIP_TRY(hipSetDevice(ix->device));
     int rc = ensure_count_tables(ix, s);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ix->d_stats, 0, sizeof(DevStats), s));
+    HIP_TRY(hipMemsetAsync(ix->d_stats.get(), 0, sizeof(DevStats), s));
     MemArgs a{};
     a.comp = complement_codes(ix->desc);
     a.min_len = min_len > 1u ? min_len : 1u;
     HIP_TRY(launch_mem(ix->kmode, ix->dev, a, d_bases, d_offsets, n_reads, reinterpret_cast<MemOut *>(d_mems), d_n_mems,
-                       d_read_err, ix->d_stats, d_read_order, s, &ix->last_launch));
+                       d_read_err, ix->d_stats.get(), d_read_order, s, &ix->last_launch));
     return MOVI_OK;
 }
 
@@ -2898,12 +2770,12 @@ int kmer_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_offset
     HIP_TRY(hipSetDevice(ix->device));
     int rc = ensure_count_tables(ix, s);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ix->d_stats, 0, sizeof(DevStats), s));
+    HIP_TRY(hipMemsetAsync(ix->d_stats.get(), 0, sizeof(DevStats), s));
     KmerArgs a{};
     a.k = k;
     a.step = kmer_look_step(k, ix->desc.length, ix->cfg.kmer_lookahead);
     HIP_TRY(launch_kmer(ix->kmode, ix->dev, a, d_bases, d_offsets, n_reads, reinterpret_cast<KmerRun *>(d_runs), d_n_runs, d_found,
-                        d_read_err, ix->d_stats, d_read_order, s, &ix->last_launch));
+                        d_read_err, ix->d_stats.get(), d_read_order, s, &ix->last_launch));
     return MOVI_OK;
 }
 
@@ -2941,18 +2813,16 @@ int movi_kmer_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_o
 
 namespace {
 
-void detach_ssa(movi_index *ix) {
-    if (ix->d_loc) (void)hipFree(ix->d_loc);
-    if (ix->d_samples) (void)hipFree(ix->d_samples);
-    ix->d_loc = nullptr;
-    ix->d_samples = nullptr;
+void drop_ssa(movi_index *ix) {
+    ix->d_loc.reset();
+    ix->d_samples.reset();
     ix->sa_rate = 0;
 }
 
 LocArgs loc_args(const movi_index *ix) {
     LocArgs a;
-    a.rows = ix->d_loc;
-    a.samples = ix->d_samples;
+    a.rows = ix->d_loc.get();
+    a.samples = ix->d_samples.get();
     a.n = ix->desc.length;
     a.n_entries = ix->desc.length / ix->sa_rate + 1;
     a.rate = (uint32_t)ix->sa_rate;
@@ -2966,17 +2836,19 @@ int attach_ssa(movi_index *ix, uint64_t rate, hipStream_t s) {
     if (ix->desc.r + 1 > 0x7FFFFFFFull)
         return fail(MOVI_ERR_ARG, "a sampled suffix array cannot be attached to a table of 2^31 - 1 rows or more yet (the prefix sum over the row "
                                   "lengths is one 32-bit-indexed device scan)");
-    detach_ssa(ix);
+    drop_ssa(ix);
     const uint64_t entries = ix->desc.length / rate + 1;
-    hipError_t e = hipMalloc(&ix->d_loc, locate_rows_bytes(ix->desc.r));
-    if (e == hipSuccess) e = hipMalloc(&ix->d_samples, entries * 8);
+    DevPtr<uint4> loc;
+    DevPtr<uint64_t> samples;
+    hipError_t e = dev_alloc(loc, locate_rows_bytes(ix->desc.r));
+    if (e == hipSuccess) e = dev_alloc(samples, entries * 8);
     uint64_t n_total = 0;
-    if (e == hipSuccess) e = build_locate_rows(ix->kmode, ix->dev, rate, ix->d_loc, &n_total, s);
-    if (e != hipSuccess) { detach_ssa(ix); return fail_hip(e, "building the locate rows"); }    // an error, never a walk without them
-    if (n_total != ix->desc.length) {
-        detach_ssa(ix);
+    if (e == hipSuccess) e = build_locate_rows(ix->kmode, ix->dev, rate, loc.get(), &n_total, s);
+    if (e != hipSuccess) return fail_hip(e, "building the locate rows");                        // an error, never a walk without them
+    if (n_total != ix->desc.length)
         return fail(MOVI_ERR_INVARIANT, "the row lengths add up to " + std::to_string(n_total) + ", the index header says " + std::to_string(ix->desc.length));
-    }
+    ix->d_loc = std::move(loc);
+    ix->d_samples = std::move(samples);
     ix->sa_rate = rate;
     return MOVI_OK;
 }
@@ -2997,7 +2869,7 @@ int sa_entries_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_
     if (!d_offsets || (n_bases && (!d_bases || !d_sa))) return fail(MOVI_ERR_ARG, "NULL device buffer");
     if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
     HIP_TRY(hipSetDevice(ix->device));
-    if (!d_stats) d_stats = ix->d_stats;
+    if (!d_stats) d_stats = ix->d_stats.get();
     HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(DevStats), s));
     LaunchInfo pos_info;
     HIP_TRY(launch_sa_pos(ix->dev, d_bases, d_offsets, n_reads, d_pml, d_sa, d_err, d_stats, d_order, s, &pos_info));
@@ -3017,11 +2889,11 @@ int movi_ssa_build(movi_index_t *ix, uint64_t rate, void *stream) {
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (int rc = attach_ssa(ix, rate, s)) return rc;
     uint32_t bad = 0;
-    HIP_TRY(hipMemsetAsync(ix->d_stats, 0, sizeof(DevStats), s));
-    const hipError_t e = build_sampled_sa(ix->kmode, ix->dev, loc_args(ix), ix->d_samples, ix->d_stats, ix->cfg.num_cus, s, &bad, &ix->last_launch);
-    if (e != hipSuccess) { detach_ssa(ix); return fail_hip(e, "building the sampled suffix array"); }
+    HIP_TRY(hipMemsetAsync(ix->d_stats.get(), 0, sizeof(DevStats), s));
+    const hipError_t e = build_sampled_sa(ix->kmode, ix->dev, loc_args(ix), ix->d_samples.get(), ix->d_stats.get(), ix->cfg.num_cus, s, &bad, &ix->last_launch);
+    if (e != hipSuccess) { drop_ssa(ix); return fail_hip(e, "building the sampled suffix array"); }
     if (bad) {
-        detach_ssa(ix);
+        drop_ssa(ix);
         return fail(MOVI_ERR_INVARIANT, "the sampled positions do not form one cycle under LF (" + std::to_string(bad) + " finding(s)): corrupt index?");
     }
     return MOVI_OK;
@@ -3036,7 +2908,7 @@ int movi_ssa_get(const movi_index_t *ix, uint64_t *rate, uint64_t *h_samples, ui
     if (!h_samples) return MOVI_OK;
     if (cap < entries) return fail(MOVI_ERR_ARG, "the sampled suffix array has " + std::to_string(entries) + " entries, cap is " + std::to_string(cap));
     HIP_TRY(hipSetDevice(ix->device));
-    HIP_TRY(hipMemcpy(h_samples, ix->d_samples, entries * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h_samples, ix->d_samples.get(), entries * 8, hipMemcpyDeviceToHost));
     return MOVI_OK;
 }
 
@@ -3046,7 +2918,7 @@ int movi_ssa_save(movi_index_t *ix, const char *path) {
     HIP_TRY(hipSetDevice(ix->device));
     const uint64_t entries = ix->desc.length / ix->sa_rate + 1, r = ix->desc.r;
     std::vector<uint64_t> buf(entries);
-    HIP_TRY(hipMemcpy(buf.data(), ix->d_samples, entries * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(buf.data(), ix->d_samples.get(), entries * 8, hipMemcpyDeviceToHost));
     const std::string tmp = std::string(path) + ".tmp";                // renamed over `path` once complete: no partial ssa.movi
     FILE *f = fopen(tmp.c_str(), "wb");
     if (!f) return fail(MOVI_ERR_IO, std::string("cannot write ") + tmp);
@@ -3054,16 +2926,16 @@ int movi_ssa_save(movi_index_t *ix, const char *path) {
     bool ok = fwrite(&ix->sa_rate, 8, 1, f) == 1 && fwrite(&entries, 8, 1, f) == 1 && fwrite(buf.data(), 8, entries, f) == entries &&
               fwrite(&r, 8, 1, f) == 1;
     constexpr uint64_t kPiece = 1ull << 22;                            // all_p back out of the locate rows, piece by piece
-    void *d_piece = nullptr;
-    hipError_t e = ok ? hipMalloc(&d_piece, std::min(r, kPiece) * 8) : hipSuccess;
+    DevPtr<uint64_t> piece;
+    hipError_t e = ok ? dev_alloc(piece, std::min(r, kPiece) * 8) : hipSuccess;
     buf.resize(std::min(r, kPiece));
     for (uint64_t first = 0; ok && e == hipSuccess && first < r; first += kPiece) {
         const uint64_t cnt = std::min(kPiece, r - first);
-        e = locate_rows_all_p(ix->d_loc, first, cnt, ix->sa_rate, static_cast<uint64_t *>(d_piece), nullptr);
-        if (e == hipSuccess) e = hipMemcpy(buf.data(), d_piece, cnt * 8, hipMemcpyDeviceToHost);
+        e = locate_rows_all_p(ix->d_loc.get(), first, cnt, ix->sa_rate, piece.get(), nullptr);
+        if (e == hipSuccess) e = hipMemcpy(buf.data(), piece.get(), cnt * 8, hipMemcpyDeviceToHost);
         if (e == hipSuccess) ok = fwrite(buf.data(), 8, cnt, f) == cnt;
     }
-    if (d_piece) (void)hipFree(d_piece);
+    piece.reset();
     ok = (fclose(f) == 0) && ok;
     if (e == hipSuccess && ok) ok = std::rename(tmp.c_str(), path) == 0;
     else (void)std::remove(tmp.c_str());
@@ -3097,8 +2969,8 @@ int movi_ssa_load(movi_index_t *ix, const char *path) {
     HIP_TRY(hipSetDevice(ix->device));
     // (the file's all_p is not read: the locate rows hold the same prefix sums, recomputed from the table on the device)
     if (int rc = attach_ssa(ix, rate, nullptr)) return rc;
-    const hipError_t e = hipMemcpy(ix->d_samples, samples.data(), entries * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { detach_ssa(ix); return fail_hip(e, "uploading the sampled suffix array"); }
+    const hipError_t e = hipMemcpy(ix->d_samples.get(), samples.data(), entries * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { drop_ssa(ix); return fail_hip(e, "uploading the sampled suffix array"); }
     return MOVI_OK;
 }
 
@@ -3108,7 +2980,7 @@ int movi_locate_device(movi_index_t *ix, uint64_t *d_positions_inout, uint64_t n
     if (n_items == 0) return MOVI_OK;
     if (!d_positions_inout) return fail(MOVI_ERR_ARG, "NULL device buffer");
     HIP_TRY(hipSetDevice(ix->device));
-    return locate_device(ix, d_positions_inout, n_items, static_cast<hipStream_t>(stream), ix->d_stats, true);
+    return locate_device(ix, d_positions_inout, n_items, static_cast<hipStream_t>(stream), ix->d_stats.get(), true);
 }
 
 int movi_sa_entries_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
@@ -3128,16 +3000,16 @@ int movi_sa_entries_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_
     if (!h_offsets || (h_offsets[n_reads] != h_offsets[0] && (!h_bases || !h_out_sa))) return fail(MOVI_ERR_ARG, "NULL host buffer");
     if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
     HIP_TRY(hipSetDevice(ix->device));
-    struct { void *p; } d_pml{}, d_sa{};
+    uint16_t *d_pml = nullptr;
+    uint64_t *d_sa = nullptr;
     auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
-        if (h_out_pml) HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_pml.p));
-        HIP_TRY(c.alloc(movi_index::kS, nb * 8, &d_sa.p));
-        return sa_entries_device(ix, db, dof, nr, nb, h_out_pml ? static_cast<uint16_t *>(d_pml.p) : nullptr, static_cast<uint64_t *>(d_sa.p),
-                                 derr, nullptr, c.s, c.d_stats);
+        if (h_out_pml) HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_pml));
+        HIP_TRY(c.alloc(movi_index::kS, nb * 8, &d_sa));
+        return sa_entries_device(ix, db, dof, nr, nb, h_out_pml ? d_pml : nullptr, d_sa, derr, nullptr, c.s, c.d_stats);
     };
     auto fetch = [&](ChunkCtx &c, uint64_t, uint64_t, uint64_t b0, uint64_t nb) -> int {
-        if (h_out_pml) HIP_TRY(c.down(h_out_pml + b0, d_pml.p, nb * 2));
-        HIP_TRY(c.down(h_out_sa + b0, d_sa.p, nb * 8));
+        if (h_out_pml) HIP_TRY(c.down(h_out_pml + b0, d_pml, nb * 2));
+        HIP_TRY(c.down(h_out_sa + b0, d_sa, nb * 8));
         return MOVI_OK;
     };
     auto harvest = [](const uint8_t *, uint64_t, uint64_t, HostPool::Group *) {};
@@ -3151,11 +3023,9 @@ int movi_sa_entries_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_
 
 namespace {
 
-void detach_color(movi_index *ix) {
-    if (ix->d_color_flat) (void)hipFree(ix->d_color_flat);
-    if (ix->d_color_inds) (void)hipFree(ix->d_color_inds);
-    ix->d_color_flat = nullptr;
-    ix->d_color_inds = nullptr;
+void drop_color(movi_index *ix) {
+    ix->d_color_flat.reset();
+    ix->d_color_inds.reset();
     ix->color_flat.clear();
     ix->color_inds.clear();
     ix->color_taxa.clear();
@@ -3170,23 +3040,27 @@ int attach_color(movi_index *ix, const char *what) {
         bool ok = at < fs && at + 1 + ix->color_flat[at] <= fs;
         for (uint64_t k = 0; ok && k < ix->color_flat[at]; k++) ok = ix->color_flat[at + 1 + k] < ix->color_species;
         if (!ok) {
-            detach_color(ix);
+            drop_color(ix);
             return fail(MOVI_ERR_FORMAT, std::string(what) + ": the document set of run " + std::to_string(i) + " does not lie inside the flat colour table "
                                          "or names a document beyond num_species");
         }
     }
-    hipError_t e = hipMalloc(&ix->d_color_flat, std::max<size_t>(fs * 2, 8));
-    if (e == hipSuccess) e = hipMalloc(&ix->d_color_inds, ix->color_inds.size() * 8);
-    if (e == hipSuccess) e = hipMemcpy(ix->d_color_flat, ix->color_flat.data(), fs * 2, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(ix->d_color_inds, ix->color_inds.data(), ix->color_inds.size() * 8, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { detach_color(ix); return fail_hip(e, "uploading the colour tables"); }
+    DevPtr<uint16_t> flat;
+    DevPtr<uint64_t> inds;
+    hipError_t e = dev_alloc(flat, std::max<size_t>(fs * 2, 8));
+    if (e == hipSuccess) e = dev_alloc(inds, ix->color_inds.size() * 8);
+    if (e == hipSuccess) e = hipMemcpy(flat.get(), ix->color_flat.data(), fs * 2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(inds.get(), ix->color_inds.data(), ix->color_inds.size() * 8, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { drop_color(ix); return fail_hip(e, "uploading the colour tables"); }
+    ix->d_color_flat = std::move(flat);
+    ix->d_color_inds = std::move(inds);
     return MOVI_OK;
 }
 
 ColorTables color_tables(const movi_index *ix) {
     ColorTables ct;
-    ct.flat = ix->d_color_flat;
-    ct.inds = ix->d_color_inds;
+    ct.flat = ix->d_color_flat.get();
+    ct.inds = ix->d_color_inds.get();
     ct.flat_size = ix->color_flat.size();
     ct.num_species = ix->color_species;
     return ct;
@@ -3206,15 +3080,15 @@ int multi_classify_device(movi_index *ix, const uint8_t *d_bases, const uint64_t
     if (!d_offsets || !d_out || (n_bases && !d_bases)) return fail(MOVI_ERR_ARG, "NULL device buffer");
     if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
     HIP_TRY(hipSetDevice(ix->device));
-    if (!d_stats) d_stats = ix->d_stats;
+    if (!d_stats) d_stats = ix->d_stats.get();
     const uint64_t S = ix->color_species;
     if (d_scratch && scratch_cap < S * 4) return fail(MOVI_ERR_ARG, "counter scratch smaller than one read's counters");
-    if (!d_counts && !d_scratch && ix->color_scratch_cap < S * 4) {      // not prepared: the scratch is reserved here, outside a capture only
+    if (!d_counts && !d_scratch && ix->color_scratch.cap() < S * 4) {    // not prepared: the scratch is reserved here, outside a capture only
         if (stream_capturing(s)) return fail(MOVI_ERR_ARG, "movi_multi_classify_device under a stream capture needs movi_index_prepare(MOVI_PREPARE_COLOR) first");
-        HIP_TRY(grow_color_scratch(ix));
+        HIP_TRY(reserve_color_scratch(ix));
     }
     // reads go through the counters chunk by chunk: at most "color_scratch_bytes" of them are live at a time
-    if (!d_scratch) { d_scratch = ix->d_color_scratch; scratch_cap = ix->color_scratch_cap; }
+    if (!d_scratch) { d_scratch = ix->color_scratch.as<uint32_t>(); scratch_cap = ix->color_scratch.cap(); }
     const uint64_t budget = d_counts ? std::max<uint64_t>(ix->color_scratch_bytes, S * 4)
                                      : std::min<uint64_t>(scratch_cap, std::max<uint64_t>(ix->color_scratch_bytes, S * 4));
     const uint64_t chunk = std::max<uint64_t>(1, budget / (S * 4));
@@ -3254,7 +3128,7 @@ int movi_color_build(movi_index_t *ix, const uint64_t *doc_offsets, const uint32
     if (ix->desc.r + 1 > 0x7FFFFFFFull)
         return fail(MOVI_ERR_ARG, "the colour builder cannot run on a table of 2^31 - 1 rows or more yet (it walks from a sampled suffix array, whose "
                                   "locate rows need one 32-bit-indexed device scan)");
-    detach_color(ix);                                                    // (first: a build that fails leaves no tables attached, older ones included)
+    drop_color(ix);                                                      // (first: a build that fails leaves no tables attached, older ones included)
     if (!ix->sa_rate)                                                    // the text position of every BWT position comes from the samples
         if (int rc = movi_ssa_build(ix, 100, stream)) return rc;
     uint64_t *d_keys = nullptr, n_keys = 0, key_cap = 0;
@@ -3271,9 +3145,10 @@ int movi_color_build(movi_index_t *ix, const uint64_t *doc_offsets, const uint32
     if (bad)
         return fail(MOVI_ERR_INVARIANT, "the walks from the sampled suffix array do not visit every BWT position exactly once (" + std::to_string(bad) +
                                             " finding(s)): corrupt index, or a sampled suffix array of another index?");
+    DevPtr<uint64_t> keys_owner(d_keys);
     std::vector<uint64_t> keys(n_keys);
     const hipError_t e2 = hipMemcpy(keys.data(), d_keys, n_keys * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d_keys);
+    keys_owner.reset();
     if (e2 != hipSuccess) return fail_hip(e2, "reading the document sets back");
     // build_doc_sets, src/move_structure_color.cpp:57-63: a set gets its number at the first run, in run order, that has it -- and
     // flat_and_serialize_colors_vectors, src/move_structure_io.cpp:515-534: sets laid out in that order, size first
@@ -3366,7 +3241,7 @@ int movi_color_load(movi_index_t *ix, const char *path, uint32_t num_species) {
     if (!shape) return fail(MOVI_ERR_FORMAT, std::string(path) + ": a flat colour table of " + std::to_string(fs) + " entries and its length do not fit an index of " +
                                                  std::to_string(r) + " rows");
     HIP_TRY(hipSetDevice(ix->device));
-    detach_color(ix);
+    drop_color(ix);
     ix->color_inds.resize(r);
     for (uint64_t i = 0; i < r; i++) {
         uint32_t lo;
@@ -3397,23 +3272,24 @@ int movi_multi_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uin
     if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
     HIP_TRY(hipSetDevice(ix->device));
     const uint64_t S = ix->color_species;
-    struct { void *p; } d_o{}, d_c{}, d_pml{};
+    movi_mc_read_t *d_o = nullptr;
+    uint32_t *d_c = nullptr;
+    uint16_t *d_pml = nullptr;
     auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
-        HIP_TRY(c.alloc(movi_index::kA, nr * sizeof(movi_mc_read_t), &d_o.p));
+        HIP_TRY(c.alloc(movi_index::kA, nr * sizeof(movi_mc_read_t), &d_o));
         // the chunk's own counters, from its own staging (chunks of the overlapped path walk side by side): the caller's rows whole,
         // or scratch within "color_scratch_bytes" through which the chunk's reads go in turn
         const size_t cbytes = h_counts ? nr * S * 4 : (size_t)std::min<uint64_t>(nr * S * 4, std::max<uint64_t>(ix->color_scratch_bytes, S * 4));
-        HIP_TRY(c.alloc(movi_index::kS, cbytes, &d_c.p));
-        if (h_out_pml) HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_pml.p));
-        return multi_classify_device(ix, db, dof, nr, nb, min_len, static_cast<movi_mc_read_t *>(d_o.p), h_counts ? static_cast<uint32_t *>(d_c.p) : nullptr,
-                                     h_out_pml ? static_cast<uint16_t *>(d_pml.p) : nullptr, derr, nullptr, c.s, c.d_stats,
-                                     h_counts ? nullptr : static_cast<uint32_t *>(d_c.p), h_counts ? 0 : cbytes);
+        HIP_TRY(c.alloc(movi_index::kS, cbytes, &d_c));
+        if (h_out_pml) HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_pml));
+        return multi_classify_device(ix, db, dof, nr, nb, min_len, d_o, h_counts ? d_c : nullptr, h_out_pml ? d_pml : nullptr, derr, nullptr, c.s,
+                                     c.d_stats, h_counts ? nullptr : d_c, h_counts ? 0 : cbytes);
     };
     // page-locked block of a chunk in flight: out[nr] | counts[nr * S]
     auto fetch = [&](ChunkCtx &c, uint64_t first, uint64_t nr, uint64_t b0, uint64_t nb) -> int {
-        HIP_TRY(c.down_small(h_out + first, 0, c.d[movi_index::kA], nr * sizeof(movi_mc_read_t)));
-        if (h_counts) HIP_TRY(c.down_small(h_counts + first * S, nr * sizeof(movi_mc_read_t), c.d[movi_index::kS], nr * S * 4));
-        if (h_out_pml) HIP_TRY(c.down(h_out_pml + b0, c.d[movi_index::kOut], nb * 2));
+        HIP_TRY(c.down_small(h_out + first, 0, c.d[movi_index::kA].ptr(), nr * sizeof(movi_mc_read_t)));
+        if (h_counts) HIP_TRY(c.down_small(h_counts + first * S, nr * sizeof(movi_mc_read_t), c.d[movi_index::kS].ptr(), nr * S * 4));
+        if (h_out_pml) HIP_TRY(c.down(h_out_pml + b0, c.d[movi_index::kOut].ptr(), nb * 2));
         return MOVI_OK;
     };
     auto harvest = [&](const uint8_t *h, uint64_t first, uint64_t nr, HostPool::Group *) {

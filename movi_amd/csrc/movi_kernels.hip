@@ -724,16 +724,6 @@ TableFacts facts(const DevIndex &ix) {   // what the launch policy (movi_launch_
     return {ix.r, ix.idx32 != 0u, ix.sep != 0u, ix.rows2 != nullptr, ix.rows3 != nullptr, ix.hints != 0u, ix.rows2_count != 0u};
 }
 
-// grow-only: a workspace of fewer than `need` bytes is freed and one of `alloc` bytes takes its place
-hipError_t seg_ws_reserve(SegWorkspace *ws, size_t need, size_t alloc) {
-    if (ws->cap >= need) return hipSuccess;
-    if (ws->buf) (void)hipFree(ws->buf);
-    ws->buf = nullptr; ws->cap = 0;
-    const hipError_t e = hipMalloc(&ws->buf, alloc);
-    if (e == hipSuccess) ws->cap = alloc;
-    return e;
-}
-
 // ---- the front half of both segment plans (launch_pml_segmented, launch_zml_segmented): decide, lay the workspace out, probe, cut.
 // Where the two plans differ:
 struct SegShape {
@@ -788,9 +778,9 @@ hipError_t seg_prelude(const SegShape &sh, const uint64_t *d_offsets, uint64_t n
     if (cfg.seg_probe == 1 && n_reads >= (uint64_t)cfg.num_cus * 64ull * sh.ragged_waves) {
         if (ragged_hint == 0) return hipSuccess;
         if (ragged_hint < 0) {
-            e = seg_ws_reserve(ws, 64, 4096);
+            e = ws->reserve(64, 4096);
             if (e != hipSuccess) return e;
-            uint32_t *d_max = static_cast<uint32_t *>(ws->buf), h_max = 0;
+            uint32_t *d_max = ws->as<uint32_t>(), h_max = 0;
             e = hipMemsetAsync(d_max, 0, 4, stream);
             if (e != hipSuccess) return e;
             hipLaunchKernelGGL(seg_maxlen_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, stream, d_offsets, n_reads, d_max);
@@ -816,9 +806,9 @@ hipError_t seg_prelude(const SegShape &sh, const uint64_t *d_offsets, uint64_t n
                  o_ck = take(n_ck * sh.ckpt_bytes), o_go = take(32);
     size_t o_extra[2] = {0, 0};
     for (int i = 0; i < sh.n_extra; ++i) o_extra[i] = take(sh.extra_bytes[i]);
-    e = seg_ws_reserve(ws, off, off + (off >> 3));
+    e = ws->reserve(off, off + (off >> 3));   // (grow-only: a workspace of fewer than `off` bytes is freed and a bigger one takes its place)
     if (e != hipSuccess) return e;
-    uint8_t *B = static_cast<uint8_t *>(ws->buf);
+    uint8_t *B = ws->as<uint8_t>();
     uint64_t *n_of = reinterpret_cast<uint64_t *>(B + o_nof);
     P->max_seg = max_seg; P->first = reinterpret_cast<uint64_t *>(B + o_first);
     P->seg_in = reinterpret_cast<uint64_t *>(B + o_in); P->seg_out = reinterpret_cast<uint64_t *>(B + o_out);
@@ -2839,27 +2829,26 @@ hipError_t build_row_start_ckpt(int mode, const uint8_t *d_rows, uint64_t r, uin
                                 hipStream_t stream) {
     // d_ckpt has n_chunks + 1 entries; entry j = sum of n over rows [0, 32 j).
     const uint64_t n_chunks = (r + (1ull << kPrefixShift) - 1) >> kPrefixShift;
-    uint64_t *d_sums = nullptr;
-    hipError_t e = hipMalloc(&d_sums, (n_chunks + 1) * sizeof(uint64_t));
+    DevPtr<uint64_t> sums;
+    DevPtr<void> temp;
+    hipError_t e = dev_alloc(sums, (n_chunks + 1) * sizeof(uint64_t));
     if (e != hipSuccess) return e;
+    uint64_t *d_sums = sums.get();
     e = hipMemsetAsync(d_sums, 0, (n_chunks + 1) * sizeof(uint64_t), stream);
-    if (e != hipSuccess) { (void)hipFree(d_sums); return e; }
+    if (e != hipSuccess) return e;
     const unsigned bt = 256;
     const unsigned blocks = (unsigned)((n_chunks + bt - 1) / bt);
     if (mode == 6) hipLaunchKernelGGL(chunk_sum_kernel<6>, dim3(blocks), dim3(bt), 0, stream, d_rows, r, n_chunks, d_sums);
     else if (mode == 3) hipLaunchKernelGGL(chunk_sum_kernel<3>, dim3(blocks), dim3(bt), 0, stream, d_rows, r, n_chunks, d_sums);
-    else { (void)hipFree(d_sums); return hipErrorInvalidValue; }
+    else return hipErrorInvalidValue;
     e = hipGetLastError();
-    void *d_temp = nullptr;
     size_t temp_bytes = 0;
     if (e == hipSuccess)
         e = hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_sums, d_ckpt, (int)(n_chunks + 1), stream);
-    if (e == hipSuccess) e = hipMalloc(&d_temp, temp_bytes ? temp_bytes : 8);
+    if (e == hipSuccess) e = dev_alloc(temp, temp_bytes ? temp_bytes : 8);
     if (e == hipSuccess)
-        e = hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, d_sums, d_ckpt, (int)(n_chunks + 1), stream);
+        e = hipcub::DeviceScan::ExclusiveSum(temp.get(), temp_bytes, d_sums, d_ckpt, (int)(n_chunks + 1), stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (d_temp) (void)hipFree(d_temp);
-    (void)hipFree(d_sums);
     return e;
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "movi_launch_policy.hpp"   // LaunchCfg, the kCap* / k*ReadLen / k*Bytes constants, the launch plans
+#include "movi_buffers.hpp"         // the owning types (host side only); their two memory policies are below
 
 namespace movi {
 
@@ -247,11 +248,28 @@ hipError_t preload_walk_u64();
 hipError_t preload_walkseg_u32();
 hipError_t preload_walkseg_u64();
 
-// Device workspace of the segmented path, owned by whoever owns the stream (the handle; a pipeline slot): grow-only.
-struct SegWorkspace {
-    void *buf = nullptr;
-    size_t cap = 0;
+// The library's memory policies (movi_buffers.hpp) and the owning types on them.  Errors of a free are dropped: it runs in destructors
+// and on cleanup paths, whose caller is about to read an earlier message.
+struct DeviceMem {
+    using error = hipError_t;
+    static constexpr error ok = hipSuccess;
+    static error alloc(void **p, size_t bytes) { return hipMalloc(p, bytes); }
+    static void free(void *p) { (void)hipFree(p); }
 };
+struct PinnedMem {
+    using error = hipError_t;
+    static constexpr error ok = hipSuccess;
+    static error alloc(void **p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+using DevBuf = GrowBuf<DeviceMem>;
+using PinnedBuf = GrowBuf<PinnedMem>;
+using GraphDevBuf = GraphSafeBuf<DeviceMem>;
+template <class T> using DevPtr = OwnedPtr<T, DeviceMem>;
+template <class T> hipError_t dev_alloc(DevPtr<T> &p, size_t bytes) { return alloc_owned(p, bytes); }
+
+// Device workspace of the segmented path, owned by whoever owns the stream (the handle; a pipeline slot): grow-only.
+using SegWorkspace = DevBuf;
 
 // Reset masks instead of the PML vector (round 6; movi_pml_mask_device): PML[k] = reset(k) ? 0 : PML[k - 1] + 1, so one bit per base
 // says everything the u16 vector does.  words: bit k % 32 of word ((offsets[i] + phase) >> 5) + i + k / 32 = 1 iff step k of read i

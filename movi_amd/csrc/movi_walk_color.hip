@@ -166,22 +166,25 @@ hipError_t build_color_keys(int mode, const DevIndex &ix, const LocArgs &loc, co
     *d_keys_out = nullptr; *n_keys_out = 0; *bad_out = 0; *n_chunks = 0;
     seconds[0] = seconds[1] = 0.0;
     if ((mode != 6 && mode != 3) || m == 0 || m > 0x7FFFFFFFull || n_docs == 0 || ix.r >= (1ull << (64 - kColorKeyDocBits))) return hipErrorInvalidValue;
-    uint64_t *d_P = nullptr, *d_sv = nullptr, *d_si = nullptr, *d_tv = nullptr, *d_tj = nullptr, *d_ends = nullptr, *d_a = nullptr, *d_b = nullptr;
-    uint16_t *d_ids = nullptr;
-    uint32_t *d_visited = nullptr, *d_bad = nullptr;      // d_bad[0] = findings, d_bad[1] = hipcub's number of unique keys
-    void *d_temp = nullptr;
+    DevPtr<uint64_t> P, sv, si, tvd, tj, ends, ka, kb;
+    DevPtr<uint16_t> ids;
+    DevPtr<uint32_t> visited, badc;                       // badc[0] = findings, badc[1] = hipcub's number of unique keys
+    DevPtr<void> temp;
     size_t temp_bytes = 0;
     std::vector<uint64_t> tv(m);
     const uint64_t vis_words = (n + 31) / 32;
-    hipError_t e = hipMalloc(&d_P, m * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_sv, m * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_si, m * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_tv, m * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_tj, m * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_ends, (size_t)n_docs * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_ids, (size_t)n_docs * 2);
-    if (e == hipSuccess) e = hipMalloc(&d_visited, vis_words * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_bad, 8);
+    hipError_t e = dev_alloc(P, m * 8);
+    if (e == hipSuccess) e = dev_alloc(sv, m * 8);
+    if (e == hipSuccess) e = dev_alloc(si, m * 8);
+    if (e == hipSuccess) e = dev_alloc(tvd, m * 8);
+    if (e == hipSuccess) e = dev_alloc(tj, m * 8);
+    if (e == hipSuccess) e = dev_alloc(ends, (size_t)n_docs * 8);
+    if (e == hipSuccess) e = dev_alloc(ids, (size_t)n_docs * 2);
+    if (e == hipSuccess) e = dev_alloc(visited, vis_words * 4);
+    if (e == hipSuccess) e = dev_alloc(badc, 8);
+    uint64_t *d_P = P.get(), *d_sv = sv.get(), *d_si = si.get(), *d_tv = tvd.get(), *d_tj = tj.get(), *d_ends = ends.get();
+    uint16_t *d_ids = ids.get();
+    uint32_t *d_visited = visited.get(), *d_bad = badc.get();
     if (e == hipSuccess) e = hipMemsetAsync(d_visited, 0, vis_words * 4, stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 8, stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_P, 0xFF, m * 8, stream);           // a sample no row holds stays kPosNone: counted by the walk
@@ -195,15 +198,13 @@ hipError_t build_color_keys(int mode, const DevIndex &ix, const LocArgs &loc, co
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_sv, d_tv, d_si, d_tj, (int)m, 0, 64, stream);
-    if (e == hipSuccess) e = hipMalloc(&d_temp, temp_bytes ? temp_bytes : 8);
-    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(d_temp, temp_bytes, d_sv, d_tv, d_si, d_tj, (int)m, 0, 64, stream);
+    if (e == hipSuccess) e = dev_alloc(temp, temp_bytes ? temp_bytes : 8);
+    if (e == hipSuccess) e = hipcub::DeviceRadixSort::SortPairs(temp.get(), temp_bytes, d_sv, d_tv, d_si, d_tj, (int)m, 0, 64, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(tv.data(), d_tv, m * 8, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (d_temp) (void)hipFree(d_temp);
-    d_temp = nullptr;
-    if (d_sv) (void)hipFree(d_sv);
-    if (d_si) (void)hipFree(d_si);
-    d_sv = d_si = nullptr;
+    temp.reset();                                          // (freed here, not at the end: the key budget below is what is free now)
+    sv.reset();
+    si.reset();
     // the samples must be distinct text positions whose highest is n - 1 (sample 0): then the stretches add up to n
     bool shape = e == hipSuccess && tv[m - 1] == n - 1;
     for (uint64_t i = 1; shape && i < m; i++) shape = tv[i] > tv[i - 1];
@@ -219,15 +220,17 @@ hipError_t build_color_keys(int mode, const DevIndex &ix, const LocArgs &loc, co
         cap = std::min<uint64_t>(cap, n + (chunk_keys ? std::min(chunk_keys, n) : n));   // (never more than everything at once)
         if (cap < longest) e = hipErrorOutOfMemory;
     }
-    if (e == hipSuccess && shape) e = hipMalloc(&d_a, cap * 8);
-    if (e == hipSuccess && shape) e = hipMalloc(&d_b, cap * 8);
+    if (e == hipSuccess && shape) e = dev_alloc(ka, cap * 8);
+    if (e == hipSuccess && shape) e = dev_alloc(kb, cap * 8);
+    uint64_t *d_a = ka.get(), *d_b = kb.get();
     if (e == hipSuccess && shape) {
         size_t t1 = 0, t2 = 0;
         e = hipcub::DeviceRadixSort::SortKeys(nullptr, t1, d_a, d_b, (int)cap, 0, 64, stream);
         if (e == hipSuccess) e = hipcub::DeviceSelect::Unique(nullptr, t2, d_b, d_a, d_bad + 1, (int)cap, stream);
         temp_bytes = std::max(t1, t2);
-        if (e == hipSuccess) e = hipMalloc(&d_temp, temp_bytes ? temp_bytes : 8);
+        if (e == hipSuccess) e = dev_alloc(temp, temp_bytes ? temp_bytes : 8);
     }
+    void *d_temp = temp.get();
     int key_bits = (int)kColorKeyDocBits;
     while (key_bits < 64 && (ix.r >> (key_bits - (int)kColorKeyDocBits)) != 0) key_bits++;
     uint32_t doc_bits = 1;
@@ -260,17 +263,12 @@ hipError_t build_color_keys(int mode, const DevIndex &ix, const LocArgs &loc, co
         i0 = i1;
         chunks += 1;
     }
-    for (void *p : {(void *)d_P, (void *)d_tv, (void *)d_tj, (void *)d_ends, (void *)d_ids, (void *)d_visited, (void *)d_bad, (void *)d_b, d_temp})
-        if (p) (void)hipFree(p);
     *bad_out = !shape ? 1u : h_cnt[0];
     *n_chunks = chunks;
     if (key_cap) *key_cap = cap;
     if (e == hipErrorOutOfMemory) *n_keys_out = acc;
-    if (e != hipSuccess || *bad_out) {
-        if (d_a) (void)hipFree(d_a);
-        return e;
-    }
-    *d_keys_out = d_a;
+    if (e != hipSuccess || *bad_out) return e;
+    *d_keys_out = ka.release();                            // the caller's from here on
     *n_keys_out = acc;
     return hipSuccess;
 }

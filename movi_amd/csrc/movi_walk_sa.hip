@@ -284,11 +284,12 @@ uint64_t locate_rows_bytes(uint64_t r) { return r * 16; }
 hipError_t build_locate_rows(int mode, const DevIndex &ix, uint64_t rate, uint4 *d_loc, uint64_t *n_total, hipStream_t stream) {
     if ((mode != 6 && mode != 3) || rate == 0 || rate > (1ull << kLocRemBits) || ix.r > 0x7FFFFFFFull * 256) return hipErrorInvalidValue;
     const uint64_t r = ix.r;
-    uint64_t *d_len = nullptr, *d_allp = nullptr;
-    void *d_temp = nullptr;
+    DevPtr<uint64_t> len, allp;
+    DevPtr<void> temp;
     size_t temp_bytes = 0;
-    hipError_t e = hipMalloc(&d_len, (r + 1) * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_allp, (r + 1) * 8);
+    hipError_t e = dev_alloc(len, (r + 1) * 8);
+    if (e == hipSuccess) e = dev_alloc(allp, (r + 1) * 8);
+    uint64_t *d_len = len.get(), *d_allp = allp.get();
     if (e == hipSuccess) e = hipMemsetAsync(d_len + r, 0, 8, stream);
     if (e == hipSuccess) {
         if (mode == 6) hipLaunchKernelGGL(row_len_kernel<6>, dim3(blocks_of(r)), dim3(256), 0, stream, ix.rows, r, d_len);
@@ -297,17 +298,14 @@ hipError_t build_locate_rows(int mode, const DevIndex &ix, uint64_t rate, uint4 
     }
     if (e == hipSuccess && r + 1 > 0x7FFFFFFFull) e = hipErrorInvalidValue;
     if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(nullptr, temp_bytes, d_len, d_allp, (int)(r + 1), stream);
-    if (e == hipSuccess) e = hipMalloc(&d_temp, temp_bytes ? temp_bytes : 8);
-    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(d_temp, temp_bytes, d_len, d_allp, (int)(r + 1), stream);
+    if (e == hipSuccess) e = dev_alloc(temp, temp_bytes ? temp_bytes : 8);
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(temp.get(), temp_bytes, d_len, d_allp, (int)(r + 1), stream);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(loc_rows_kernel, dim3(blocks_of(r)), dim3(256), 0, stream, ix.rows, r, d_allp, rate, d_loc);
         e = hipGetLastError();
     }
     if (e == hipSuccess && n_total) e = hipMemcpyAsync(n_total, d_allp + r, 8, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (d_temp) (void)hipFree(d_temp);
-    if (d_allp) (void)hipFree(d_allp);
-    if (d_len) (void)hipFree(d_len);
     return e;
 }
 
@@ -329,16 +327,20 @@ hipError_t build_sampled_sa(int mode, const DevIndex &ix, const LocArgs &loc, ui
     const uint64_t n = loc.n, rate = loc.rate, m = (n + rate - 1) / rate, entries = n / rate + 1;
     *bad_out = 0;
     if (m == 0 || m > 0x7FFFFFFFull * 256) return hipErrorInvalidValue;
-    uint64_t *d_next = nullptr, *d_dist = nullptr;
-    ListNode *d_a = nullptr, *d_b = nullptr;
-    unsigned long long *d_tail = nullptr;                  // tail node, tails found, the cut edge's length | then bad (u32)
-    uint32_t *d_seen = nullptr;
-    hipError_t e = hipMalloc(&d_next, m * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_dist, m * 8);
-    if (e == hipSuccess) e = hipMalloc(&d_a, m * sizeof(ListNode));
-    if (e == hipSuccess) e = hipMalloc(&d_b, m * sizeof(ListNode));
-    if (e == hipSuccess) e = hipMalloc(&d_tail, 32);
-    if (e == hipSuccess) e = hipMalloc(&d_seen, m * 4);
+    DevPtr<uint64_t> next, dist;
+    DevPtr<ListNode> la, lb;
+    DevPtr<unsigned long long> tail;                       // tail node, tails found, the cut edge's length | then bad (u32)
+    DevPtr<uint32_t> seen;
+    hipError_t e = dev_alloc(next, m * 8);
+    if (e == hipSuccess) e = dev_alloc(dist, m * 8);
+    if (e == hipSuccess) e = dev_alloc(la, m * sizeof(ListNode));
+    if (e == hipSuccess) e = dev_alloc(lb, m * sizeof(ListNode));
+    if (e == hipSuccess) e = dev_alloc(tail, 32);
+    if (e == hipSuccess) e = dev_alloc(seen, m * 4);
+    uint64_t *d_next = next.get(), *d_dist = dist.get();
+    ListNode *d_a = la.get(), *d_b = lb.get();
+    unsigned long long *d_tail = tail.get();
+    uint32_t *d_seen = seen.get();
     uint32_t *d_bad = d_tail ? reinterpret_cast<uint32_t *>(d_tail + 3) : nullptr;
     if (e == hipSuccess) e = hipMemsetAsync(d_tail, 0, 32, stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_seen, 0, m * 4, stream);
@@ -373,8 +375,6 @@ hipError_t build_sampled_sa(int mode, const DevIndex &ix, const LocArgs &loc, ui
     }
     if (e == hipSuccess) e = hipMemcpyAsync(bad_out, d_bad, 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    for (void *p : {(void *)d_next, (void *)d_dist, (void *)d_a, (void *)d_b, (void *)d_tail, (void *)d_seen})
-        if (p) (void)hipFree(p);
     return e;
 }
 

@@ -210,3 +210,14 @@ def test_parse_fuzz_sanitized(tmp_path):
     r = subprocess.run([script, "1500", str(tmp_path)], capture_output=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
     assert b"fuzz ok" in r.stdout and b"no sanitizer report" in r.stdout
+
+
+def test_buffers_driver(tmp_path):
+    """The owning buffer types of the handle (movi_amd/csrc/movi_buffers.hpp) on a counting malloc policy: grow-only, free before
+    allocate, the slack rules' capacities, retired blocks, moves (tests/host/buffers_driver.cpp; its header has the sanitizer build)."""
+    import subprocess
+    exe = str(tmp_path / "buffers_driver")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "host", "buffers_driver.cpp")])
+    r = subprocess.run([exe], capture_output=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    assert b"cases ok" in r.stdout
