@@ -289,7 +289,7 @@ int movi_launch_log(char *buf, size_t cap, size_t *needed);
  * pangenome BWT, 0.51 on a uniformly random run sequence; -1 = not tallied yet), "device_scratch_bytes" (device scratch the
  * *_device calls hold: movi_pml_device's mask words -- retired buffers that captured graphs may still use included --, the u16 vector
  * of a movi_pml_mask_device call whose path has no mask output, the segment workspace, the park queue), "host_staging_bytes" (the
- * *_host calls' device staging), "park_lanes" (what the last PML call's mask walk parked at: 0 = it parked nothing) and "parked_reads"
+ * *_host calls' device staging), "park_lanes" (what the last PML call's mask walk parked at: 0 = it parked nothing), "ff_skip" (1 = the last PML call's walk ran with the fast-forward skip) and "parked_reads"
  * (reads the last movi_pml_device / movi_pml_mask_device call's first launch handed to its second; waits for the device, so not under a
  * stream capture).  Unknown key: MOVI_ERR_ARG. */
 int movi_index_info(const movi_index_t *ix, const char *key, double *value);
@@ -797,7 +797,12 @@ int movi_host_unregister(void *p);
  * short reads -- and picks 0 there: c2 is slower at every N from 2 to 16 although SIMT rises, profiles/park_lanes.txt); 0 = off; 1 .. 63 = N wherever the walk writes
  * masks itself, and for the vector only on the fused route.  Same answers and counters either way.  The queue is reserved with the mask
  * words by movi_index_prepare, or by this option on a handle that holds mask words; it never grows under a stream capture: a captured call
- * whose queue does not fit parks nothing), "reserve_device_masks" (device scratch
+ * whose queue does not fit parks nothing),
+ * "ff_skip" (fast-forward skip of the PML walk on the look-ahead and the deep rows: where a row's entry shows that the offset arrives at
+ * or beyond the length of the LF target j, fast_forward passes j whatever the next base is, so the walk gathers the window of j + 1 with
+ * that fast-forward taken instead of j's.  -1, the default: the launch policy decides per layout (ff_skip_on: on on the deep rows -- c2 88.0 -> 89.8 Gbases/s --, off on the look-ahead rows, where it gains 0.5 - 4.7 % when forced on: profiles/ff_skip.txt section 5);
+ * 0 = off; 1 = on wherever the walk has entries.  Same vectors, error bytes and counters either way; fewer lane and wavefront steps:
+ * profiles/ff_skip.txt), "reserve_device_masks" (device scratch
  * for the mask words of movi_pml_device calls of up to this many bases, reserved now instead of inside the first such call; grow-only,
  * beside what movi_index_prepare reserves),
  * "host_threads" (worker threads of the host-side expansion, 0 = three quarters of the CPUs the process may use -- affinity mask capped by the cgroup's quota --, at most 24),

@@ -1194,7 +1194,12 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
         }
         return MOVI_OK;
     }
-    if (!strcmp(key, "reserve_device_masks")) {             // device scratch for the mask words of movi_pml_device calls of up to `value` bases (and as many reads / 16)
+    if (!strcmp(key, "ff_skip")) {                           // the PML walk's fast-forward skip (DevIndex::ff_skip): -1 = the policy (ff_skip_on), 0 = off, 1 = on wherever the walk has entries (A/B)
+        if (value < -1 || value > 1) return fail(MOVI_ERR_ARG, "ff_skip must be -1, 0 or 1");
+        ix->cfg.ff_skip = (int)value;
+        return MOVI_OK;
+    }
+    if (!strcmp(key, "reserve_device_masks")) {            // device scratch for the mask words of movi_pml_device calls of up to `value` bases (and as many reads / 16)
         if (value < 0 || (uint64_t)value > (1ull << 40)) return fail(MOVI_ERR_ARG, "reserve_device_masks out of range");
         HIP_TRY(hipSetDevice(ix->device));
         HIP_TRY(grow(ix->dmask, (size_t)pml_mask_words((uint64_t)value / 16 + 1, (uint64_t)value, 0) * 4));
@@ -1473,7 +1478,8 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
                  (double)ix->color_scratch.cap();      // (held_bytes: the live words and the handle's retired blocks, queues among them)
     }
     else if (!strcmp(key, "park_lanes")) *value = (double)ix->last_launch.park_lanes;   // what the last PML call's mask walk parked at (0 = it parked nothing)
-    else if (!strcmp(key, "parked_reads")) {                 // reads the last query call's first launch handed to its second (waits for the device; not under a stream capture)
+    else if (!strcmp(key, "ff_skip")) *value = (double)ix->last_launch.ff_skip;         // 1 = the last PML call's walk ran with the fast-forward skip
+    else if (!strcmp(key, "parked_reads")) {               // reads the last query call's first launch handed to its second (waits for the device; not under a stream capture)
         unsigned long long parked = 0;
         HIP_TRY(hipSetDevice(ix->device));
         HIP_TRY(hipDeviceSynchronize());

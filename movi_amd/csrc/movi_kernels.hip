@@ -886,6 +886,7 @@ static hipError_t launch_pml_segmented(const DevIndex &ix, const uint8_t *d_base
     ixl.hint_w = seg_deep ? (cfg.hints != 0 ? 2u : 0u) : ((cfg.hints != 0 && ix.hints != 0u && ix.rows2 != nullptr) ? 3u : 0u);
     auto launch_seg = [&](int segv, uint64_t lanes, const PmlPlan &sp, LaunchInfo *li) -> hipError_t {
         ixl.stage_lds = sp.stage_lds;
+        ixl.ff_skip = ff_skip_on(cfg, sp.use_deep, sp.use_ahead) ? 1u : 0u;
         WalkLaunch L;
         L.grid = dim3((unsigned)((lanes + bt - 1) / bt)); L.block = dim3(bt); L.dyn_lds = sp.dyn_lds; L.stream = stream;
         L.ix = ixl; L.bases = d_bases; L.offs = d_offsets; L.n = lanes; L.out = d_out; L.err = d_err; L.stats = d_stats;
@@ -899,6 +900,7 @@ static hipError_t launch_pml_segmented(const DevIndex &ix, const uint8_t *d_base
     if (info) {                                           // the dominant kernel: K1
         info->variant = 14; info->block_threads = 64; info->segmented = 1; info->idx64 = ix.idx32 ? 0 : 1;
         info->waves_per_cu = 0; info->staged = (int)k1.stage_lds; info->ahead = k1.use_deep ? 2 : (k1.use_ahead ? 1 : 0);
+        info->ff_skip = ff_skip_on(cfg, k1.use_deep, k1.use_ahead) ? 1 : 0;
     }
     // (blocks of one wavefront: a boundary lane that has to walk far holds up only the 63 beside it)
     const uint32_t max_over = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (uint64_t)cfg.seg_len * (uint64_t)kSegOverrun);
@@ -1043,7 +1045,7 @@ hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
                       const uint32_t *d_order, const LaunchCfg &cfg, hipStream_t stream, const ClsArgs &cls,
                       SegWorkspace *seg_ws, int ragged_hint, int *seg_verdict, LaunchInfo *info, const MaskArgs &mask) {
     if (n_reads == 0) return hipSuccess;
-    if (info) info->park_lanes = 0;
+    if (info) { info->park_lanes = 0; info->ff_skip = 0; }
     // 0 = PML vector only, 1 = vector + classification bins, 2 = bins only
     bool want_mask = mask.words != nullptr;                // reset masks out instead of the vector (MaskArgs)
     const bool logging0 = cls.log_ff != nullptr || cls.log_scan != nullptr;
@@ -1084,6 +1086,7 @@ hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
     ixl.inwin = cfg.inwin ? 1u : 0u;
     ixl.hint_w = P.use_deep ? (cfg.hints != 0 ? 2u : 0u) : ((cfg.hints != 0 && ix.hints != 0u && ix.rows2 != nullptr) ? 3u : 0u);
     ixl.mask_phase = mask.phase & 31u;
+    ixl.ff_skip = (v == 14 && ff_skip_on(cfg, P.use_deep, P.use_ahead)) ? 1u : 0u;
     const bool mask_native = want_mask && v == 14 && P.stage_lds != 0u;
     // the vector from the mask walk itself: one-wavefront blocks whose 64 reads are one contiguous, 16-byte aligned stretch of it
     const bool fused_expand = mask_native && mask.expand_out != nullptr && bt == 64 && d_order == nullptr &&
@@ -1143,6 +1146,7 @@ hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
         info->staged = (int)ixl.stage_lds;
         info->ahead = P.use_deep ? 2 : (P.use_ahead ? 1 : 0);
         info->park_lanes = park_lanes;
+        info->ff_skip = (int)ixl.ff_skip;
     }
     if (e == hipSuccess && want_mask && !mask_native) e = launch_pml_to_mask(d_out, d_offsets, n_reads, n_bases, mask.phase, mask.words, stream);
     if (e == hipSuccess && mask_native && mask.expand_out != nullptr && !fused_expand)

@@ -51,7 +51,11 @@ struct DevIndex {
     // (12 bits each); w = fast-forwards (15 bits) | scan rows << 15 (16 bits) | valid << 31.  valid = 0: the interval of this K-mer
     // is empty before K bases are consumed (or a step throws): such reads take the ordinary search from their last base.
     uint32_t ftab_k;
-    uint32_t pad2_;
+    // set per launch, PML walk on the look-ahead or deep rows ("ff_skip"): 1 = FAST-FORWARD SKIP -- an LF whose entry says that the offset
+    // arrives at or beyond n(j) (the chain breaks by a fast-forward, whatever the next base is) gathers the window of j + 1 with that
+    // fast-forward already taken, instead of j's: where j is its window's last row the old iteration learnt only "next window".
+    // 0 = every LF gathers its target's window.  Same vectors, error bytes and counters either way; fewer lane and wavefront steps.
+    uint32_t ff_skip;
     const uint4 *ftab;
     uint32_t stage_lds;           // set per launch by launch_pml: bytes of dynamic LDS per lane for read staging (0 = none; 336 at cap 7)
     uint32_t mask_phase;          // set per launch, reset-mask output (pml_kernel_flatp<..., RING = 2>): the low 5 bits of the position of the batch's first base in the caller's whole read set (0 for a whole call)
@@ -148,6 +152,7 @@ struct LaunchInfo {
     int ahead = 0;           // 1 = the walk ran on the look-ahead rows (two bases per gather where the next base matches)
     int staged = 0;          // > 0: every lane keeps the next `staged` bases of its read in LDS (pml_kernel_flatp<..., STG = 1>)
     int park_lanes = 0;      // > 0: the mask walk parked a wavefront's last `park_lanes` lanes and a second launch of the named kernel resumed them
+    int ff_skip = 0;         // 1 = the PML walk ran with the fast-forward skip (DevIndex::ff_skip)
 };
 
 // Classifier::classify bins (src/classifier.cpp:99-143) fused into the PML kernels: per read the number of

@@ -19,6 +19,8 @@ constexpr uint64_t kDeepReadLen = 1024;           // plan_pml: batches whose mea
 constexpr uint64_t kPairLoadBytes = 2ull << 30;   // walked tables of this size and more: pair-shared gathers (plan_pml)
 constexpr int kParkLanesAuto = 0;                 // parked lanes: what "park_lanes" -1 picks where plan_pml's rule holds; 0 = off -- on c2 every threshold from 2 to 16 is slower than none (84.8 / 81.0 / 75.7 Gbases/s at 2 / 8 / 16 against 88.1: profiles/park_lanes.txt)
 constexpr uint64_t kParkMinRounds = 2;            // ... and only for batches of at least this many rounds of resident wavefronts (unmeasured: with kParkLanesAuto 0 the rule picks nothing; it is where a non-zero default would start from)
+constexpr int kFfSkipDeep = 1;                    // fast-forward skip (DevIndex::ff_skip): what "ff_skip" -1 picks on the deep rows -- c2 88.0 -> 89.8 Gbases/s, c2mid 70.6 -> 73.4, every run above the parent's fastest (profiles/ff_skip.txt)
+constexpr int kFfSkipAhead = 0;                   // ... and on the look-ahead rows: off in this commit -- forced on it gains 3.9 % on c2synth, 0.5 % on c3 and 4.7 % on c4, every run above the parent's; the whole GPU suite has been run with 0 only, so 1 goes in together with a suite run (same file, section 5)
 
 struct LaunchCfg {
     int block_threads = 0;   // 0 = auto: 64 for the PML and count kernels and the ZML state machine (finest dispatch grain), 256 for the base-synchronous ZML kernel
@@ -44,6 +46,7 @@ struct LaunchCfg {
     int fused_expand = 1;  // 1: a mask walk whose caller wants the vector expands its wavefronts' reads itself (DevIndex::expand_out); 0 = pml_expand_* kernels behind the walk: A/B
     int kmer_lookahead = -1; // kmer_kernel: -1 = hinted look-ahead with a split chosen by k and the text's length (kmer_look_step), 0 = every end searched from its own base, n >= 2 = split k / n (A/B)
     int park_lanes = -1;   // parked lanes of the mask walk (DevIndex::park_at): -1 = plan_pml's rule, 0 never, 1 .. 63 = a wavefront stops at that many walking lanes, wherever the walk can park (A/B)
+    int ff_skip = -1;      // fast-forward skip of the PML walk on the look-ahead / deep rows (DevIndex::ff_skip): -1 = ff_skip_on's rule, 0 never, 1 always (A/B)
     int deep = -1;         // the PML walk on the deep rows (DevIndex::rows3) where the handle holds them: -1 = batches of short reads (mean length < kDeepReadLen), 0 never, 1 always
 };
 
@@ -103,6 +106,12 @@ inline void stage_budget(PmlPlan &P, size_t pad_lds, bool uncapped, bool stage_o
 // pair-shared gathers by themselves: tables beyond the reach of the per-CU TLBs ("pair_loads" 1 / 0 forces them on / off)
 inline bool pair_wanted(const LaunchCfg &cfg, uint64_t walked_bytes) {
     return cfg.pair_loads > 0 || (cfg.pair_loads < 0 && walked_bytes >= kPairLoadBytes);
+}
+
+// Fast-forward skip (DevIndex::ff_skip), decided by the layout a launch walks on: the rule needs entries, so never on the plain rows.
+inline bool ff_skip_on(const LaunchCfg &cfg, bool use_deep, bool use_ahead) {
+    if (!use_deep && !use_ahead) return false;
+    return cfg.ff_skip > 0 || (cfg.ff_skip < 0 && (use_deep ? kFfSkipDeep : kFfSkipAhead) != 0);
 }
 
 inline PmlPlan plan_pml(const TableFacts &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, int cm, bool logging,

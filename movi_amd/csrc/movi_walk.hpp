@@ -40,6 +40,12 @@ namespace movi {
 // bit-exact, lane iterations per base 0.68 -> 0.56 on c2 as tools/iter_model.c predicts, and 10 % SLOWER there, 38 % slower on a
 // 113 M-row real BWT: twice the bytes, six loads and 18 % more instructions per iteration.  Measured with PMC
 // (profiles/r04_chain_rows.txt) and removed again; the code is in the history: commit b8d3f4e.)
+// FAST-FORWARD SKIP (DevIndex::ff_skip; look-ahead and deep rows; a wave-uniform run-time value, no instantiation of its own): the test
+// that decides whether the next base rides along, offset < n(j), fails in two ways.  Where it fails because the offset is at or beyond
+// n(j), the reference's next action is decided whatever that base is -- LF_move lands on j, fast_forward passes j -- so the gather goes
+// to the window of j + 1 with that fast-forward taken.  Where j is its window's last row the old iteration learnt only "next window":
+// c2 lane iterations per base 0.5426 -> 0.5068, fabric lines -4.1 %, 88.0 -> 89.8 Gbases/s for 22 more VALU per iteration
+// (profiles/ff_skip.txt).
 // PSH = 1 (round 4: "pair-shared gathers"; staged kernels, plain and look-ahead rows): the two lanes of a pair (2i, 2i + 1) fetch
 // their windows TOGETHER -- one load instruction brings the even lane's window (each lane one 16-byte half), the next the odd
 // lane's, and one exchange across the pair (DPP quad_perm) hands every lane the half it is missing.  Same loads per lane,
@@ -401,10 +407,11 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
         struct StepOut {
             uint32_t resolved, match, ffm, lf, mism, scanning, found, down, qf, qn, jump, jdist, landed, landed_down, nf, n, rofff, emit;
             uint32_t dbl, lf2, off1, tpl, lf3, off2, errc, st_next;
+            uint32_t sk, skn;                             // fast-forward skip: the gather goes past the LF target, whose length skn leaves the offset
             uint64_t j;
             IdxT needf, need_next, j2, j3;
         } R;
-        R.tpl = 0; R.lf3 = 0; R.off2 = 0; R.j3 = 0;
+        R.tpl = 0; R.lf3 = 0; R.off2 = 0; R.j3 = 0; R.sk = 0; R.skn = 0;
         if (AHD == 2) {
             // ---- DEEP ROWS (round 6; DevIndex::rows3): the window is the aligned group of THREE rows that holds `need` (64 bytes: half a
             // cache line), and every row carries what the walk reads at its LF target j AND at j's target j2 -- so that up to THREE
@@ -506,6 +513,14 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
             const uint32_t lf3 = tpl & (uint32_t)(k + 3 != len);
             need_next = tpl ? (lf3 ? jj3 : nd) : (dbl ? (lf2 ? jj2 : nd) : need_next);
             st_next = tpl ? (lf3 ? sFF : sDone) : (dbl ? (lf2 ? sFF : sDone) : st_next);
+            // FAST-FORWARD SKIP (DevIndex::ff_skip): a chain that breaks because the offset arrives at or beyond n(j) has its next action
+            // decided whatever the next base is -- LF_move lands on j and fast_forward (move_structure.cpp:524-545) passes it -- so the gather
+            // goes to j + 1's window with that fast-forward taken (off - n(j), ff_run = 1: below), not to j's.  Only with a valid entry (an
+            // invalid one has n = 0) and below row r - 1, which fast_forward never passes; an id that is no row still raises lf_bad.
+            const uint32_t sk1 = lf & ix.ff_skip & (uint32_t)(e1c != 7u) & (uint32_t)(off_e >= e1n) & (uint32_t)(jj < r1u);
+            const uint32_t sk2 = lf2 & ix.ff_skip & (uint32_t)(e2c != 7u) & (uint32_t)(off_e2 >= e2n) & (uint32_t)(jj2 < r1u);   // (lf2: dbl, and tpl is 0 then)
+            need_next += sk1 | sk2;                        // (sk1: no dbl, need_next is jj; sk2: dbl without tpl, need_next is jj2)
+            R.sk = sk1 | sk2; R.skn = sk1 ? e1n : (sk2 ? e2n : 0u);
             uint32_t errc = kErrNone;
             if (wave_any((ff_over | repo_edge | scan_edge | lf_bad) != 0u)) {
                 errc = ff_over ? kErrFastForward
@@ -663,6 +678,10 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
                 j2 = (id32 || ix.hints) ? (IdxT)ah.x : (IdxT)((uint64_t)ah.x | ((uint64_t)((ah.y >> 25) & 15u) << 32));
                 need_next = dbl ? (lf2 ? j2 : need) : need_next;
                 st_next = dbl ? (lf2 ? sFF : sDone) : st_next;
+                // fast-forward skip (DevIndex::ff_skip; the deep rows' branch has the argument): the offset arrives at or beyond n(j)
+                const uint32_t sk = lf & ix.ff_skip & (ah.y >> 31) & (uint32_t)(off_e >= n1) & (uint32_t)(j < (uint64_t)r1);
+                need_next += (IdxT)sk;                   // (sk: no dbl, need_next is j)
+                R.sk = sk; R.skn = sk ? n1 : 0u;
             }
             // The reference's throws: practically never, so which one it was is sorted out off the common path (as one
             // select ladder over need_next / st_next it cost ~45 instructions between a window's arrival and the next
@@ -683,7 +702,7 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
         const uint32_t resolved = R.resolved, match = R.match, ffm = R.ffm, lf = R.lf, mism = R.mism, scanning = R.scanning, found = R.found,
                        down = R.down, qf = R.qf, qn = R.qn, jump = R.jump, jdist = R.jdist, landed = R.landed, landed_down = R.landed_down,
                        nf = R.nf, n = R.n, rofff = R.rofff, emit = R.emit, dbl = R.dbl, lf2 = R.lf2, off1 = R.off1, tpl = R.tpl, lf3 = R.lf3,
-                       off2 = R.off2, errc = R.errc, st_next = R.st_next;
+                       off2 = R.off2, errc = R.errc, st_next = R.st_next, sk = R.sk, skn = R.skn;
         const uint64_t j = R.j;
         const IdxT needf = R.needf, need_next = R.need_next, j2 = R.j2, j3 = R.j3;
         (void)j3; (void)tpl; (void)lf3; (void)off2;
@@ -702,7 +721,7 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
         uint64_t nx_e = 0;
         ml = resolved ? (match ? ml + 1 : 0u) : ml;
         ff_total += resolved ? ff_run : 0u;
-        ff_run = lf ? 0u : ff_run + ffm;
+        ff_run = lf ? sk : ff_run + ffm;                 // (a skipped LF target is the run's first fast-forward: the counter, `room` and the limit see it)
         repo_total += mism;
         scan_total += scanning + (found ? (down ? qf - qn : qn - qf) : 0u) + (jump ? jdist - 1u : 0u);   // (a jump's last row is counted where it lands)
         off = ffm ? off - n : (landed ? (landed_down ? 0u : nf - 1) : off);   // read_processor.cpp:223
@@ -768,6 +787,7 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
                 off += lf3 ? off2 : 0u;
                 emit_pml(ml);
             }
+            if (AHD) off -= skn;                          // fast-forward skip: the walk arrives at the row behind its LF target
             if (STG && CLS != 2 && ring && ((k ^ k_in) & 16u) != 0u) ring_flush(k_in);   // a group of 16 PMLs is complete
             if (STG) {
                 // (the next base's code: after the state update below, where a lane about to leave its staged stretch is seen)

@@ -10,7 +10,9 @@
 //   * in-window repositions (inwin): a reposition whose target is a row of the window already held costs nothing;
 //   * own = 1: only the gather's own row carries an entry (a step that ends on a neighbour cannot ride);
 //   * look-ahead chains, depth S: after a base is resolved at row i, up to S following bases ride along while
-//     they match c(j_s) and arrive without a fast-forward (entry of row i holds the chain j_1 .. j_S).
+//     they match c(j_s) and arrive without a fast-forward (entry of row i holds the chain j_1 .. j_S);
+//   * fast-forward skip (skip = 1): where the entry of j_s shows that the offset arrives at or beyond n(j_s), the first window
+//     charged is the one that holds j_s + 1, not j_s.
 // Output: lane iterations per base, the share of iterations by kind, SIMT efficiency for waves of 64 consecutive
 // reads (wave iterations = max over lanes), and the distributions the designs depend on.
 //
@@ -37,7 +39,8 @@ static inline uint32_t rthr(uint64_t i, uint32_t k) {
 }
 static int code_of(uint8_t ch) { return ch == 'A' ? 0 : ch == 'C' ? 1 : ch == 'G' ? 2 : ch == 'T' ? 3 : -1; }
 
-typedef struct { int S, W, side, side_reach, inwin, own, rpl; } Design;   // rpl: rows per 128-byte line of the walked layout (round 6: fabric lines per base)
+typedef struct { int S, W, side, side_reach, inwin, own, rpl, skip; } Design;   // rpl: rows per 128-byte line of the walked layout (round 6: fabric lines per base)
+// skip = 1 (DevIndex::ff_skip): an arrival that fast-forwards, reached by an LF whose entry was still alive (it holds n(j)), gathers j + 1's window first
 typedef struct {
     uint64_t iters, bases, it_arrive, it_ffwin, it_mism, it_scanwin, chained, waves_iters, lanes_iters;
     uint64_t ff_rows, scan_rows, repos;
@@ -62,12 +65,13 @@ static uint32_t walk(const uint8_t *rd, uint32_t len, uint32_t top_k, const Desi
             uint32_t ff = 0;
             while (jj < r - 1 && off >= rn(jj)) { off -= rn(jj); jj++; ff++; }
             t->ff_rows += ff; arr_ff = ff != 0;
+            const int alive = chain_left > 0;        // the LF was taken from an entry that holds n(j): the kernel knows `ff != 0` before it gathers
             // does this base ride on the look-ahead chain? (match at j, no fast-forward)
             if (chain_left > 0 && ff == 0 && a >= 0 && (int)rc(j) == a && k >= top_k) { rode = 1; chain_left--; }
             else chain_left = 0;
             if (!rode && k >= top_k) {
                 it++; t->it_arrive++;
-                const uint64_t w0 = j / W, w1 = jj / W;
+                const uint64_t w0 = (d->skip && alive && ff ? j + 1 : j) / W, w1 = jj / W;
                 it += (uint32_t)(w1 - w0); t->it_ffwin += w1 - w0;
                 for (uint64_t w = w0; w <= w1; w++) FETCH(w * W);
             }
@@ -183,6 +187,8 @@ int main(int argc, char **argv) {
         // round 6: entries TWO rows deep packed to 21.33 bytes per row (6 rows per 128-byte line, windows of 3 rows = half a line), with / without hints;
         // beside them what ships (S = 1, W = 4, 8 rows per line) and round 4's chain rows (S = 2, W = 4, 4 rows per line) with hints
         {1, 4, 2, 7, 1, 0, 8}, {2, 4, 2, 7, 1, 0, 4}, {2, 3, 0, 0, 1, 0, 6}, {2, 3, 2, 7, 1, 0, 6}, {2, 3, 2, 3, 1, 0, 6}, {2, 6, 2, 7, 1, 0, 6}, {3, 3, 2, 7, 1, 0, 6},
+        // the fast-forward skip on the two layouts that ship: deep rows (S = 2, W = 3, hints of 2 bits) and look-ahead rows (S = 1, W = 4, hints of 3 bits)
+        {2, 3, 2, 3, 1, 0, 6, 1}, {1, 4, 2, 7, 1, 0, 8, 1},
     };
     printf("r = %llu rows, %llu reads x %u, top-of-walk K = %u\n", (unsigned long long)r, (unsigned long long)n_reads, L, top_k);
     printf("%-40s %9s %9s | %7s %7s %7s %7s | %7s | %6s %6s %6s | %7s\n", "design", "iter/base", "SIMT", "arrive", "ff-win", "mismat", "scanwin",
@@ -203,7 +209,8 @@ int main(int argc, char **argv) {
         }
         if (df) fclose(df);
         char name[96];
-        snprintf(name, sizeof name, "S=%d W=%d side=%d(%d) inwin=%d own=%d rpl=%d", designs[di].S, designs[di].W, designs[di].side, designs[di].side_reach, designs[di].inwin, designs[di].own, designs[di].rpl ? designs[di].rpl : 8);
+        snprintf(name, sizeof name, "S=%d W=%d side=%d(%d) inwin=%d own=%d rpl=%d%s", designs[di].S, designs[di].W, designs[di].side, designs[di].side_reach, designs[di].inwin, designs[di].own, designs[di].rpl ? designs[di].rpl : 8,
+                 designs[di].skip ? " sk" : "");
         const double b = (double)t.bases;
         printf("%-40s %9.4f %9.3f | %7.4f %7.4f %7.4f %7.4f | %7.4f | %6.3f %6.3f %6.4f | %7.4f\n", name, t.iters / b, (double)t.iters / t.waves_iters,
                t.it_arrive / b, t.it_ffwin / b, t.it_mism / b, t.it_scanwin / b, t.chained / b, t.ff_rows / b, t.scan_rows / b, t.repos / b, t.lines / b);
