@@ -220,26 +220,35 @@ static size_t park_queue_bytes(uint64_t n_reads, int lanes) {
     return kParkHeadBytes + (size_t)recs * kParkRecBytes;
 }
 // Is `s` being captured into a graph?  A query that cannot tell (hipErrorStreamCaptureImplicit: the null stream while another stream
-// captures in global mode) answers yes: the callers then take the route that allocates nothing.
-static bool stream_capturing(hipStream_t s) {
+// captures in global mode) answers yes: the callers then take the route that allocates nothing.  *known_active (optional): the query
+// succeeded and said that `s` itself is capturing.
+static bool stream_capturing(hipStream_t s, bool *known_active = nullptr) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (known_active) *known_active = false;
     if (hipStreamIsCapturing(s, &st) != hipSuccess) {
         (void)hipGetLastError();
         return true;
     }
+    if (known_active) *known_active = st == hipStreamCaptureStatusActive;
     return st != hipStreamCaptureStatusNone;
 }
-// The queue of a mask walk of n_reads reads on `s`: grown outside a stream capture only; a call whose queue does not fit runs with parking off.
-static void lend_park_queue(movi_index *ix, uint64_t n_reads, hipStream_t s, MaskArgs &m) {
+// The queue a mask walk of n_reads reads can be lent, in records (0: none -- parking is off, or the call is being captured and the queue
+// it would need is not there yet): what the plan is told, before anything is grown.
+static uint64_t park_queue_offer(const movi_index *ix, uint64_t n_reads, bool capturing) {
     const int lanes = park_lanes_wanted(ix);
-    if (lanes <= 0) return;
+    if (lanes <= 0) return 0;
     const size_t need = park_queue_bytes(n_reads, lanes);
-    const bool capturing = stream_capturing(s);
-    if (!capturing && grow(ix->dpark, need) != hipSuccess) { (void)hipGetLastError(); return; }
-    if (need > ix->dpark.cap()) return;
+    if (capturing && need > ix->dpark.cap()) return 0;
+    return (std::max(need, ix->dpark.cap()) - kParkHeadBytes) / kParkRecBytes;
+}
+// Lends that queue: grown outside a stream capture only.  false: the queue could not be grown, the call runs with parking off.
+static bool lend_park_queue(movi_index *ix, uint64_t n_reads, bool capturing, MaskArgs &m) {
+    const size_t need = park_queue_bytes(n_reads, park_lanes_wanted(ix));
+    if (!capturing && grow(ix->dpark, need) != hipSuccess) { (void)hipGetLastError(); return false; }
     if (capturing) ix->dpark.mark_in_graph();
     m.park_q = ix->dpark.ptr();
     m.park_cap = (ix->dpark.cap() - kParkHeadBytes) / kParkRecBytes;
+    return true;
 }
 // The upload stream of the overlapped host paths.  Streams of one priority share a handful of hardware queues, and a chunk's stream that
 // landed on the upload stream's queue had its walk queued behind the copies' completion packets (every sixth chunk waited for uploads that
@@ -1288,105 +1297,113 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
 
 // ---------------------------------------------------------------------------- PML
 
-// mask (optional; PML only): reset masks out instead of the vector -- mask->words / phase from the caller; a path without a mask output
-// of its own writes its vector to *tmp first (grow-only device scratch: the handle's, or a pipeline slot's).
-static int ml_device(bool zml, movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
-                     uint64_t n_bases, uint16_t *d_out, uint8_t *d_read_err, const uint32_t *d_read_order, void *stream,
-                     const ClsArgs &cls = ClsArgs(), DevStats *d_stats = nullptr, SegWorkspace *seg_ws = nullptr,
-                     int ragged_hint = -1, int *seg_verdict = nullptr, const MaskArgs *mask = nullptr, DevBuf *tmp = nullptr,
-                     bool tables_ready = false) {
-    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
-    if (!d_stats) d_stats = ix->d_stats.get();               // (the pipelined host path counts per chunk in flight ...
-    if (!seg_ws) seg_ws = &ix->seg_ws;                       //  ... and keeps a segment workspace per chunk in flight)
-    if (!zml && !mode_has_thresholds(ix->desc.mode))
-        return fail(MOVI_ERR_ARG, "PML needs thresholds: on a `regular`, `blocked` or `sampled` index the reference repositions "
-                                  "randomly (reposition_randomly), which cannot be reproduced; use --zml or --count, or a "
-                                  "*-thresholds index");
-    if (n_reads == 0) return MOVI_OK;
-    const bool bins_only = cls.bin_width != 0 && !d_out;
-    const bool masks = mask && mask->words;
-    if (masks && (zml || cls.bin_width != 0 || cls.log_ff)) return fail(MOVI_ERR_ARG, "reset masks: plain PML queries only");
-    if (!d_offsets || (n_bases && (!d_bases || (!d_out && !bins_only && !masks)))) return fail(MOVI_ERR_ARG, "NULL device buffer");
+// One PML or ZML call on device pointers, as every entry point hands it to pml_call / zml_call: the reads, where the results go (`out`;
+// PML: null = verdict bins only, or mask.words / mask.phase = reset masks are the result) and the stream; the calls fill in the handle's
+// part (mode, ix, cfg, info).  A chunk in flight of a *_host call brings its own counters, segment workspace, length hint, probe verdict and
+// scratch slots; a device-pointer call leaves them null and runs on the handle's (ix->dmask, ix->scratch[kTmp], the park queue).
+struct MlRequest : PmlCall {
+    bool lend_masks = false;                 // PML: `out` may come through mask words in scratch, where "pml_via_mask" and the plan say so
+    DevBuf *chunk = nullptr;                 // the chunk's scratch slots: kMask and kTmp are this call's
+};
+
+// What the PML and ZML calls share behind their argument checks: the device, and the call's counters cleared.  *no_alloc: `s` is being
+// captured, the call must not allocate.
+static int ml_begin(movi_index_t *ix, uint64_t n_reads, DevStats *d_stats, hipStream_t s, bool *no_alloc) {
     HIP_TRY(hipSetDevice(ix->device));
-    hipStream_t s = static_cast<hipStream_t>(stream);
     HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(DevStats), s));
     // (under a capture the counters are cleared by a kernel as well: a memset NODE behind kernel nodes -- an unpack captured in front of
     // this call -- was seen to replay with a stale pattern; an uncaptured call makes the HIP calls it always made)
-    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &capturing) != hipSuccess) { (void)hipGetLastError(); capturing = hipStreamCaptureStatusNone; }
-    if (capturing == hipStreamCaptureStatusActive) HIP_TRY(launch_stats_reset(d_stats, s));
+    bool active = false;
+    *no_alloc = stream_capturing(s, &active);
+    if (active) HIP_TRY(launch_stats_reset(d_stats, s));
     if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
-    // the first PML query on a handle builds its derived tables -- unless movi_index_prepare did (--logs runs on the first
-    // kernel, which uses none of them; tables_ready: the caller has asked already, once per call)
-    if (!zml && cls.log_ff == nullptr && !tables_ready) ensure_pml_tables(ix, s);
-    if (zml)
-        HIP_TRY(launch_zml(ix->kmode, ix->dev, d_bases, d_offsets, n_reads, n_bases, d_out, d_read_err, d_stats,
-                           d_read_order, ix->cfg, s, seg_ws, ragged_hint, seg_verdict, &ix->last_launch));
-    else {
-        MaskArgs m;
-        if (masks) {
-            m = *mask;
-            if (!m.expand_out && pml_mask_needs_tmp(ix->dev, ix->cfg, n_reads, n_bases, seg_ws != nullptr)) {   // (expand_out: such a batch writes the vector itself)
-                if (!tmp) tmp = &ix->scratch[movi_index::kTmp];
-                HIP_TRY(grow(*tmp, n_bases * 2));
-                m.tmp_pml = tmp->as<uint16_t>();
-            }
-        }
-        // (device-pointer calls: the probe's verdict is remembered for the next 15 calls on batches of the same shape -- mean read length
-        // and read count to a factor of two --: such calls then enqueue the walk without the probe and its read-back.  Either verdict
-        // gives the same answers; a stale one costs speed for at most those calls.  "seg_probe" 0 / 2 never probe anyway.)
-        int cached = -1;
-        const bool use_cache = seg_verdict == nullptr && ix->cfg.seg_probe == 1 && n_bases / n_reads >= 2ull * (uint64_t)std::max(ix->cfg.seg_len, 1);
-        const uint32_t key = use_cache ? ((uint32_t)(63 - __builtin_clzll(n_bases / n_reads)) << 8) | (uint32_t)(63 - __builtin_clzll(n_reads)) : 0u;
-        if (use_cache) {
-            if (ix->seg_cache_left > 0 && ix->seg_cache_key == key) { cached = ix->seg_cache_verdict; ix->seg_cache_left -= 1; }
-            seg_verdict = &cached;
-        }
-        const int before = cached;
-        HIP_TRY(launch_pml(ix->kmode, ix->dev, d_bases, d_offsets, n_reads, n_bases, d_out, d_read_err, d_stats,
-                           d_read_order, ix->cfg, s, cls, seg_ws, ragged_hint, seg_verdict, &ix->last_launch, m));
-        if (use_cache && before < 0 && cached >= 0) { ix->seg_cache_verdict = cached; ix->seg_cache_key = key; ix->seg_cache_left = 15; }
+    return MOVI_OK;
+}
+
+static int zml_call(movi_index_t *ix, const MlRequest &r) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (r.n_reads == 0) return MOVI_OK;
+    if (!r.offs || (r.n_bases && (!r.bases || !r.out))) return fail(MOVI_ERR_ARG, "NULL device buffer");
+    DevStats *d_stats = r.stats ? r.stats : ix->d_stats.get();
+    bool no_alloc = false;
+    if (int rc = ml_begin(ix, r.n_reads, d_stats, r.stream, &no_alloc)) return rc;
+    HIP_TRY(launch_zml(ix->kmode, ix->dev, r.bases, r.offs, r.n_reads, r.n_bases, r.out, r.err, d_stats, r.order, ix->cfg,
+                       r.stream, r.seg_ws ? r.seg_ws : &ix->seg_ws, r.ragged_hint, r.seg_verdict, &ix->last_launch));
+    return MOVI_OK;
+}
+
+// Every PML call.  The derived tables first, so that the plan sees the handle's final facts; then the plan (plan_pml: the one place that
+// says where the results leave the walk); then the scratch the planned route needs, and nothing else.
+// The vector THROUGH RESET MASKS (lend_masks; "pml_via_mask" 1: wherever the walk can, -1, the default: batches of short reads, 0: never):
+// the mask words live in scratch (device-pointer calls: ix->dmask, which movi_index_prepare reserves for kPrepareMaskBases bases and
+// "reserve_device_masks" for more).  A bigger batch grows them -- but never under a stream capture: a captured call whose words do not fit
+// is planned as the plain vector, which needs no scratch, and a buffer a captured call has used is retired on growth, not freed
+// (GraphSafeBuf).
+static int pml_call(movi_index_t *ix, const MlRequest &r) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (!mode_has_thresholds(ix->desc.mode))
+        return fail(MOVI_ERR_ARG, "PML needs thresholds: on a `regular`, `blocked` or `sampled` index the reference repositions "
+                                  "randomly (reposition_randomly), which cannot be reproduced; use --zml or --count, or a "
+                                  "*-thresholds index");
+    if (r.n_reads == 0) return MOVI_OK;
+    const bool bins_only = r.cls.bin_width != 0 && !r.out;
+    const bool masks = r.mask.words != nullptr;
+    if (masks && (r.cls.bin_width != 0 || r.cls.log_ff)) return fail(MOVI_ERR_ARG, "reset masks: plain PML queries only");
+    if (!r.offs || (r.n_bases && (!r.bases || (!r.out && !bins_only && !masks)))) return fail(MOVI_ERR_ARG, "NULL device buffer");
+    PmlCall c = r;
+    c.mode = ix->kmode; c.ix = &ix->dev; c.cfg = &ix->cfg; c.info = &ix->last_launch;
+    if (!c.stats) c.stats = ix->d_stats.get();                   // (the pipelined host path counts per chunk in flight ...
+    if (!c.seg_ws) c.seg_ws = &ix->seg_ws;                       //  ... and keeps a segment workspace per chunk in flight)
+    bool no_alloc = false;
+    if (int rc = ml_begin(ix, r.n_reads, c.stats, r.stream, &no_alloc)) return rc;
+    // the first PML query on a handle builds its derived tables -- unless movi_index_prepare did (--logs runs on the first kernel, which
+    // uses none of them)
+    if (r.cls.log_ff == nullptr) ensure_pml_tables(ix, r.stream);
+    // what the caller wants: masks, or the vector -- with mask words lent where there is a vector to write, the option allows it and, under
+    // a capture, the handle's words hold the batch already
+    const size_t lent_bytes = (size_t)pml_mask_words(r.n_reads, r.n_bases, 0) * 4;
+    const bool lends = r.lend_masks && r.out && ix->pml_via_mask != 0 && (r.chunk || !no_alloc || lent_bytes <= ix->dmask.cap());
+    // (the park queue's capacity is one of the plan's inputs; the queue itself is lent behind the plan, to the device-pointer calls that
+    // write masks -- parked or not, as ever)
+    PmlAsk ask = pml_ask(c, masks ? PmlWant::kMasks : lends ? PmlWant::kVectorLendsMasks : PmlWant::kVector, ix->pml_via_mask);
+    ask.park_cap = r.chunk ? 0 : park_queue_offer(ix, r.n_reads, no_alloc);
+    ask.park_queue = ask.park_cap > 0;
+    PmlRoute route = plan_pml(facts(ix->dev), ix->cfg, r.n_reads, r.n_bases, ask);
+    if (route.lent_masks()) {
+        HIP_TRY(r.chunk ? grow(r.chunk[movi_index::kMask], lent_bytes) : grow(ix->dmask, lent_bytes));
+        if (!r.chunk && no_alloc) ix->dmask.mark_in_graph();
+        c.mask.words = r.chunk ? r.chunk[movi_index::kMask].as<uint32_t>() : ix->dmask.as<uint32_t>();
     }
+    if (ask.park_queue && (masks || route.lent_masks()) && !lend_park_queue(ix, r.n_reads, no_alloc, c.mask)) route.park_lanes = 0, route.park_grid = 0;
+    if (route.needs_tmp) {                                       // (masks by way of a vector: grow-only device scratch, the handle's or the chunk's)
+        DevBuf &tmp = r.chunk ? r.chunk[movi_index::kTmp] : ix->scratch[movi_index::kTmp];
+        HIP_TRY(grow(tmp, r.n_bases * 2));
+        c.mask.tmp_pml = tmp.as<uint16_t>();
+    }
+    // (device-pointer calls: the probe's verdict is remembered for the next 15 calls on batches of the same shape -- mean read length
+    // and read count to a factor of two --: such calls then enqueue the walk without the probe and its read-back.  Either verdict
+    // gives the same answers; a stale one costs speed for at most those calls.  "seg_probe" 0 / 2 never probe anyway.)
+    int cached = -1;
+    const bool use_cache = r.seg_verdict == nullptr && ix->cfg.seg_probe == 1 && r.n_bases / r.n_reads >= 2ull * (uint64_t)std::max(ix->cfg.seg_len, 1);
+    const uint32_t key = use_cache ? ((uint32_t)(63 - __builtin_clzll(r.n_bases / r.n_reads)) << 8) | (uint32_t)(63 - __builtin_clzll(r.n_reads)) : 0u;
+    if (use_cache) {
+        if (ix->seg_cache_left > 0 && ix->seg_cache_key == key) { cached = ix->seg_cache_verdict; ix->seg_cache_left -= 1; }
+        c.seg_verdict = &cached;
+    }
+    const int before = cached;
+    HIP_TRY(launch_pml(c, route));
+    if (use_cache && before < 0 && cached >= 0) { ix->seg_cache_verdict = cached; ix->seg_cache_key = key; ix->seg_cache_left = 15; }
     return MOVI_OK;
 }
 
 int movi_pml_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
                     uint64_t n_bases, uint16_t *d_out_pml, uint8_t *d_read_err, const uint32_t *d_read_order,
                     void *stream) {
-    if (ix && n_reads && d_out_pml && d_offsets && mode_has_thresholds(ix->desc.mode) && ix->pml_via_mask != 0) {
-        // The vector THROUGH RESET MASKS: the walk writes one bit per base (a ninth fewer vector instructions per iteration than the
-        // u16 packer, a third of the write traffic) and every wavefront, when its 64 walks are over, expands its reads' words into the
-        // vector itself -- the expansion runs under the other wavefronts' gathers (pml_kernel_flatp's tail; "fused_expand" 0: the
-        // pml_expand_* kernels behind the walk).  "pml_via_mask" 1: always; -1, the default: where the walk runs on the deep rows -- three
-        // emissions per iteration: c2 78.4 -> 86.7 Gbases/s; the 1 B-row table 42.3 -> 46.0 --, i.e. batches of short reads; long reads keep
-        // the ring in LDS, which is as good there (c3: 16.76 against 16.66 ms).  The mask words live in device scratch of the handle
-        // (ix->dmask, grow-only): movi_index_prepare reserves them for kPrepareMaskBases bases, "reserve_device_masks" for more.  A bigger
-        // batch grows them -- but never under a stream capture: a captured call whose words do not fit takes the packer route, which
-        // needs no scratch, and a buffer a captured call has used is retired on growth, not freed (GraphSafeBuf).
-        // The vector of a fused expansion leaves in aligned 16-byte stores: launch_pml fuses it only into a 16-byte aligned d_out_pml
-        // and hands any other to launch_pml_expand behind the walk.
-        HIP_TRY(hipSetDevice(ix->device));
-        hipStream_t s = static_cast<hipStream_t>(stream);
-        ensure_pml_tables(ix, s);                            // (once per call: ml_device is told so)
-        if (ix->pml_via_mask > 0 || pml_vector_via_masks(ix->dev, ix->cfg, n_reads, n_bases, true, d_read_order != nullptr)) {
-            const size_t need = (size_t)pml_mask_words(n_reads, n_bases, 0) * 4;
-            const bool capturing = stream_capturing(s);
-            if (!capturing || need <= ix->dmask.cap()) {
-                HIP_TRY(grow(ix->dmask, need));
-                if (capturing) ix->dmask.mark_in_graph();
-                MaskArgs m;
-                m.words = ix->dmask.as<uint32_t>();
-                m.phase = 0;
-                m.expand_out = d_out_pml;
-                lend_park_queue(ix, n_reads, s, m);
-                return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, nullptr, d_read_err, d_read_order, stream, ClsArgs(), nullptr,
-                                 nullptr, -1, nullptr, &m, nullptr, true);
-            }
-        }
-        return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, d_out_pml, d_read_err, d_read_order, stream, ClsArgs(), nullptr,
-                         nullptr, -1, nullptr, nullptr, nullptr, true);
-    }
-    return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, d_out_pml, d_read_err, d_read_order, stream);
+    MlRequest r;
+    r.bases = d_bases; r.offs = d_offsets; r.n_reads = n_reads; r.n_bases = n_bases;
+    r.out = d_out_pml; r.err = d_read_err; r.order = d_read_order; r.stream = static_cast<hipStream_t>(stream);
+    r.lend_masks = true;
+    return pml_call(ix, r);
 }
 
 int movi_pml_mask_words(uint64_t n_reads, uint64_t n_bases, uint64_t first_base, uint64_t *n_words) {
@@ -1399,15 +1416,11 @@ int movi_pml_mask_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_
                          uint64_t n_bases, uint64_t first_base, uint32_t *d_mask_words, uint8_t *d_read_err,
                          const uint32_t *d_read_order, void *stream) {
     if (n_reads && !d_mask_words) return fail(MOVI_ERR_ARG, "NULL device buffer");
-    MaskArgs m;
-    m.words = d_mask_words;
-    m.phase = (uint32_t)(first_base & 31u);
-    if (ix && n_reads) {
-        if (hipSetDevice(ix->device) == hipSuccess) lend_park_queue(ix, n_reads, static_cast<hipStream_t>(stream), m);
-        else (void)hipGetLastError();                        // (ml_device reports it)
-    }
-    return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, nullptr, d_read_err, d_read_order, stream, ClsArgs(), nullptr,
-                     nullptr, -1, nullptr, &m);
+    MlRequest r;
+    r.bases = d_bases; r.offs = d_offsets; r.n_reads = n_reads; r.n_bases = n_bases;
+    r.mask.words = d_mask_words; r.mask.phase = (uint32_t)(first_base & 31u);
+    r.err = d_read_err; r.order = d_read_order; r.stream = static_cast<hipStream_t>(stream);
+    return pml_call(ix, r);
 }
 
 int movi_pml_expand_device(movi_index_t *ix, const uint32_t *d_mask_words, const uint64_t *d_offsets, uint64_t n_reads,
@@ -1424,7 +1437,10 @@ int movi_pml_expand_device(movi_index_t *ix, const uint32_t *d_mask_words, const
 int movi_zml_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
                     uint64_t n_bases, uint16_t *d_out_zml, uint8_t *d_read_err, const uint32_t *d_read_order,
                     void *stream) {
-    return ml_device(true, ix, d_bases, d_offsets, n_reads, n_bases, d_out_zml, d_read_err, d_read_order, stream);
+    MlRequest r;
+    r.bases = d_bases; r.offs = d_offsets; r.n_reads = n_reads; r.n_bases = n_bases;
+    r.out = d_out_zml; r.err = d_read_err; r.order = d_read_order; r.stream = static_cast<hipStream_t>(stream);
+    return zml_call(ix, r);
 }
 
 int movi_last_launch(const movi_index_t *ix, movi_launch_info_t *info) {
@@ -1583,6 +1599,13 @@ struct ChunkCtx {
         hipError_t e = grow(d[slot], bytes);
         *out = d[slot].template as<T>();
         return e;
+    }
+    // the chunk as a PML / ZML call: its reads, stream, counters, segment state and scratch slots (the caller adds where the results go)
+    MlRequest request(const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) const {
+        MlRequest r;
+        r.bases = db; r.offs = dof; r.n_reads = nr; r.n_bases = nb; r.err = derr; r.stream = s;
+        r.stats = d_stats; r.seg_ws = seg_ws; r.ragged_hint = ragged_hint; r.seg_verdict = seg_verdict; r.chunk = d;
+        return r;
     }
     // device -> host: straight into the caller's buffer (synchronous path, or a page-locked destination) ...
     hipError_t down(void *h_dst, const void *d_src, size_t bytes) {
@@ -2230,12 +2253,10 @@ static int ml_host(bool zml, movi_index_t *ix, const ReadSource &src, const uint
     uint64_t acc_all = 0, acc_mask = 0;                       // bases launched so far / of them by the mask route
     std::unordered_map<uint64_t, Way> way_of;                 // first read of a chunk -> its way (launch, fetch and harvest run on the calling thread)
     const int threads = ix->host_threads > 0 ? ix->host_threads : host_threads_default();
-    uint16_t *d_out = nullptr;
     auto phase_of = [&](uint64_t b0) { return (uint32_t)((b0 - o0) & 31u); };
     auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
         Way w;
         w.phase = phase_of(c.b0);
-        const bool through_masks = !zml && ix->pml_via_mask != 0 && pml_vector_via_masks(ix->dev, ix->cfg, nr, nb, true, false);
         if (route == kMasks) w.masks = true;
         else if (route == kMixed) {                           // (the first chunk comes down as it is: its DMA starts when its walk ends)
             w.masks = (acc_mask + nb) * 100 <= (uint64_t)ix->host_mask_share * (acc_all + nb);
@@ -2243,23 +2264,16 @@ static int ml_host(bool zml, movi_index_t *ix, const ReadSource &src, const uint
             if (w.masks) acc_mask += nb;
         }
         way_of[c.first] = w;
+        MlRequest r = c.request(db, dof, nr, nb, derr);
         if (w.masks) {
-            MaskArgs m;
-            m.phase = w.phase;
-            HIP_TRY(c.alloc(movi_index::kMask, (size_t)pml_mask_words(nr, nb, m.phase) * 4, &m.words));
-            return ml_device(false, ix, db, dof, nr, nb, nullptr, derr, nullptr, c.s, ClsArgs(), c.d_stats, c.seg_ws, c.ragged_hint,
-                             c.seg_verdict, &m, &c.d[movi_index::kTmp]);
+            r.mask.phase = w.phase;
+            HIP_TRY(c.alloc(movi_index::kMask, (size_t)pml_mask_words(nr, nb, w.phase) * 4, &r.mask.words));
+            return pml_call(ix, r);
         }
-        HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_out));
-        // (the vector itself comes down: on the device it is written through reset masks where movi_pml_device's policy says so)
-        if (through_masks || (!zml && ix->pml_via_mask > 0)) {
-            MaskArgs m;
-            HIP_TRY(c.alloc(movi_index::kMask, (size_t)pml_mask_words(nr, nb, 0) * 4, &m.words));
-            m.expand_out = d_out;
-            return ml_device(false, ix, db, dof, nr, nb, nullptr, derr, nullptr, c.s, ClsArgs(), c.d_stats, c.seg_ws, c.ragged_hint,
-                             c.seg_verdict, &m);
-        }
-        return ml_device(zml, ix, db, dof, nr, nb, d_out, derr, nullptr, c.s, ClsArgs(), c.d_stats, c.seg_ws, c.ragged_hint, c.seg_verdict);
+        HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &r.out));
+        if (zml) return zml_call(ix, r);
+        r.lend_masks = true;      // (the vector itself comes down: on the device it is written through reset masks where the plan says so)
+        return pml_call(ix, r);
     };
     // what a chunk's masks are to the host: the words land in `words`; they are the result, or the vector is expanded from them
     auto deliver = [&](const uint32_t *words, uint64_t first, uint64_t nr, uint32_t ph, HostPool::Group *g) {
@@ -2408,10 +2422,12 @@ int movi_pml_logs_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t 
         HIP_TRY(c.alloc(movi_index::kS, nb * 2, &d_sc));
         HIP_TRY(hipMemsetAsync(d_ff, 0, nb * 2, c.s));                 // a read of one base has no LF: its entry stays 0
         HIP_TRY(hipMemsetAsync(d_sc, 0, nb * 2, c.s));
-        ClsArgs logs;
-        logs.log_ff = d_ff;
-        logs.log_scan = d_sc;
-        return ml_device(false, ix, db, dof, nr, nb, d_out, derr, nullptr, c.s, logs, c.d_stats);
+        MlRequest r;                                                   // (the handle's segment workspace: logs never reach the segment plan)
+        r.bases = db; r.offs = dof; r.n_reads = nr; r.n_bases = nb; r.out = d_out; r.err = derr; r.stream = c.s;
+        r.stats = c.d_stats;
+        r.cls.log_ff = d_ff;
+        r.cls.log_scan = d_sc;
+        return pml_call(ix, r);
     };
     auto fetch = [&](ChunkCtx &c, uint64_t, uint64_t, uint64_t b0, uint64_t nb) -> int {
         HIP_TRY(c.down(h_out_pml + b0, c.d[movi_index::kOut].ptr(), nb * 2));
@@ -2444,48 +2460,41 @@ int movi_classify_device(movi_index_t *ix, const uint16_t *d_pml, const uint64_t
 }
 
 constexpr uint64_t kClassifyTwoPassLen = 1024;          // mean read length from which vector + bins run as walk + pass (short reads: fused 71.5 against 63.5 on c2)
-static int pml_classify_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
-                               uint64_t n_bases, uint32_t bin_width, uint32_t max_value_thr, uint16_t *d_out_pml,
-                               uint32_t *d_bins_above, uint32_t *d_bins_below, uint64_t *d_sum_max, uint8_t *d_read_err,
-                               const uint32_t *d_read_order, void *stream, DevStats *d_stats,
-                               SegWorkspace *seg_ws = nullptr, int ragged_hint = -1, int *seg_verdict = nullptr) {
+static int pml_classify_device(movi_index_t *ix, MlRequest r, uint32_t bin_width, uint32_t max_value_thr, uint32_t *d_bins_above,
+                               uint32_t *d_bins_below, uint64_t *d_sum_max) {
     if (bin_width == 0) return fail(MOVI_ERR_ARG, "bin_width must be > 0");
-    if (n_reads && (!d_bins_above || !d_bins_below || !d_sum_max)) return fail(MOVI_ERR_ARG, "NULL device buffer");
-    ClsArgs cls;
-    cls.bin_width = bin_width;
-    cls.thr = max_value_thr;
-    cls.above = d_bins_above;
-    cls.below = d_bins_below;
-    cls.sum_max = d_sum_max;
+    if (r.n_reads && (!d_bins_above || !d_bins_below || !d_sum_max)) return fail(MOVI_ERR_ARG, "NULL device buffer");
     // When the PML vector is wanted anyway, the bins are cheaper as a second, streaming pass over the resident vectors
     // (classify_kernel: 2 B per base at HBM speed) than fused into the walk: the running bins cost the latency-bound walk
     // ~20 instructions per emission and eight registers -- 100 k x 10 kbp: fused 46.9, walk + pass 53.6 Gbases/s
     // (profiles/r04_classify.txt).  Bins WITHOUT the vector (--classify --filter, --no-output) stay fused: nothing is
     // written at all (60.7).  "classify_fused" 1 / 0 forces either; the pass needs the error bytes (failed reads report
     // no bins), so without d_read_err the fused kernel runs.
-    const bool two_pass = d_out_pml != nullptr && d_read_err != nullptr && n_reads != 0 &&
-                          (ix ? (ix->cfg.classify_fused == 0 || (ix->cfg.classify_fused < 0 && n_bases / n_reads >= kClassifyTwoPassLen)) : false);
+    const bool two_pass = r.out != nullptr && r.err != nullptr && r.n_reads != 0 &&
+                          (ix ? (ix->cfg.classify_fused == 0 || (ix->cfg.classify_fused < 0 && r.n_bases / r.n_reads >= kClassifyTwoPassLen)) : false);
     if (two_pass) {
-        const int rc = ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, d_out_pml, d_read_err, d_read_order, stream, ClsArgs(),
-                                 d_stats, seg_ws, ragged_hint, seg_verdict);
+        const int rc = pml_call(ix, r);
         if (rc != MOVI_OK) return rc;
-        HIP_TRY(launch_classify(d_out_pml, d_offsets, n_reads, bin_width, max_value_thr, d_bins_above, d_bins_below, d_sum_max,
-                                static_cast<hipStream_t>(stream), d_read_err, n_bases));
+        HIP_TRY(launch_classify(r.out, r.offs, r.n_reads, bin_width, max_value_thr, d_bins_above, d_bins_below, d_sum_max, r.stream,
+                                r.err, r.n_bases));
         return MOVI_OK;
     }
-    // (a chunk in flight of the overlapped host path brings its own segment workspace, length hint and the call's probe
-    // verdict: without them every chunk fell back to the handle's workspace -- shared by chunks on different streams --
-    // and probed again)
-    return ml_device(false, ix, d_bases, d_offsets, n_reads, n_bases, d_out_pml, d_read_err, d_read_order, stream, cls, d_stats,
-                     seg_ws, ragged_hint, seg_verdict);
+    r.cls.bin_width = bin_width;
+    r.cls.thr = max_value_thr;
+    r.cls.above = d_bins_above;
+    r.cls.below = d_bins_below;
+    r.cls.sum_max = d_sum_max;
+    return pml_call(ix, r);
 }
 
 int movi_pml_classify_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
                              uint64_t n_bases, uint32_t bin_width, uint32_t max_value_thr, uint16_t *d_out_pml,
                              uint32_t *d_bins_above, uint32_t *d_bins_below, uint64_t *d_sum_max, uint8_t *d_read_err,
                              const uint32_t *d_read_order, void *stream) {
-    return pml_classify_device(ix, d_bases, d_offsets, n_reads, n_bases, bin_width, max_value_thr, d_out_pml, d_bins_above,
-                               d_bins_below, d_sum_max, d_read_err, d_read_order, stream, nullptr);
+    MlRequest r;
+    r.bases = d_bases; r.offs = d_offsets; r.n_reads = n_reads; r.n_bases = n_bases;
+    r.out = d_out_pml; r.err = d_read_err; r.order = d_read_order; r.stream = static_cast<hipStream_t>(stream);
+    return pml_classify_device(ix, r, bin_width, max_value_thr, d_bins_above, d_bins_below, d_sum_max);
 }
 
 int movi_pml_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads,
@@ -2505,8 +2514,9 @@ int movi_pml_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uint6
         HIP_TRY(c.alloc(movi_index::kB, nr * 4, &d_b));
         HIP_TRY(c.alloc(movi_index::kS, nr * 8, &d_s));
         // bins reduced inside the PML kernel; no PML vector is written at all
-        return pml_classify_device(ix, db, dof, nr, nb, bin_width, max_value_thr, nullptr, d_a, d_b, d_s, derr, nullptr, c.s,
-                                   c.d_stats, c.seg_ws, c.ragged_hint, c.seg_verdict);
+        // (a chunk in flight of the overlapped host path brings its own segment workspace, length hint and the call's probe verdict:
+        // without them every chunk fell back to the handle's workspace -- shared by chunks on different streams -- and probed again)
+        return pml_classify_device(ix, c.request(db, dof, nr, nb, derr), bin_width, max_value_thr, d_a, d_b, d_s);
     };
     // page-locked block of a chunk in flight: sum_max[nr] | above[nr] | below[nr]
     auto fetch = [&](ChunkCtx &c, uint64_t first, uint64_t nr, uint64_t, uint64_t) -> int {

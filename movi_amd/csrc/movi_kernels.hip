@@ -716,13 +716,13 @@ __global__ __launch_bounds__(256) void seg_finalize_kernel(const uint32_t *__res
     }
 }
 
-namespace {
-size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-constexpr int kSegOverrun = 4;   // a boundary lane looks for its meeting point over at most this many seg_len of bases
-
 TableFacts facts(const DevIndex &ix) {   // what the launch policy (movi_launch_policy.hpp) reads of the index
     return {ix.r, ix.idx32 != 0u, ix.sep != 0u, ix.rows2 != nullptr, ix.rows3 != nullptr, ix.hints != 0u, ix.rows2_count != 0u};
 }
+
+namespace {
+size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+constexpr int kSegOverrun = 4;   // a boundary lane looks for its meeting point over at most this many seg_len of bases
 
 // ---- the front half of both segment plans (launch_pml_segmented, launch_zml_segmented): decide, lay the workspace out, probe, cut.
 // Where the two plans differ:
@@ -851,35 +851,37 @@ hipError_t seg_prelude(const SegShape &sh, const uint64_t *d_offsets, uint64_t n
 // length (100 k x 10 kbp: 40.5 Gbases/s either way); segments pay when lanes are scarce -- fewer than 4 wavefronts of reads
 // per CU: 60 k x 10 kbp 28.6 -> 34.3, 25 k 12.1 -> 31.4, 200 x 1 Mbp 0.11 -> 27 Gbases/s -- or when the batch is ragged
 // (its longest read holds a lane long after the others are done; log-normal lengths around 10 kbp: 12.2 -> 32.3).
-static hipError_t launch_pml_segmented(const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
-                                       uint64_t n_bases, uint16_t *d_out, uint8_t *d_err, DevStats *d_stats,
-                                       const LaunchCfg &cfg, hipStream_t stream, SegWorkspace *ws, bool big_batch_cap,
-                                       int ragged_hint, bool *declined, const ClsArgs &bins, int *verdict, LaunchInfo *info) {
+// d_out: where the vector goes (the call's own, or the scratch that a mask call's words are packed from).
+static hipError_t launch_pml_segmented(const PmlCall &c, uint16_t *d_out, bool *declined) {
+    const DevIndex &ix = *c.ix;
+    const LaunchCfg &cfg = *c.cfg;
+    uint8_t *d_err = c.err;
+    const bool big_batch_cap = cfg.pml_variant < 0 || cfg.pml_variant == 14;
     // a verdict-only call (bins, no PML vector) keeps its PMLs in the workspace, sized from n_bases: for offsets that only
     // the device has seen (ragged_hint < 0) the verdict of seg_decide_kernel -- which checks them -- is always read back
-    const bool ws_pml = bins.bin_width && !d_out;
-    if (ws_pml && ragged_hint < 0 && cfg.seg_probe == 2) { *declined = true; return hipSuccess; }
+    const bool ws_pml = c.cls.bin_width && !d_out;
+    if (ws_pml && c.ragged_hint < 0 && cfg.seg_probe == 2) { *declined = true; return hipSuccess; }
     // Classification bins (bins.bin_width != 0): not fused into this walk -- a bin spans segments -- but reduced from the
     // resident PML vector afterwards (classify_kernel: 2 B per base, streaming); without a caller's vector (d_out == NULL:
     // verdicts only) the PMLs go to the workspace.
     const SegShape shape = {kSegWavesPml, kSegRaggedWavesPml, sizeof(SegFin), sizeof(SegCkpt), 2,
-                            {ws_pml ? (size_t)n_bases * 2 : 0, (bins.bin_width && !d_err) ? (size_t)n_reads : 0}, ws_pml && ragged_hint < 0};
+                            {ws_pml ? (size_t)c.n_bases * 2 : 0, (c.cls.bin_width && !d_err) ? (size_t)c.n_reads : 0}, ws_pml && c.ragged_hint < 0};
     SegPrelude pre;
-    hipError_t e = seg_prelude(shape, d_offsets, n_reads, n_bases, cfg, stream, ws, ragged_hint, declined, verdict, [&](uint32_t *tally) {
-        hipLaunchKernelGGL(seg_probe_kernel<6>, dim3(16), dim3(64), 0, stream, ix, d_bases, d_offsets, n_reads, 32u, 384u, tally);
+    hipError_t e = seg_prelude(shape, c.offs, c.n_reads, c.n_bases, cfg, c.stream, c.seg_ws, c.ragged_hint, declined, c.seg_verdict, [&](uint32_t *tally) {
+        hipLaunchKernelGGL(seg_probe_kernel<6>, dim3(16), dim3(64), 0, c.stream, ix, c.bases, c.offs, c.n_reads, 32u, 384u, tally);
     }, &pre);
     if (e != hipSuccess || *declined) return e;
     if (ws_pml) d_out = reinterpret_cast<uint16_t *>(pre.extra[0]);
-    if (bins.bin_width && !d_err) d_err = pre.extra[1];
+    if (c.cls.bin_width && !d_err) d_err = pre.extra[1];
     const uint64_t max_seg = pre.max_seg;
     SegArgs seg;
-    pre.fill(seg, n_reads);
+    pre.fill(seg, c.n_reads);
     seg.go = pre.go;
     const unsigned bt256 = 256;
     // K1 and K3b: the window-parallel lane state machine in blocks of one wavefront, capped like any big batch (plan_pml_seg)
     const int bt = 64;
     const TableFacts T = facts(ix);
-    const PmlPlan k1 = plan_pml_seg(T, cfg, max_seg, big_batch_cap), k3 = plan_pml_seg(T, cfg, n_reads, big_batch_cap);
+    const PmlPlan k1 = plan_pml_seg(T, cfg, max_seg, big_batch_cap), k3 = plan_pml_seg(T, cfg, c.n_reads, big_batch_cap);
     DevIndex ixl = ix;
     ixl.inwin = cfg.inwin ? 1u : 0u;
     const bool seg_deep = ix.rows3 != nullptr && ix.idx32 != 0u && cfg.deep > 0 && cfg.stage_reads != 0;
@@ -888,32 +890,32 @@ static hipError_t launch_pml_segmented(const DevIndex &ix, const uint8_t *d_base
         ixl.stage_lds = sp.stage_lds;
         ixl.ff_skip = ff_skip_on(cfg, sp.use_deep, sp.use_ahead) ? 1u : 0u;
         WalkLaunch L;
-        L.grid = dim3((unsigned)((lanes + bt - 1) / bt)); L.block = dim3(bt); L.dyn_lds = sp.dyn_lds; L.stream = stream;
-        L.ix = ixl; L.bases = d_bases; L.offs = d_offsets; L.n = lanes; L.out = d_out; L.err = d_err; L.stats = d_stats;
+        L.grid = dim3((unsigned)((lanes + bt - 1) / bt)); L.block = dim3(bt); L.dyn_lds = sp.dyn_lds; L.stream = c.stream;
+        L.ix = ixl; L.bases = c.bases; L.offs = c.offs; L.n = lanes; L.out = d_out; L.err = d_err; L.stats = c.stats;
         L.seg = seg;
         L.cls_mode = 0; L.sep = ix.sep ? 1 : 0; L.stg = sp.stage_lds != 0u ? 1 : 0;
         L.ahd = sp.use_deep ? 2 : (sp.use_ahead ? 1 : 0); L.psh = sp.use_pair ? 1 : 0; L.ring = sp.use_ring ? 1 : 0;
         return ix.idx32 ? launch_walkseg_u32(segv, L, li) : launch_walkseg_u64(segv, L, li);
     };
-    e = launch_seg(1, max_seg, k1, info);
+    e = launch_seg(1, max_seg, k1, c.info);
     if (e != hipSuccess) return e;
-    if (info) {                                           // the dominant kernel: K1
-        info->variant = 14; info->block_threads = 64; info->segmented = 1; info->idx64 = ix.idx32 ? 0 : 1;
-        info->waves_per_cu = 0; info->staged = (int)k1.stage_lds; info->ahead = k1.use_deep ? 2 : (k1.use_ahead ? 1 : 0);
-        info->ff_skip = ff_skip_on(cfg, k1.use_deep, k1.use_ahead) ? 1 : 0;
+    if (c.info) {                                           // the dominant kernel: K1
+        c.info->variant = 14; c.info->block_threads = 64; c.info->segmented = 1; c.info->idx64 = ix.idx32 ? 0 : 1;
+        c.info->waves_per_cu = 0; c.info->staged = (int)k1.stage_lds; c.info->ahead = k1.use_deep ? 2 : (k1.use_ahead ? 1 : 0);
+        c.info->ff_skip = ff_skip_on(cfg, k1.use_deep, k1.use_ahead) ? 1 : 0;
     }
     // (blocks of one wavefront: a boundary lane that has to walk far holds up only the 63 beside it)
     const uint32_t max_over = (uint32_t)std::min<uint64_t>(0xFFFFFFFFull, (uint64_t)cfg.seg_len * (uint64_t)kSegOverrun);
-    hipLaunchKernelGGL((seg_stitch_kernel<6, 0>), dim3((unsigned)((max_seg + kStitchLanes - 1) / kStitchLanes)), dim3(64), 0, stream, ix, d_bases, seg,
+    hipLaunchKernelGGL((seg_stitch_kernel<6, 0>), dim3((unsigned)((max_seg + kStitchLanes - 1) / kStitchLanes)), dim3(64), 0, c.stream, ix, c.bases, seg,
                        pre.seg_j, pre.seg_rem, max_over, pre.on_chain, d_out, pre.join);
-    hipLaunchKernelGGL(seg_finalize_kernel, dim3((unsigned)((n_reads + bt256 - 1) / bt256)), dim3(bt256), 0, stream, pre.go, pre.first, n_reads,
-                       seg.tot, pre.join, pre.seg_l, pre.seg_rem, pre.on_chain, pre.read_fail, d_err, d_stats);
-    hipLaunchKernelGGL((seg_stitch_kernel<6, 1>), dim3((unsigned)((max_seg + kStitchLanes - 1) / kStitchLanes)), dim3(64), 0, stream, ix, d_bases, seg,
+    hipLaunchKernelGGL(seg_finalize_kernel, dim3((unsigned)((c.n_reads + bt256 - 1) / bt256)), dim3(bt256), 0, c.stream, pre.go, pre.first, c.n_reads,
+                       seg.tot, pre.join, pre.seg_l, pre.seg_rem, pre.on_chain, pre.read_fail, d_err, c.stats);
+    hipLaunchKernelGGL((seg_stitch_kernel<6, 1>), dim3((unsigned)((max_seg + kStitchLanes - 1) / kStitchLanes)), dim3(64), 0, c.stream, ix, c.bases, seg,
                        pre.seg_j, pre.seg_rem, max_over, pre.on_chain, d_out, pre.join);
-    e = launch_seg(2, n_reads, k3, nullptr);
+    e = launch_seg(2, c.n_reads, k3, nullptr);
     if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess && bins.bin_width)
-        e = launch_classify(d_out, d_offsets, n_reads, bins.bin_width, bins.thr, bins.above, bins.below, bins.sum_max, stream, d_err);
+    if (e == hipSuccess && c.cls.bin_width)
+        e = launch_classify(d_out, c.offs, c.n_reads, c.cls.bin_width, c.cls.thr, c.cls.above, c.cls.below, c.cls.sum_max, c.stream, d_err);
     return e;
 }
 
@@ -1007,22 +1009,6 @@ size_t take_launch_log(char *buf, size_t cap) {
     return all.size();
 }
 
-// movi_pml_device's own choice ("pml_via_mask" -1): the vector through reset masks wherever the default walk writes the masks itself and
-// the register packer would otherwise write the vector -- batches of short reads (mean length below kOutRingReadLen; long reads keep the
-// ring in LDS, which is as good there: c3 16.76 against 16.66 ms).  Measured, vector out, packer -> fused masks: c2 on the deep rows 78.4
-// -> 86.7 Gbases/s, the random 10 M-row table 62.4 -> 64.8, the 1 B-row table 42.3 -> 46.0 (profiles/r06_mask_path.txt).
-bool pml_vector_via_masks(const DevIndex &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, bool have_seg_ws, bool ordered) {
-    if (n_reads == 0) return false;
-    const PmlPlan P = plan_pml(facts(ix), cfg, n_reads, n_bases, 0, false, have_seg_ws, ordered, true);
-    return !P.seg_eligible && P.v == 14 && P.stage_lds != 0u && n_bases / n_reads < kOutRingReadLen;
-}
-
-bool pml_mask_needs_tmp(const DevIndex &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, bool have_seg_ws) {
-    if (n_reads == 0) return false;
-    const PmlPlan P = plan_pml(facts(ix), cfg, n_reads, n_bases, 0, false, have_seg_ws, false, true);
-    return P.seg_eligible || P.v != 14 || P.stage_lds == 0u;
-}
-
 // The park queue's counter, zeroed in front of the first launch of a mask walk that parks (launch_pml): by a kernel, so that what the
 // second launch resumes never depends on anything but stream order.  It clears the call's counters as well, which the caller's memset has
 // cleared already: captured into a graph (memset, walk, walk), that call was observed to report counters that did not start from zero
@@ -1040,89 +1026,82 @@ hipError_t launch_stats_reset(DevStats *d_stats, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets,
-                      uint64_t n_reads, uint64_t n_bases, uint16_t *d_out, uint8_t *d_err, DevStats *d_stats,
-                      const uint32_t *d_order, const LaunchCfg &cfg, hipStream_t stream, const ClsArgs &cls,
-                      SegWorkspace *seg_ws, int ragged_hint, int *seg_verdict, LaunchInfo *info, const MaskArgs &mask) {
-    if (n_reads == 0) return hipSuccess;
+PmlAsk pml_ask(const PmlCall &c, PmlWant want, int via_mask) {
+    PmlAsk a;
+    a.want = want;
+    a.cm = c.cls_mode();
+    a.logging = c.logging();
+    a.have_seg_ws = c.seg_ws != nullptr;
+    a.ordered = c.order != nullptr;
+    a.out_aligned = (reinterpret_cast<uintptr_t>(c.out) & 15u) == 0;
+    a.via_mask = via_mask;
+    a.park_queue = c.mask.park_q != nullptr;
+    a.park_cap = c.mask.park_cap;
+    return a;
+}
+
+hipError_t launch_pml(const PmlCall &c, const PmlRoute &R) {
+    if (c.n_reads == 0) return hipSuccess;
+    const DevIndex &ix = *c.ix;
+    const LaunchCfg &cfg = *c.cfg;
+    const MaskArgs &mask = c.mask;
+    const PmlPlan &P = R.plan;
+    LaunchInfo *info = c.info;
     if (info) { info->park_lanes = 0; info->ff_skip = 0; }
-    // 0 = PML vector only, 1 = vector + classification bins, 2 = bins only
-    bool want_mask = mask.words != nullptr;                // reset masks out instead of the vector (MaskArgs)
-    const bool logging0 = cls.log_ff != nullptr || cls.log_scan != nullptr;
-    if (want_mask && mask.expand_out) {
-        // the caller wants the VECTOR and lends scratch for masks: through masks only where the walk writes them itself
-        const PmlPlan P0 = plan_pml(facts(ix), cfg, n_reads, n_bases, 0, logging0, seg_ws != nullptr, d_order != nullptr, true);
-        if (P0.seg_eligible || P0.v != 14 || P0.stage_lds == 0u || cls.bin_width != 0) {
-            want_mask = false;
-            d_out = mask.expand_out;
-        }
-    }
-    if (want_mask) d_out = mask.tmp_pml;                   // (the paths without a mask output of their own write here first)
-    const int cm = cls.bin_width == 0 ? 0 : (d_out ? 1 : 2);
-    if (cm == 0 && !d_out && !want_mask) return hipErrorInvalidValue;
-    if (cm != 0 && (!cls.above || !cls.below || !cls.sum_max || want_mask)) return hipErrorInvalidValue;
+    const bool want_mask = R.through_masks();              // reset masks out of the walk (or packed behind it) instead of the vector
+    const bool mask_native = want_mask && R.kind != PmlRouteKind::kMaskFromTmp;
+    uint16_t *const expand_out = R.lent_masks() ? c.out : nullptr;
+    // the vector the walk (or the segment plan) writes: the caller's, or -- masks by way of a vector -- the scratch they are packed from
+    uint16_t *const d_out = !want_mask ? c.out : (R.needs_tmp ? mask.tmp_pml : nullptr);
+    const int cm = c.cls_mode();
     // One resident row layout: blocked- and sampled-thresholds tables are expanded to regular-thresholds rows at upload
     // (expand_blocked_kernel / expand_sampled_kernel), so the query kernels exist for MODE 6 only.
-    if (mode != 6) return hipErrorInvalidValue;
-    const bool logging = cls.log_ff != nullptr || cls.log_scan != nullptr;
-    if (logging && (cm != 0 || want_mask)) return hipErrorInvalidValue;
-    const PmlPlan P = plan_pml(facts(ix), cfg, n_reads, n_bases, cm, logging, seg_ws != nullptr, d_order != nullptr, want_mask);
+    if (c.mode != 6 || !R.valid) return hipErrorInvalidValue;
+    if (want_mask ? (!mask.words || (R.needs_tmp && !d_out) || (R.lent_masks() && !c.out)) : (cm == 0 && !c.out)) return hipErrorInvalidValue;
+    if (cm != 0 && (!c.cls.above || !c.cls.below || !c.cls.sum_max)) return hipErrorInvalidValue;
     const int v = P.v;
-    if (P.seg_eligible && (!want_mask || d_out)) {
+    if (R.seg_first) {
         bool declined = false;
-        const hipError_t es = launch_pml_segmented(ix, d_bases, d_offsets, n_reads, n_bases, d_out, d_err, d_stats, cfg, stream,
-                                                   seg_ws, cfg.pml_variant < 0 || cfg.pml_variant == 14, ragged_hint, &declined, cls,
-                                                   seg_verdict, info);
+        const hipError_t es = launch_pml_segmented(c, d_out, &declined);
         if (es != hipSuccess) return es;
-        if (!declined) return want_mask ? launch_pml_to_mask(d_out, d_offsets, n_reads, n_bases, mask.phase, mask.words, stream) : hipSuccess;
+        if (!declined) return want_mask ? launch_pml_to_mask(d_out, c.offs, c.n_reads, c.n_bases, mask.phase, mask.words, c.stream) : hipSuccess;
     }
     const int bt = P.bt;
-    const uint64_t blocks = (n_reads + bt - 1) / bt;
+    const uint64_t blocks = (c.n_reads + bt - 1) / bt;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
     dim3 grid((unsigned)blocks), block((unsigned)bt);
     size_t dyn_lds = P.dyn_lds;
     DevIndex ixl = ix;
     ixl.stage_lds = P.stage_lds;
     ixl.inwin = cfg.inwin ? 1u : 0u;
-    ixl.hint_w = P.use_deep ? (cfg.hints != 0 ? 2u : 0u) : ((cfg.hints != 0 && ix.hints != 0u && ix.rows2 != nullptr) ? 3u : 0u);
+    ixl.hint_w = R.hint_w;
     ixl.mask_phase = mask.phase & 31u;
-    ixl.ff_skip = (v == 14 && ff_skip_on(cfg, P.use_deep, P.use_ahead)) ? 1u : 0u;
-    const bool mask_native = want_mask && v == 14 && P.stage_lds != 0u;
-    // the vector from the mask walk itself: one-wavefront blocks whose 64 reads are one contiguous, 16-byte aligned stretch of it
-    const bool fused_expand = mask_native && mask.expand_out != nullptr && bt == 64 && d_order == nullptr &&
-                              (reinterpret_cast<uintptr_t>(mask.expand_out) & 15u) == 0 && cfg.fused_expand != 0;
-    ixl.expand_out = fused_expand ? mask.expand_out : nullptr;
-    // Parked lanes (DevIndex::park_at; the plan's park_lanes): where the walk writes the masks itself -- for the vector only on the fused
-    // route, whose resumed lanes expand their own reads -- the caller lent a queue of one record per lane that can park (park_lanes per
-    // wavefront: no read-back needed).  The queue's counter is zeroed by a kernel on the stream (park_reset_kernel), not by a memset.
-    const uint64_t waves = blocks * (uint64_t)(bt / 64);
-    int park_lanes = (mask_native && (mask.expand_out == nullptr || fused_expand) && mask.park_q != nullptr) ? P.park_lanes : 0;
-    // (room for every lane of the second launch's grid, whatever the counter says; slots are 32-bit)
-    const uint64_t park_grid_lanes = (waves * (uint64_t)(park_lanes > 0 ? park_lanes : 0) + (uint64_t)bt - 1) / (uint64_t)bt * (uint64_t)bt;
-    if (park_lanes > 0 && (park_grid_lanes > mask.park_cap || park_grid_lanes > 0x7FFFFFFFull)) park_lanes = 0;
-    ixl.park_at = (uint32_t)park_lanes;
+    ixl.ff_skip = R.ff_skip ? 1u : 0u;
+    ixl.expand_out = R.kind == PmlRouteKind::kVectorFused ? expand_out : nullptr;
+    // Parked lanes (DevIndex::park_at; the route's park_lanes): the queue's counter is zeroed by a kernel on the stream (park_reset_kernel),
+    // not by a memset.
+    ixl.park_at = (uint32_t)R.park_lanes;
     ixl.resume = 0u;
     ixl.park_count = static_cast<unsigned long long *>(mask.park_q);
     ixl.park_q = reinterpret_cast<uint4 *>(static_cast<uint8_t *>(mask.park_q) + kParkHeadBytes);
-    if (want_mask && !mask_native && !d_out) return hipErrorInvalidValue;     // (pml_mask_needs_tmp told the caller)
     hipError_t e = hipSuccess;
     if (v == 14) {
         WalkLaunch L;
-        L.grid = grid; L.block = block; L.dyn_lds = dyn_lds; L.stream = stream;
-        L.ix = ixl; L.bases = d_bases; L.offs = d_offsets; L.n = n_reads; L.out = mask_native ? reinterpret_cast<uint16_t *>(mask.words) : d_out;
-        L.err = d_err; L.stats = d_stats;
-        L.order = d_order; L.cls = cls;
+        L.grid = grid; L.block = block; L.dyn_lds = dyn_lds; L.stream = c.stream;
+        L.ix = ixl; L.bases = c.bases; L.offs = c.offs; L.n = c.n_reads; L.out = mask_native ? reinterpret_cast<uint16_t *>(mask.words) : d_out;
+        L.err = c.err; L.stats = c.stats;
+        L.order = c.order; L.cls = c.cls;
         L.cls_mode = cm; L.sep = ix.sep ? 1 : 0; L.stg = ixl.stage_lds != 0u ? 1 : 0;
-        L.ahd = P.use_deep ? 2 : (P.use_ahead ? 1 : 0); L.psh = P.use_pair ? 1 : 0; L.ring = mask_native ? 2 : (P.use_ring ? 1 : 0);
-        if (park_lanes > 0) {
-            hipLaunchKernelGGL(park_reset_kernel, dim3(1), dim3(64), 0, stream, ixl.park_count, d_stats);
+        L.ahd = R.ahd; L.psh = R.psh; L.ring = R.ring;
+        if (R.park_lanes > 0) {
+            hipLaunchKernelGGL(park_reset_kernel, dim3(1), dim3(64), 0, c.stream, ixl.park_count, c.stats);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = ix.idx32 ? launch_walk_u32(L, info) : launch_walk_u64(L, info);
-        if (e == hipSuccess && park_lanes > 0) {
+        if (e == hipSuccess && R.park_lanes > 0) {
             // the second launch: the same kernel resumes the parked reads, 64 to a wavefront -- a grid for every record the first can have
             // written, the same dynamic LDS, the same stream (stream order is all the synchronisation there is); `info` names the first
-            L.grid = dim3((unsigned)(park_grid_lanes / (uint64_t)bt));
+            L.grid = dim3((unsigned)R.park_grid);
             L.ix.park_at = 0u;
             L.ix.resume = 1u;
             L.order = nullptr;                             // (a record names its read)
@@ -1131,7 +1110,7 @@ hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
     } else {
         // the base-synchronous kernels (every one takes at most 64 KiB of dynamic LDS: the cap's padding)
         if (dyn_lds > 65536) dyn_lds = 65536 - 1024;
-#define MOVI_LAUNCH_PML(V, C) hipLaunchKernelGGL((pml_kernel<6, V, C>), grid, block, dyn_lds, stream, ixl, d_bases, d_offsets, n_reads, d_out, d_err, d_stats, d_order, cls)
+#define MOVI_LAUNCH_PML(V, C) hipLaunchKernelGGL((pml_kernel<6, V, C>), grid, block, dyn_lds, c.stream, ixl, c.bases, c.offs, c.n_reads, d_out, c.err, c.stats, c.order, c.cls)
         if (v == 0) MOVI_LAUNCH_PML(0, 0);
         else if (cm == 0) MOVI_LAUNCH_PML(1, 0);
         else if (cm == 1) MOVI_LAUNCH_PML(1, 1);
@@ -1144,13 +1123,13 @@ hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, cons
         info->variant = v;
         info->block_threads = bt; info->waves_per_cu = P.wpc; info->segmented = 0; info->idx64 = ix.idx32 ? 0 : 1;
         info->staged = (int)ixl.stage_lds;
-        info->ahead = P.use_deep ? 2 : (P.use_ahead ? 1 : 0);
-        info->park_lanes = park_lanes;
+        info->ahead = R.ahd;
+        info->park_lanes = R.park_lanes;
         info->ff_skip = (int)ixl.ff_skip;
     }
-    if (e == hipSuccess && want_mask && !mask_native) e = launch_pml_to_mask(d_out, d_offsets, n_reads, n_bases, mask.phase, mask.words, stream);
-    if (e == hipSuccess && mask_native && mask.expand_out != nullptr && !fused_expand)
-        e = launch_pml_expand(mask.words, d_offsets, n_reads, n_bases, mask.phase, mask.expand_out, stream);
+    if (e == hipSuccess && R.kind == PmlRouteKind::kMaskFromTmp) e = launch_pml_to_mask(d_out, c.offs, c.n_reads, c.n_bases, mask.phase, mask.words, c.stream);
+    if (e == hipSuccess && R.kind == PmlRouteKind::kVectorExpand)
+        e = launch_pml_expand(mask.words, c.offs, c.n_reads, c.n_bases, mask.phase, expand_out, c.stream);
     return e;
 }
 

@@ -281,22 +281,20 @@ using SegWorkspace = DevBuf;
 // reset match_len (its PML is 0); phase = the low five bits of the batch's first base's position in the caller's whole read set
 // (sub-batches of one call then concatenate word for word).  The default walk writes them natively (pml_kernel_flatp<..., RING = 2>);
 // every other path (segment-parallel long reads, the base-synchronous kernels) writes its vector to tmp_pml (n_bases u16, which the
-// caller provides whenever pml_mask_needs_tmp says so) and pml_to_mask_kernel packs it.
+// caller provides whenever the call's route says needs_tmp) and pml_to_mask_kernel packs it.
+// The mask buffers of one PML call.  Which of them the call uses is the route's to say (PmlRoute, movi_launch_policy.hpp): `words` are the
+// result (kMaskNative, kMaskFromTmp) or scratch the caller lent for the vector (kVectorFused: the mask walk expands its wavefronts' reads
+// itself; kVectorExpand: the pml_expand_* kernels do it behind the walk) and stay unused on the plain vector route.
 struct MaskArgs {
     uint32_t *words = nullptr;
     uint32_t phase = 0;
     uint16_t *tmp_pml = nullptr;
-    // non-null: the caller wants the u16 VECTOR here and `words` is scratch (movi_pml_device through masks): the mask walk expands its
-    // wavefronts' reads itself where it can (one-wavefront blocks, reads in order, a 16-byte aligned vector), pml_expand_* kernels do
-    // it behind the walk otherwise; a batch whose path has no mask output of its own simply writes the vector (no masks at all)
-    uint16_t *expand_out = nullptr;
     // parked lanes (DevIndex::park_at): device scratch of kParkHeadBytes + park_cap records of kParkRecBytes; null = the walk parks nothing
     void *park_q = nullptr;
     uint64_t park_cap = 0;
 };
 uint64_t pml_mask_words(uint64_t n_reads, uint64_t n_bases, uint32_t phase);          // words a batch's masks take (gap words included)
-bool pml_mask_needs_tmp(const DevIndex &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, bool have_seg_ws);
-bool pml_vector_via_masks(const DevIndex &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, bool have_seg_ws, bool ordered);   // movi_pml_device's policy: the vector of this batch through reset masks
+TableFacts facts(const DevIndex &ix);     // what the launch policy reads of the index
 // u16 vector <-> masks, streaming (one lane per read; a wavefront per read from a mean length of 2048 bases)
 hipError_t launch_pml_expand(const uint32_t *d_words, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t phase,
                              uint16_t *d_out, hipStream_t stream);
@@ -313,14 +311,33 @@ hipError_t preload_pack();                // load the translation unit's code ob
 hipError_t launch_pml_to_mask(const uint16_t *d_pml, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t phase,
                               uint32_t *d_words, hipStream_t stream);
 
-// d_out == nullptr is allowed when cls.bin_width != 0: verdict bins only, no PML vector is written.
-// seg_ws != nullptr allows the segment-parallel path for batches of long reads (cfg.seg_len); ragged_hint: 1 / 0 = the
-// caller knows that the longest read is / is not more than 1.5 x the mean, -1 = it does not know (device offsets only).
-hipError_t launch_pml(int mode, const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets,
-                      uint64_t n_reads, uint64_t n_bases, uint16_t *d_out, uint8_t *d_err, DevStats *d_stats,
-                      const uint32_t *d_order, const LaunchCfg &cfg, hipStream_t stream,
-                      const ClsArgs &cls = ClsArgs(), SegWorkspace *seg_ws = nullptr, int ragged_hint = -1,
-                      int *seg_verdict = nullptr, LaunchInfo *info = nullptr, const MaskArgs &mask = MaskArgs());
+// One PML call as launch_pml takes it, beside the plan (plan_pml) that says what to do with it.
+struct PmlCall {
+    int mode = 6;                         // the resident row layout (the query kernels exist for 6 only)
+    const DevIndex *ix = nullptr;
+    const LaunchCfg *cfg = nullptr;
+    const uint8_t *bases = nullptr;
+    const uint64_t *offs = nullptr;
+    uint64_t n_reads = 0, n_bases = 0;
+    uint16_t *out = nullptr;              // the u16 vector; null: verdict bins only (cls.bin_width != 0), or reset masks are the result
+    uint8_t *err = nullptr;
+    DevStats *stats = nullptr;
+    const uint32_t *order = nullptr;
+    hipStream_t stream = nullptr;
+    ClsArgs cls;
+    SegWorkspace *seg_ws = nullptr;       // non-null allows the segment-parallel path for batches of long reads (cfg.seg_len)
+    int ragged_hint = -1;                 // 1 / 0 = the caller knows that the longest read is / is not more than 1.5 x the mean, -1 = it does not (device offsets only)
+    int *seg_verdict = nullptr;
+    LaunchInfo *info = nullptr;
+    MaskArgs mask;
+    int cls_mode() const { return cls.bin_width == 0 ? 0 : (out ? 1 : 2); }   // 0 = PML vector only, 1 = vector + classification bins, 2 = bins only
+    bool logging() const { return cls.log_ff != nullptr || cls.log_scan != nullptr; }
+};
+// What the call asks of the policy: `want` and "pml_via_mask" from the caller, the rest read off the call's pointers.
+PmlAsk pml_ask(const PmlCall &c, PmlWant want, int via_mask);
+// Validates, runs the route's pre-step (the park queue's reset), the walk (or the segment plan where it has the first say) and the
+// route's post-step (masks packed from the vector in tmp, or the vector expanded from the masks).
+hipError_t launch_pml(const PmlCall &c, const PmlRoute &route);
 
 hipError_t launch_count(int mode, const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets,
                         uint64_t n_reads, uint64_t *d_matched, uint64_t *d_count, uint8_t *d_err,

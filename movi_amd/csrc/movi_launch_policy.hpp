@@ -1,4 +1,6 @@
 // movi_launch_policy.hpp -- the launch policy of the PML / ZML / count queries: which kernel, which block, how much dynamic LDS and what it holds.
+// For a PML call also the ROUTE its results take out of the walk (plan_pml: the vector, reset masks, the vector through masks), decided once:
+// the C ABI's one PML helper asks, sizes the scratch the route needs and hands the plan to launch_pml, which acts on it and derives nothing.
 // Plain C++ over plain values (no HIP type, no runtime call): movi_kernels.hip acts on these plans, tests/test_launch_policy_cpu.py prints them.
 #pragma once
 #include <stddef.h>
@@ -68,8 +70,23 @@ inline size_t cap_lds(int blocks_per_cu, int floor, size_t ceiling = ~(size_t)0)
 }
 
 // ------------------------------------------------------------------------------------------------------------------- PML
-// The launch policy of one PML call, apart from the segment plan's own decisions (plan_pml_seg): launch_pml acts on it;
-// pml_mask_needs_tmp asks it whether the reset-mask output can come straight from the walk.
+// What a PML call asks of the policy: what the caller wants back, and the facts that sit in its pointers and in the handle's options.
+enum class PmlWant {
+    kVector,              // the u16 vector
+    kMasks,               // reset masks are the result
+    kVectorLendsMasks,    // the vector; the caller lends mask words as scratch: through masks where the walk writes them itself
+};
+struct PmlAsk {
+    PmlWant want = PmlWant::kVector;
+    int cm = 0;                      // 0 = PML vector only, 1 = vector + classification bins, 2 = bins only
+    bool logging = false, have_seg_ws = false, ordered = false;
+    bool out_aligned = true;         // the vector starts on a 16-byte boundary (the fused expansion's stores)
+    int via_mask = 1;                // kVectorLendsMasks ("pml_via_mask"): 1 = wherever the walk writes masks itself, -1 = only for batches of short reads (mean length < kOutRingReadLen: long reads keep the LDS ring)
+    bool park_queue = false;         // a park queue is lent ...
+    uint64_t park_cap = 0;           // ... of this many records
+};
+
+// The walk of one PML call, apart from the segment plan's own decisions (plan_pml_seg): kernel, block, dynamic LDS, rows.
 struct PmlPlan {
     int v = 14, bt = 64, wpc = 0;
     bool seg_eligible = false;       // a batch of long reads: the segment plan gets the first say (it may decline)
@@ -77,7 +94,30 @@ struct PmlPlan {
     uint32_t stage_lds = 0;
     bool use_ring = false, use_ahead = false, use_pair = false;
     bool use_deep = false;           // the walk runs on the deep rows (DevIndex::rows3: three bases per gather)
-    int park_lanes = 0;              // > 0: a mask walk of this plan parks a wavefront's last lanes for a second launch (launch_pml still needs a queue and, for the vector, the fused expansion)
+    int park_lanes = 0;              // > 0: a mask walk of this plan parks a wavefront's last lanes for a second launch (plan_pml: where a queue is lent and, for the vector, the expansion is fused)
+};
+
+// Where the results of one PML call leave the walk, and everything launch_pml needs to act on it: decided once, by plan_pml.
+enum class PmlRouteKind {
+    kVector,              // the u16 vector straight from the walk (register packer or LDS ring; fused bins ride here)
+    kMaskNative,          // reset masks straight from the walk (pml_kernel_flatp<..., RING = 2>)
+    kMaskFromTmp,         // the walk cannot write masks: its vector goes to `tmp` and launch_pml_to_mask packs it
+    kVectorFused,         // the mask walk's wavefronts expand their own reads into the vector (DevIndex::expand_out)
+    kVectorExpand,        // a native mask walk, launch_pml_expand behind it
+};
+struct PmlRoute {
+    PmlPlan plan;
+    PmlRouteKind kind = PmlRouteKind::kVector;
+    bool valid = true;               // false: the call asks for what no kernel gives (masks with bins or logs, logs with bins)
+    bool seg_first = false;          // the segment plan gets the first say; it writes a vector (masks: into `tmp`, packed behind it); if it declines: `kind`
+    bool needs_tmp = false;          // masks as the result by way of a vector: the caller provides n_bases u16 of scratch
+    int park_lanes = 0;              // the walk parks at this many lanes (0: no second launch) -- the queue fits ...
+    uint64_t park_grid = 0;          // ... the blocks of the second launch
+    uint32_t hint_w = 0;             // DevIndex::hint_w
+    bool ff_skip = false;            // DevIndex::ff_skip
+    int ahd = 0, psh = 0, ring = 0;  // the walk kernel's template selectors (WalkLaunch)
+    bool through_masks() const { return kind != PmlRouteKind::kVector; }                                       // the walk (or the packer behind it) writes mask words
+    bool lent_masks() const { return kind == PmlRouteKind::kVectorFused || kind == PmlRouteKind::kVectorExpand; }   // ... the caller's scratch
 };
 
 // Reads staged through LDS (pml_kernel_flatp<..., STG = 1>): the block's dynamic LDS holds the next stage_lds bases of each
@@ -114,8 +154,10 @@ inline bool ff_skip_on(const LaunchCfg &cfg, bool use_deep, bool use_ahead) {
     return cfg.ff_skip > 0 || (cfg.ff_skip < 0 && (use_deep ? kFfSkipDeep : kFfSkipAhead) != 0);
 }
 
-inline PmlPlan plan_pml(const TableFacts &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, int cm, bool logging,
-                        bool have_seg_ws, bool ordered, bool want_mask) {
+// The walk of a call (a.cm, a.logging, a.have_seg_ws, a.ordered) that writes reset masks (want_mask) or the vector: plan_pml's core.
+inline PmlPlan plan_pml_walk(const TableFacts &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, const PmlAsk &a, bool want_mask) {
+    const int cm = a.cm;
+    const bool logging = a.logging, have_seg_ws = a.have_seg_ws, ordered = a.ordered;
     PmlPlan P;
     // Variants: 0 first correct kernel (serves --logs), 1 base-synchronous packed I/O (tables of fewer than 8 rows, batches of
     // fewer than 16 bases; A/B), 14 = the lane state machine over row windows (pml_kernel_flatp, movi_walk.hpp; the default).
@@ -183,6 +225,54 @@ inline PmlPlan plan_pml(const TableFacts &ix, const LaunchCfg &cfg, uint64_t n_r
         P.park_lanes = cfg.park_lanes > 0 ? std::min(cfg.park_lanes, 63) : ((cfg.park_lanes < 0 && auto_on) ? kParkLanesAuto : 0);
     }
     return P;
+}
+
+// The plan of one PML call: the walk (plan_pml_walk) and the route its results take.
+// The walk writes reset masks itself where it is the staged default walk (one-wavefront blocks of variant 14) of a plain query -- no bins,
+// no logs.  Masks as the result come from there, or by way of a vector in `tmp` (the segment plan, the base-synchronous kernels, unstaged
+// launches).  A caller who wants the VECTOR and lends mask words gets it through masks only where the walk writes them itself and the
+// segment plan has no say -- the walk writes one bit per base (a ninth fewer vector instructions per iteration than the u16 packer, a
+// third of the write traffic): c2 on the deep rows 78.4 -> 86.7 Gbases/s, the random 10 M-row table 62.4 -> 64.8, the 1 B-row table
+// 42.3 -> 46.0 (profiles/r06_mask_path.txt) -- and, by the default policy (via_mask -1), the batch is one of short reads: long reads
+// keep the ring in LDS, which is as good there (c3 16.76 against 16.66 ms).  Everywhere else such a call is planned again as the plain
+// vector (the LDS ring is wanted again) and the lent words stay unused.
+inline PmlRoute plan_pml(const TableFacts &ix, const LaunchCfg &cfg, uint64_t n_reads, uint64_t n_bases, const PmlAsk &a) {
+    PmlRoute R;
+    if (n_reads == 0) { R.valid = false; return R; }   // (an empty call has no route; the mean read length below divides by n_reads)
+    const bool plain_query = a.cm == 0 && !a.logging;
+    R.valid = !(a.want == PmlWant::kMasks && !plain_query) && !(a.logging && a.cm != 0);
+    const bool lends = a.want == PmlWant::kVectorLendsMasks;
+    PmlPlan &P = R.plan;
+    P = plan_pml_walk(ix, cfg, n_reads, n_bases, a, a.want != PmlWant::kVector);
+    auto writes_masks = [&] { return P.v == 14 && P.stage_lds != 0u; };
+    bool masks = a.want == PmlWant::kMasks;
+    if (lends) {
+        masks = plain_query && !P.seg_eligible && writes_masks() && (a.via_mask > 0 || n_bases / n_reads < kOutRingReadLen);
+        if (!masks) P = plan_pml_walk(ix, cfg, n_reads, n_bases, a, false);
+    }
+    const bool native = masks && writes_masks();
+    // the vector from the mask walk itself: one-wavefront blocks whose 64 reads are one contiguous, 16-byte aligned stretch of it
+    const bool fused = native && lends && P.bt == 64 && !a.ordered && a.out_aligned && cfg.fused_expand != 0;
+    R.kind = !masks ? PmlRouteKind::kVector : !native ? PmlRouteKind::kMaskFromTmp : !lends ? PmlRouteKind::kMaskNative
+             : fused ? PmlRouteKind::kVectorFused : PmlRouteKind::kVectorExpand;
+    R.seg_first = P.seg_eligible;
+    R.needs_tmp = masks && (P.seg_eligible || !native);
+    // Parked lanes (DevIndex::park_at; the walk's park_lanes): where the walk writes the masks itself -- for the vector only on the fused
+    // route, whose resumed lanes expand their own reads -- and the caller lent a queue with room for every lane of the second launch's
+    // grid, whatever the counter says: park_lanes per wavefront, whole blocks (no read-back needed); slots are 32-bit.
+    const uint64_t bt = (uint64_t)P.bt, waves = (n_reads + bt - 1) / bt * (bt / 64);
+    const int park = (native && (!lends || fused) && a.park_queue) ? P.park_lanes : 0;
+    const uint64_t park_grid_lanes = (waves * (uint64_t)(park > 0 ? park : 0) + bt - 1) / bt * bt;
+    if (park > 0 && park_grid_lanes <= a.park_cap && park_grid_lanes <= 0x7FFFFFFFull) {
+        R.park_lanes = park;
+        R.park_grid = park_grid_lanes / bt;
+    }
+    R.hint_w = P.use_deep ? (cfg.hints != 0 ? 2u : 0u) : ((cfg.hints != 0 && ix.hints && ix.rows2) ? 3u : 0u);
+    R.ff_skip = P.v == 14 && ff_skip_on(cfg, P.use_deep, P.use_ahead);
+    R.ahd = P.use_deep ? 2 : (P.use_ahead ? 1 : 0);
+    R.psh = P.use_pair ? 1 : 0;
+    R.ring = native ? 2 : (P.use_ring ? 1 : 0);
+    return R;
 }
 
 // The segment length of one call: cfg.seg_len, or shorter (down to 512) when the batch is so small that even then the

@@ -44,6 +44,24 @@ def test_plans_equal_the_recorded_launches(driver):
     assert not bad, (len(bad), bad[:5])
 
 
+def test_routes_equal_the_recorded_launches(driver):
+    """tests/golden/launch_route_table.txt: the route of a PML call (plan_pml) -- where its results leave the walk, the scratch it needs,
+    the parked lanes and their second grid, hint_w, ff_skip, the walk kernel's selectors -- beside what the launcher and the C ABI's four
+    layers derived around the plan BEFORE the route moved into the header (tools/launch_policy_cases.py says how it was recorded, and
+    marks the two columns the one planner changes on purpose)."""
+    table = open(os.path.join(GOLDEN, "launch_route_table.txt")).read().splitlines()
+    fields, defaults = table[0].split()[1:], [int(x) for x in table[1].split()[1:]]
+    assert len(fields) == 36 and len(defaults) == 36 and fields[:28] == FIELDS
+    rows = [ln.split(" => ") for ln in table[2:] if not ln.startswith("#")]
+    cases = [dict(zip(fields, defaults), **{k: int(v) for k, v in (kv.split("=") for kv in left.split())}) for left, _ in rows]
+    text = "".join(" ".join(str(c[f]) for f in fields) + "\n" for c in cases)
+    got = subprocess.run([driver, "route"], input=text.encode(), capture_output=True, check=True).stdout.decode().splitlines()
+    assert len(rows) >= 300 and len(got) == len(rows)
+    assert {want.split()[1] for _, want in rows} == {"vector", "mask_native", "mask_from_tmp", "vector_fused", "vector_expand", "invalid"}
+    bad = [(left, g, want) for (left, want), g in zip(rows, got) if g != want]
+    assert not bad, (len(bad), bad[:5])
+
+
 def test_occupancy_caps_by_hand(driver):
     # A cap of bpc blocks per CU pads every block to dyn_lds + 1 KiB (static LDS and granule) so that bpc of them fill the CU's 160 KiB
     # and bpc + 1 do not; a lane stages dyn_lds / 64 bases, rounded down to 16.
