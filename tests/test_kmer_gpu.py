@@ -407,3 +407,27 @@ def test_cli(texts, tmp_path):
     assert r.returncode == 0, r.stderr
     assert r.stdout == _kmer_lines(ids, reads, o, 12)
     o.close()
+
+
+def test_cli_more_runs_than_the_first_guess(texts, tmp_path):
+    """The command gives a shard's runs room for 8 per read and one per 16 bases first, and calls again with room for exactly what the
+    first call found.  Six random reads of 200 bases at -k 8 (about every other 8-mer is in the text: 578 runs by the restatement) against
+    a first guess of 6 * 8 + 1200 / 16 = 123 (two shards: 3 * 8 + 600 / 16 = 61 each), so the bytes below come from the second call."""
+    from oracle.oracle import Oracle
+    rng = np.random.default_rng(7)
+    seqs = [bytes(rng.choice(list(b"ACGT"), 200).astype(np.uint8)) for _ in range(6)]
+    idx = tmp_path / "idx"
+    idx.mkdir()
+    (idx / "index.movi").write_bytes(texts[False][6])
+    fa = tmp_path / "q.fa"
+    fa.write_bytes(b"".join(b">r%d\n%s\n" % (i, s) for i, s in enumerate(seqs)))
+    o = Oracle(texts[False][6])
+    exp, _ = kmer_ref.restate(o, seqs, (8,))
+    per_read = [len(runs) for _, runs in exp[8]]
+    assert sum(per_read) > 6 * 8 + 1200 // 16 and min(sum(per_read[:3]), sum(per_read[3:])) > 3 * 8 + 600 // 16
+    want = _kmer_lines([b"r%d" % i for i in range(6)], seqs, o, 8)
+    for extra, env in (([], {}), (["--gpus", "2"], {"MOVI_SHARE_GPU": "1"})):
+        r = subprocess.run([MOVI, "query", "-i", str(idx), "--kmer", "-k", "8", "-r", str(fa), "--stdout"] + extra,
+                           capture_output=True, env=dict(os.environ, **env))
+        assert r.returncode == 0 and r.stdout == want, (extra, r.stderr)
+    o.close()

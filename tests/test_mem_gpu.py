@@ -367,6 +367,52 @@ def test_cli(texts, tmp_path):
     o.close()
 
 
+def _cli_setup(texts, tmp_path, seqs):
+    import movi_amd
+    from oracle.oracle import Oracle
+    idx = tmp_path / "idx"
+    idx.mkdir()
+    (idx / "index.movi").write_bytes(texts[False][6])
+    fa = tmp_path / "q.fa"
+    fa.write_bytes(b"".join(b">r%d\n%s\n" % (i, s) for i, s in enumerate(seqs)))
+    return idx, fa, Oracle(texts[False][6]), movi_amd.parse_index_image(texts[False][6])[0].code_of
+
+
+def test_cli_shards(texts, tmp_path):
+    """--gpus 3 shards each chunk of reads over three handles (MOVI_SHARE_GPU=1: every logical GPU is device 0) and puts the shards' MEMs
+    back in read order: the same bytes as one GPU, from the restatement."""
+    ref = _ref()
+    seqs = [ref[100:300], ref[500:560] + b"NNN" + ref[600:700], b"ACGTN" * 10, ref[900:1000].lower() + ref[1000:1100], ref[50:60],
+            ref[1200:1300] + b"T" + ref[1301:1500], ref[3000:3400]]
+    idx, fa, o, code_of = _cli_setup(texts, tmp_path, seqs)
+    want = _mem_lines([b"r%d" % i for i in range(len(seqs))], seqs, o, code_of, 20)
+    assert want.count(b"\n") >= 5                                 # five of the reads hold 60 bases of the text or more: every shard has MEMs
+    for extra, env in (([], {}), (["--gpus", "3"], {"MOVI_SHARE_GPU": "1"})):
+        r = subprocess.run([MOVI, "query", "-i", str(idx), "--mem", "--ftab-k", "12", "-l", "20", "-r", str(fa), "--stdout"] + extra,
+                           capture_output=True, env=dict(os.environ, **env))
+        assert r.returncode == 0 and r.stdout == want, (extra, r.stderr)
+    o.close()
+
+
+def test_cli_more_mems_than_the_first_guess(texts, tmp_path):
+    """The command gives a shard's MEMs room for 8 per read and one per 16 bases first, and calls again with room for exactly what the
+    first call found.  Six random reads of 200 bases at -l 4 hold 675 MEMs against a first guess of 6 * 8 + 1200 / 16 = 123 (two shards:
+    3 * 8 + 600 / 16 = 61 each), so the bytes below come from the second call."""
+    rng = np.random.default_rng(7)
+    seqs = [bytes(rng.choice(list(b"ACGT"), 200).astype(np.uint8)) for _ in range(6)]
+    idx, fa, o, code_of = _cli_setup(texts, tmp_path, seqs)
+    exp, _ = mem_ref.restate(o, seqs, code_of, (4,))
+    per_read = [len(ms) for ms in exp[4]]
+    assert sum(per_read) > 6 * 8 + 1200 // 16 and min(sum(per_read[:3]), sum(per_read[3:])) > 3 * 8 + 600 // 16
+    want = _mem_lines([b"r%d" % i for i in range(6)], seqs, o, code_of, 4)
+    assert want.count(b"\n") == sum(per_read)
+    for extra, env in (([], {}), (["--gpus", "2"], {"MOVI_SHARE_GPU": "1"})):
+        r = subprocess.run([MOVI, "query", "-i", str(idx), "--mem", "--ftab-k", "12", "-l", "4", "-r", str(fa), "--stdout"] + extra,
+                           capture_output=True, env=dict(os.environ, **env))
+        assert r.returncode == 0 and r.stdout == want, (extra, r.stderr)
+    o.close()
+
+
 def test_count_beyond_u16(built_lib, tmp_path):
     """A MEM that occurs more than 65535 times: the ABI returns occ, the file prints occ mod 2^16 (mem_t::count is a uint16_t)."""
     import movi_amd
