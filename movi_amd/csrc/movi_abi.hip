@@ -4,6 +4,7 @@
 // query entry point fails with MOVI_ERR_NO_DEVICE / MOVI_ERR_HIP.
 #include "../../include/movi_hip.h"
 #include "movi_kernels.hpp"
+#include "movi_host_plan.hpp"
 #include "movi_expand_host.hpp"
 #include "movi_pack_host.hpp"
 #include "movi_build.hpp"
@@ -1533,25 +1534,6 @@ int movi_last_stats(movi_index_t *ix, void *stream, movi_query_stats_t *stats) {
 
 namespace {
 
-// Reads are cut into chunks so that the staging buffers stay bounded whatever the input size:
-// about kChunkBases bases per launch -- but never so few READS that the GPU runs empty.  One lane
-// walks one read, so a chunk of long reads (2^28 bases = 27 k reads of 10 kbp) would leave most of
-// the 524 k lane slots idle and the walk latency-bound; such chunks grow until they hold
-// kMinChunkReads reads or kMaxChunkBases bases (3 B of device memory per base, 6 GiB).
-constexpr uint64_t kChunkBases = 1ull << 28;
-constexpr uint64_t kMinChunkReads = 1ull << 18;
-constexpr uint64_t kMaxChunkBases = 1ull << 31;
-// The overlapped path (page-locked caller buffers) wants several chunks per call -- chunk i+1 goes up and chunk i-1 comes
-// down while chunk i is walked, and the kernels of neighbouring chunks share the GPU -- so it cuts finer: about an
-// eighth of the call, between 2^22 and 2^28 bases, and at least 2^15 reads (a download can only start when a walk
-// has finished, so chunks must be short; the lanes in flight are those of the kPipeAhead chunks being walked, and a
-// read takes as long as it takes however few lanes walk beside it -- long reads are best cut into just those
-// kPipeAhead chunks: 100 k x 10 kbp as 3 x 33 k reads 57 ms, as 8 x 12.5 k reads 85 ms, synchronous 74 ms).
-constexpr uint64_t kPipeMinBases = 1ull << 22;
-constexpr uint64_t kPipeMinReads = 1ull << 15;
-constexpr uint64_t kPipeTargetChunks = 8;
-constexpr uint64_t kPipeMaskChunks = 16;
-
 // Where a *_host call's bases come from: the caller's ASCII bytes (h_bases, indexed by offsets[]), or reads packed two bits per base
 // plus their exception list (include/movi_hip.h): those go up as they are, a quarter of the bytes, and every chunk is unpacked on the
 // device into the staging the ASCII bytes would have been copied to.  The ASCII form makes exactly the HIP calls it always made.
@@ -1567,7 +1549,7 @@ struct ReadSource {
         : two_bit(true), packed(h_packed), exc_pos(h_exc_pos), exc_byte(h_exc_byte), n_exc(n) {}
     // what crosses the link for bases [b0, b0 + nb): where it starts in the caller's buffer and how long it is
     const uint8_t *up_from(uint64_t b0) const { return two_bit ? packed + (b0 >> 2) : ascii + b0; }
-    size_t up_bytes(uint64_t b0, uint64_t nb) const { return two_bit ? (size_t)(((b0 + nb + 3) >> 2) - (b0 >> 2)) : (size_t)nb; }
+    size_t up_bytes(uint64_t b0, uint64_t nb) const { return two_bit ? packed_span_bytes(b0, nb) : (size_t)nb; }
 };
 // A chunk of a packed call: d_packed holds the caller's packed bytes from byte b0 >> 2 on; its slice of the exception list (already on the
 // device, the whole call's) is found on the host.  Two kernels on the chunk's stream (movi_walk_pack.hip).
@@ -1591,9 +1573,9 @@ struct ChunkCtx {
     SegWorkspace *seg_ws = nullptr;
     int ragged_hint = -1;            // the chunk's longest read is (1) / is not (0) more than 1.5 x its mean: launch_pml's segment policy
     int *seg_verdict = nullptr;      // one probe per call: the first chunk's verdict serves the others (launch_pml_segmented)
-    uint64_t first = 0, b0 = 0;      // the chunk: its first read and the position of its first base in the caller's arrays
     HostPool::Group *grp = nullptr;  // overlapped path: the slot's group of worker-pool tasks (what reads the slot's page-locked block)
     bool async = false;
+    bool delivered = false;          // overlapped path, set by fetch(): a host function on the chunk's stream hands its mask words on, harvest() need not
     template <typename T>
     hipError_t alloc(int slot, size_t bytes, T **out) {
         hipError_t e = grow(d[slot], bytes);
@@ -1601,9 +1583,9 @@ struct ChunkCtx {
         return e;
     }
     // the chunk as a PML / ZML call: its reads, stream, counters, segment state and scratch slots (the caller adds where the results go)
-    MlRequest request(const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) const {
+    MlRequest request(const HostChunk &c, const uint8_t *db, const uint64_t *dof, uint8_t *derr) const {
         MlRequest r;
-        r.bases = db; r.offs = dof; r.n_reads = nr; r.n_bases = nb; r.err = derr; r.stream = s;
+        r.bases = db; r.offs = dof; r.n_reads = c.nr; r.n_bases = c.nb; r.err = derr; r.stream = s;
         r.stats = d_stats; r.seg_ws = seg_ws; r.ragged_hint = ragged_hint; r.seg_verdict = seg_verdict; r.chunk = d;
         return r;
     }
@@ -1668,7 +1650,8 @@ int check_offsets(const uint64_t *h_offsets, uint64_t n_reads) {
     return MOVI_OK;
 }
 
-void add_stats(movi_query_stats_t *acc, uint64_t nb, const DevStats &h) {
+template <typename Counters>                                 // (DevStats, or what movi_last_stats made of them)
+void add_stats(movi_query_stats_t *acc, uint64_t nb, const Counters &h) {
     acc->bases += nb;
     acc->fast_forwards += h.fast_forwards;
     acc->scans += h.scans;
@@ -1680,22 +1663,34 @@ void add_stats(movi_query_stats_t *acc, uint64_t nb, const DevStats &h) {
     acc->rewalked += h.rewalked;
 }
 
-// One kind of query behind a *_host entry point:
-//   launch(ctx, d_bases, d_offs, nr, nb, d_err)  allocates the chunk's result staging from ctx and enqueues the kernel;
-//   fetch(ctx, first, nr, b0, nb)                enqueues the results' way back (ctx.down / ctx.down_small);
-//   harvest(h_small, first, nr, group)           overlapped path only, after the chunk's stream has drained: per-read
-//                                                results from the page-locked block to the caller's arrays;
-//   small_bytes                                  page-locked bytes per read that fetch / harvest use.
-template <typename Launch, typename Fetch, typename Harvest>
-int run_chunked(movi_index *ix, const ReadSource &src, const uint64_t *h_offsets, uint64_t n_reads,
-                uint8_t *h_read_err, movi_query_stats_t *stats, Launch launch, Fetch fetch, Harvest, size_t, size_t) {
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (src.two_bit && src.n_exc) {                           // the call's exception list, once
-        HIP_TRY(grow(ix->scratch[movi_index::kExcPos], (size_t)src.n_exc * 8));
-        HIP_TRY(grow(ix->scratch[movi_index::kExcByte], (size_t)src.n_exc));
-        HIP_TRY(hipMemcpy(ix->scratch[movi_index::kExcPos].ptr(), src.exc_pos, (size_t)src.n_exc * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(ix->scratch[movi_index::kExcByte].ptr(), src.exc_byte, (size_t)src.n_exc, hipMemcpyHostToDevice));
-    }
+// A packed call's exception list goes up once, ahead of every chunk's bytes: synchronously, or (overlapped path) on the upload stream.
+int upload_exceptions(movi_index *ix, const ReadSource &src, bool on_upload_stream) {
+    if (!src.two_bit || !src.n_exc) return MOVI_OK;
+    DevBuf &pos = ix->scratch[movi_index::kExcPos], &byte = ix->scratch[movi_index::kExcByte];
+    const size_t n = (size_t)src.n_exc;
+    hipError_t e = hipSuccess;
+    if (on_upload_stream && !ix->pipe_up) e = create_upload_stream(&ix->pipe_up);
+    if (e == hipSuccess) e = grow(pos, n * 8);
+    if (e == hipSuccess) e = grow(byte, n);
+    if (e == hipSuccess) e = on_upload_stream ? hipMemcpyAsync(pos.ptr(), src.exc_pos, n * 8, hipMemcpyHostToDevice, ix->pipe_up)
+                                              : hipMemcpy(pos.ptr(), src.exc_pos, n * 8, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = on_upload_stream ? hipMemcpyAsync(byte.ptr(), src.exc_byte, n, hipMemcpyHostToDevice, ix->pipe_up)
+                                              : hipMemcpy(byte.ptr(), src.exc_byte, n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) return MOVI_OK;
+    if (on_upload_stream && ix->pipe_up) (void)hipStreamSynchronize(ix->pipe_up);
+    return fail_hip(e, "uploading the exception list");
+}
+
+// One kind of query behind a *_host entry point, over the call's planned chunks (movi_host_plan.hpp):
+//   launch(ctx, chunk, d_bases, d_offs, d_err)   allocates the chunk's result staging from ctx and enqueues the kernel;
+//   fetch(ctx, chunk)                            enqueues the results' way back (ctx.down / ctx.down_small);
+//   harvest(h_small, chunk, group, delivered)    overlapped path only, after the chunk's stream has drained: per-read
+//                                                results from the page-locked block to the caller's arrays.
+template <typename Launch, typename Fetch>
+int run_chunked(movi_index *ix, const ReadSource &src, const uint64_t *h_offsets, const std::vector<HostChunk> &chunks,
+                uint8_t *h_read_err, movi_query_stats_t *stats, Launch launch, Fetch fetch) {
+    memset(stats, 0, sizeof(*stats));
+    if (int rc = upload_exceptions(ix, src, false)) return rc;
     int seg_verdict = -1;
     ChunkCtx ctx;
     ctx.ix = ix;
@@ -1703,77 +1698,50 @@ int run_chunked(movi_index *ix, const ReadSource &src, const uint64_t *h_offsets
     ctx.d_stats = ix->d_stats.get();
     ctx.d = ix->scratch;
     ctx.seg_ws = &ix->seg_ws;
-    uint64_t first = 0;
-    while (first < n_reads) {
-        uint64_t last = first + 1;
-        while (last < n_reads) {
-            const uint64_t nb_next = h_offsets[last + 1] - h_offsets[first];
-            if (nb_next <= kChunkBases || (last - first < kMinChunkReads && nb_next <= kMaxChunkBases)) ++last;
-            else break;
-        }
-        const uint64_t nr = last - first;
-        const uint64_t b0 = h_offsets[first], nb = h_offsets[last] - b0;
+    for (const HostChunk &c : chunks) {
         uint8_t *d_bases = nullptr, *d_err = nullptr;
         uint64_t *d_offs = nullptr;
         static const bool trace = getenv("MOVI_TRACE_HOST_CALLS") != nullptr;   // diagnostic: where a synchronous host call's time goes, to stderr
         double tr[8] = {0};
         auto stamp = [&](int k) { if (trace) tr[k] = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         stamp(0);
-        HIP_TRY(ctx.alloc(movi_index::kBases, nb, &d_bases));
-        HIP_TRY(ctx.alloc(movi_index::kOffs, (nr + 1) * 8, &d_offs));
-        HIP_TRY(ctx.alloc(movi_index::kErr, nr, &d_err));
-        HIP_TRY(grow_entries(ix->h_rel, (size_t)(nr + 1)));
+        HIP_TRY(ctx.alloc(movi_index::kBases, c.nb, &d_bases));
+        HIP_TRY(ctx.alloc(movi_index::kOffs, (c.nr + 1) * 8, &d_offs));
+        HIP_TRY(ctx.alloc(movi_index::kErr, c.nr, &d_err));
+        HIP_TRY(grow_entries(ix->h_rel, (size_t)(c.nr + 1)));
         uint64_t *rel = ix->h_rel.as<uint64_t>();             // (read by the copy below before the call returns: hipMemcpy is synchronous)
-        uint64_t longest = 0;
-        for (uint64_t i = 0; i <= nr; i++) {
-            rel[i] = h_offsets[first + i] - b0;
-            if (i && rel[i] - rel[i - 1] > longest) longest = rel[i] - rel[i - 1];
-        }
-        ctx.ragged_hint = (nr && longest * 2 > (nb / nr) * 3) ? 1 : 0;
+        ctx.ragged_hint = fill_relative_offsets(rel, h_offsets, c);
         // No length sort here: on ragged batches handing the lanes out longest-first measured
         // slightly SLOWER (31.1 vs 32.8 Gbases/s, log-normal lengths) -- the walk is bound by the
         // memory system, not by lane occupancy, and the dispatcher already refills whole blocks.
         stamp(1);
-        if (nb && !src.two_bit) HIP_TRY(hipMemcpy(d_bases, src.ascii + b0, nb, hipMemcpyHostToDevice));
-        if (nb && src.two_bit) {                              // a quarter of the bytes go up; the null stream unpacks them ahead of the walk
+        if (c.nb && !src.two_bit) HIP_TRY(hipMemcpy(d_bases, src.ascii + c.b0, c.nb, hipMemcpyHostToDevice));
+        if (c.nb && src.two_bit) {                            // a quarter of the bytes go up; the null stream unpacks them ahead of the walk
             void *d_packed = nullptr;
-            HIP_TRY(ctx.alloc(movi_index::kPacked, src.up_bytes(b0, nb), &d_packed));
-            HIP_TRY(hipMemcpy(d_packed, src.up_from(b0), src.up_bytes(b0, nb), hipMemcpyHostToDevice));
-            HIP_TRY(unpack_chunk(src, ix->scratch[movi_index::kExcPos].ptr(), ix->scratch[movi_index::kExcByte].ptr(), d_packed, b0, nb, d_bases, nullptr));
+            HIP_TRY(ctx.alloc(movi_index::kPacked, src.up_bytes(c.b0, c.nb), &d_packed));
+            HIP_TRY(hipMemcpy(d_packed, src.up_from(c.b0), src.up_bytes(c.b0, c.nb), hipMemcpyHostToDevice));
+            HIP_TRY(unpack_chunk(src, ix->scratch[movi_index::kExcPos].ptr(), ix->scratch[movi_index::kExcByte].ptr(), d_packed, c.b0, c.nb, d_bases, nullptr));
         }
         stamp(2);
-        HIP_TRY(hipMemcpy(d_offs, rel, (nr + 1) * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_offs, rel, (c.nr + 1) * 8, hipMemcpyHostToDevice));
         stamp(3);
-        ctx.first = first;
-        ctx.b0 = b0;
-        int rc = launch(ctx, d_bases, d_offs, nr, nb, d_err);
+        int rc = launch(ctx, c, d_bases, d_offs, d_err);
         if (rc) return rc;
         stamp(4);
         movi_query_stats_t st{};
         rc = movi_last_stats(ix, nullptr, &st);
         if (rc) return rc;
         stamp(5);
-        rc = fetch(ctx, first, nr, b0, nb);
+        rc = fetch(ctx, c);
         if (rc) return rc;
         stamp(6);
-        if (h_read_err) HIP_TRY(hipMemcpy(h_read_err + first, d_err, nr, hipMemcpyDeviceToHost));
+        if (h_read_err) HIP_TRY(hipMemcpy(h_read_err + c.first, d_err, c.nr, hipMemcpyDeviceToHost));
         stamp(7);
         if (trace)
             fprintf(stderr, "[movi_hip] host call: %llu reads %llu bases | staging + offsets %.3f | bases up %.3f | offsets up %.3f | launch %.3f | walk + counters %.3f | "
-                            "results down %.3f | error bytes down %.3f ms\n", (unsigned long long)nr, (unsigned long long)nb, (tr[1] - tr[0]) * 1e3, (tr[2] - tr[1]) * 1e3,
+                            "results down %.3f | error bytes down %.3f ms\n", (unsigned long long)c.nr, (unsigned long long)c.nb, (tr[1] - tr[0]) * 1e3, (tr[2] - tr[1]) * 1e3,
                     (tr[3] - tr[2]) * 1e3, (tr[4] - tr[3]) * 1e3, (tr[5] - tr[4]) * 1e3, (tr[6] - tr[5]) * 1e3, (tr[7] - tr[6]) * 1e3);
-        if (stats) {
-            stats->bases += nb;
-            stats->fast_forwards += st.fast_forwards;
-            stats->scans += st.scans;
-            stats->repositions += st.repositions;
-            stats->errors += st.errors;
-            stats->lane_steps += st.lane_steps;
-            stats->wave_steps += st.wave_steps;
-            stats->segments += st.segments;
-            stats->rewalked += st.rewalked;
-        }
-        first = last;
+        add_stats(stats, c.nb, st);
     }
     return MOVI_OK;
 }
@@ -1784,9 +1752,6 @@ int run_chunked(movi_index *ix, const ReadSource &src, const uint64_t *h_offsets
 // the device and come down behind those of the chunks before it.
 //   device(d_bases, d_offs, nr, nb, d_out, d_n, d_err)   enqueues the query on the null stream: read i's results from d_out + elem_bytes *
 //                                                        d_offs[i], their number in d_n[i], a second u32 per read in d_n[nr + i] if `second`.
-constexpr uint64_t kCompactChunkBases = 1ull << 25;
-constexpr uint64_t kCompactChunkReads = 1ull << 18;
-constexpr uint64_t kCompactMaxChunkBases = 1ull << 27;
 struct CompactOut {
     size_t elem_bytes;         // of one result
     void *h_out;               // the caller's array of `cap` results; *n_total = the number found (set even when they do not fit)
@@ -1803,18 +1768,17 @@ int run_compact(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offset
     if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
     HIP_TRY(hipSetDevice(ix->device));
     DevBuf *d = ix->scratch;
+    HostFacts facts;
+    facts.query = HostQuery::kCompact;
+    facts.total = h_offsets[n_reads] - h_offsets[0];
+    facts.n_reads = n_reads;
+    HostCall call = plan_host_call(facts, HostOptions());
+    call.settle(false);
     std::vector<uint64_t> rel;
     uint64_t total = 0, errors = 0;
     bool overflow = false;
-    uint64_t first = 0;
-    while (first < n_reads) {
-        uint64_t last = first + 1;
-        while (last < n_reads) {
-            const uint64_t nb_next = h_offsets[last + 1] - h_offsets[first];
-            if (nb_next <= kCompactChunkBases || (last - first < kCompactChunkReads && nb_next <= kCompactMaxChunkBases)) ++last;
-            else break;
-        }
-        const uint64_t nr = last - first, b0 = h_offsets[first], nb = h_offsets[last] - b0;
+    for (const HostChunk &c : plan_chunks(call, h_offsets, n_reads)) {
+        const uint64_t first = c.first, nr = c.nr, nb = c.nb;
         HIP_TRY(grow(d[movi_index::kBases], nb));
         HIP_TRY(grow(d[movi_index::kOffs], (nr + 1) * 8));
         HIP_TRY(grow(d[movi_index::kErr], nr));
@@ -1822,8 +1786,8 @@ int run_compact(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offset
         HIP_TRY(grow(d[movi_index::kA], nr * (o.second ? 8 : 4)));
         HIP_TRY(grow(d[movi_index::kB], (nr + 1) * 8));
         rel.resize(nr + 1);
-        for (uint64_t i = 0; i <= nr; i++) rel[i] = h_offsets[first + i] - b0;
-        if (nb) HIP_TRY(hipMemcpy(d[movi_index::kBases].ptr(), h_bases + b0, nb, hipMemcpyHostToDevice));
+        (void)fill_relative_offsets(rel.data(), h_offsets, c);
+        if (nb) HIP_TRY(hipMemcpy(d[movi_index::kBases].ptr(), h_bases + c.b0, nb, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(d[movi_index::kOffs].ptr(), rel.data(), (nr + 1) * 8, hipMemcpyHostToDevice));
         const uint64_t *d_offs = d[movi_index::kOffs].as<uint64_t>();
         uint32_t *d_n = d[movi_index::kA].as<uint32_t>();
@@ -1849,7 +1813,6 @@ int run_compact(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offset
         total += found;
         errors += h.errors;
         if (stats) add_stats(stats, nb, h);
-        first = last;
     }
     if (o.n_total) *o.n_total = total;
     if (overflow) return fail(MOVI_ERR_ARG, std::to_string(total) + o.what + std::to_string(o.cap));
@@ -1867,50 +1830,17 @@ int run_compact(movi_index *ix, const uint8_t *h_bases, const uint64_t *h_offset
 // after it -- the next chunk's upload included.  Enqueued that way (the first version) the timeline was strictly serial,
 // chunk after chunk (rocprofv3 --memory-copy-trace), and the call no faster than the synchronous one.
 template <typename Launch, typename Fetch, typename Harvest>
-int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offsets, uint64_t n_reads,
-                  uint8_t *h_read_err, movi_query_stats_t *stats, Launch launch, Fetch fetch, Harvest harvest,
-                  size_t small_bytes, size_t mask_word_bytes, bool vector_down) {
-    if (stats) memset(stats, 0, sizeof(*stats));
+int run_pipelined(movi_index *ix, const HostCall &call, const ReadSource &src, const uint64_t *h_offsets, const std::vector<HostChunk> &chunks,
+                  uint8_t *h_read_err, movi_query_stats_t *stats, Launch launch, Fetch fetch, Harvest harvest) {
+    memset(stats, 0, sizeof(*stats));
     movi_query_stats_t acc{};
-    const uint64_t total = h_offsets[n_reads] - h_offsets[0];
-    // (calls whose results -- all or part of them -- come down as reset masks for the host's worker pool are cut twice as fine: the pool's
-    // work arrives earlier and more evenly; 1 M x 150 bp: masks alone 22.9 -> 32.4 Gbases/s, both ways down 30 -> 33.9; finer still and
-    // the walks no longer fill the GPU: profiles/r06_host_path.txt)
-    uint64_t target = total / (mask_word_bytes ? kPipeMaskChunks : kPipeTargetChunks);
-    target = target < kPipeMinBases ? kPipeMinBases : (target > kChunkBases ? kChunkBases : target);
-    uint64_t min_reads = kPipeMinReads;
-    // Long reads are cut into few, big chunks because a read takes its time however few lanes walk beside it -- unless the
-    // reads are walked segment-parallel, which the host only knows afterwards: a caller whose last call was (a stream of
-    // batches of the same kind of reads) gets chunks of >= 2^12 reads from then on, whose downloads start earlier.
-    if (ix->seg_seen && ix->cfg.seg_len > 0 && total / n_reads >= 2ull * (uint64_t)ix->cfg.seg_len) min_reads = 1ull << 12;
-    if (ix->pipe_chunk_bases) { target = ix->pipe_chunk_bases; min_reads = 1; }
-    struct Chunk { uint64_t first, nr, b0, nb; };
-    std::vector<Chunk> chunks;
-    for (uint64_t first = 0; first < n_reads;) {
-        // the longest run of reads from `first` with at most `target` bases (the offsets are non-decreasing: checked) --
-        // at least one read, at least min_reads of them if that stays below kMaxChunkBases
-        const uint64_t *lo = h_offsets + first + 1, *end = h_offsets + n_reads + 1;
-        // (the first download can only start when the first walk is over: the first two chunks are a quarter and
-        // half the size)
-        uint64_t tgt = target;
-        // (not where masks come down: a chunk's masks are 1/16 of its vector, and sixteen equal chunks ran 8 % faster than the same with a
-        // half-size second one)
-        if (!ix->pipe_chunk_bases && !mask_word_bytes && chunks.size() < 2 && (target >> (2 - chunks.size())) >= kPipeMinBases)
-            tgt = target >> (2 - chunks.size());
-        uint64_t last = (uint64_t)(std::upper_bound(lo, end, h_offsets[first] + tgt) - h_offsets) - 1;
-        if (last - first < min_reads) {
-            const uint64_t cap = (uint64_t)(std::upper_bound(lo, end, h_offsets[first] + kMaxChunkBases) - h_offsets) - 1;
-            last = std::min(first + min_reads, cap);
-        }
-        if (last <= first) last = first + 1;
-        if (last > n_reads) last = n_reads;
-        chunks.push_back({first, last - first, h_offsets[first], h_offsets[last] - h_offsets[first]});
-        first = last;
-    }
+    const uint64_t total = call.facts.total, n_reads = call.facts.n_reads;
+    const size_t small_bytes = call.small_bytes, mask_word_bytes = call.words_in_block ? 4 : 0;
     uint8_t *all = nullptr;                                    // the call's reads in one device buffer (set below, ahead of the loop), or chunk by chunk
     uint8_t *all_packed = nullptr;                             // packed calls: what went up ahead of the loop, from byte chunks[0].b0 >> 2 of the caller's buffer
     constexpr int S = movi_index::kPipeSlots;
-    struct InFlight { int stage = 0; Chunk c{}; } fl[S];       // 0 free, 1 walking (upload + kernel enqueued), 2 coming down
+    // a slot: 0 free, 1 walking (upload + kernel enqueued), 2 coming down; its chunk; whether fetch() already handed the chunk's results on
+    struct InFlight { int stage = 0; HostChunk c{}; bool delivered = false; } fl[S];
     HostPool::Group grp[S];                                    // host-side work a slot's harvest has handed to the worker pool (it reads the slot's page-locked block)
     // layout of a slot's page-locked block
     auto off_err = [](uint64_t nr) { return (size_t)(nr + 1) * 8; };
@@ -1931,8 +1861,6 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
         ctx.h_small = sl.h.as<uint8_t>() + off_small(nr);
         ctx.seg_ws = &sl.seg_ws;
         ctx.async = true;
-        ctx.first = fl[k].c.first;
-        ctx.b0 = fl[k].c.b0;
         ctx.grp = &grp[k];
         return ctx;
     };
@@ -1948,11 +1876,12 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
         memcpy(&h, blk + off_stats(f.c.nr, f.c.nb), sizeof(h));
         add_stats(&acc, f.c.nb, h);
         if (h_read_err) memcpy(h_read_err + f.c.first, blk + off_err(f.c.nr), f.c.nr);
-        harvest(blk + off_small(f.c.nr), f.c.first, f.c.nr, &grp[k]);
+        harvest(blk + off_small(f.c.nr), f.c, &grp[k], f.delivered);
         return MOVI_OK;
     };
-    // chunk c goes up into slot k and is walked
-    auto up = [&](const Chunk &c, int k, size_t ci) -> int {
+    // chunk ci goes up into slot k and is walked
+    auto up = [&](int k, size_t ci) -> int {
+        const HostChunk &c = chunks[ci];
         movi_index::PipeSlot &sl = ix->pipe[k];
         if (int rc = finish(k)) return rc;
         HostPool::get().wait(&grp[k]);                       // (the slot's block is about to be rewritten)
@@ -1962,7 +1891,6 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
         if (!ix->pipe_up) HIP_TRY(create_upload_stream(&ix->pipe_up));
         if (!sl.d_stats) HIP_TRY(dev_alloc(sl.d_stats, sizeof(DevStats)));
         HIP_TRY(grow_block(sl.h, off_stats(c.nr, c.nb) + sizeof(DevStats)));
-        fl[k].c = c;
         ChunkCtx ctx = ctx_of(k, c.nr);
         uint8_t *d_bases = nullptr, *d_err = nullptr, *d_packed = nullptr;
         uint64_t *d_offs = nullptr;
@@ -1973,13 +1901,9 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
         HIP_TRY(ctx.alloc(movi_index::kOffs, (c.nr + 1) * 8, &d_offs));
         HIP_TRY(ctx.alloc(movi_index::kErr, c.nr, &d_err));
         uint64_t *rel = sl.h.as<uint64_t>();
-        uint64_t longest = 0;
-        for (uint64_t i = 0; i <= c.nr; i++) {
-            rel[i] = h_offsets[c.first + i] - c.b0;
-            if (i && rel[i] - rel[i - 1] > longest) longest = rel[i] - rel[i - 1];
-        }
-        ctx.ragged_hint = (c.nr && longest * 2 > (c.nb / c.nr) * 3) ? 1 : 0;
+        ctx.ragged_hint = fill_relative_offsets(rel, h_offsets, c);
         fl[k].c = c;
+        fl[k].delivered = false;
         fl[k].stage = 1;                                     // from here on the streams hold work that touches caller memory
         // (the upload stream carries the bases alone, copy behind copy: with the chunk's offsets in between, every chunk left it idle for
         // ~40 us -- a fifth of a 9.4 MB copy; the offsets go up on the chunk's own stream, ahead of its walk: profiles/r06_host_path.txt)
@@ -1995,17 +1919,19 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
         // (packed calls: the chunk's own stream unpacks what has arrived into the place the ASCII copy lands in; the upload stream carries copies alone)
         if (src.two_bit)
             HIP_TRY(unpack_chunk(src, ix->scratch[movi_index::kExcPos].ptr(), ix->scratch[movi_index::kExcByte].ptr(), d_packed, c.b0, c.nb, d_bases, sl.s));
-        if (int rc = launch(ctx, d_bases, d_offs, c.nr, c.nb, d_err)) return rc;
+        if (int rc = launch(ctx, c, d_bases, d_offs, d_err)) return rc;
         HIP_TRY(hipEventRecord(sl.ev, sl.s));
         return MOVI_OK;
     };
     // slot k's walk is over: its results start their way down
     auto down = [&](int k) -> int {
         movi_index::PipeSlot &sl = ix->pipe[k];
-        const Chunk &c = fl[k].c;
+        const HostChunk &c = fl[k].c;
         HIP_TRY(hipEventSynchronize(sl.ev));
         ChunkCtx ctx = ctx_of(k, c.nr);
-        if (int rc = fetch(ctx, c.first, c.nr, c.b0, c.nb)) return rc;
+        const int rc = fetch(ctx, c);
+        fl[k].delivered = ctx.delivered;
+        if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(sl.h.as<uint8_t>() + off_err(c.nr), sl.d[movi_index::kErr].ptr(), c.nr, hipMemcpyDeviceToHost, sl.s));
         HIP_TRY(hipMemcpyAsync(sl.h.as<uint8_t>() + off_stats(c.nr, c.nb), sl.d_stats.get(), sizeof(DevStats), hipMemcpyDeviceToHost, sl.s));
         fl[k].stage = 2;
@@ -2029,23 +1955,12 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
     int rc = MOVI_OK;
     const size_t n = chunks.size();
     size_t next_up = 0;
+    if (int rce = upload_exceptions(ix, src, true)) return rce;   // ahead of every chunk's bytes on the upload stream
     // ALL THE READS GO UP AHEAD OF THE LOOP (calls of up to 2^31 bases, into the handle's call-wide staging): the copies queued behind one
     // another, an event behind each, and a chunk's walk waits for its event.  Enqueued chunk by chunk from the loop -- three ahead of the
     // walk being waited for -- the upload stream ran dry two or three times per call (0.1 ms each), and the upload is what bounds the
     // call.  (The chunks' offsets then must not travel by the copy engine: they would queue behind the whole call's reads.)
-    if (src.two_bit && src.n_exc) {                           // the call's exception list, once, ahead of every chunk's bytes on the upload stream
-        hipError_t e = hipSuccess;
-        if (!ix->pipe_up) e = create_upload_stream(&ix->pipe_up);
-        if (e == hipSuccess) e = grow(ix->scratch[movi_index::kExcPos], (size_t)src.n_exc * 8);
-        if (e == hipSuccess) e = grow(ix->scratch[movi_index::kExcByte], (size_t)src.n_exc);
-        if (e == hipSuccess) e = hipMemcpyAsync(ix->scratch[movi_index::kExcPos].ptr(), src.exc_pos, (size_t)src.n_exc * 8, hipMemcpyHostToDevice, ix->pipe_up);
-        if (e == hipSuccess) e = hipMemcpyAsync(ix->scratch[movi_index::kExcByte].ptr(), src.exc_byte, (size_t)src.n_exc, hipMemcpyHostToDevice, ix->pipe_up);
-        if (e != hipSuccess) {
-            if (ix->pipe_up) (void)hipStreamSynchronize(ix->pipe_up);
-            return fail_hip(e, "uploading the exception list");
-        }
-    }
-    if (n > 1 && total <= (1ull << 31) && !vector_down) {
+    if (call.upload_ahead(n)) {
         hipError_t e = hipSuccess;
         if (!ix->pipe_up) e = create_upload_stream(&ix->pipe_up);
         if (e == hipSuccess) e = grow(ix->scratch[movi_index::kBases], total);
@@ -2059,7 +1974,7 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
             all = ix->scratch[movi_index::kBases].as<uint8_t>();
             if (src.two_bit) all_packed = ix->scratch[movi_index::kPacked].as<uint8_t>();
             for (size_t i = 0; i < n && e == hipSuccess; i++) {
-                const Chunk &c = chunks[i];
+                const HostChunk &c = chunks[i];
                 // (packed: the bytes that cover the chunk; a byte that two chunks share goes up with both, to the same place)
                 if (c.nb) e = hipMemcpyAsync(src.two_bit ? all_packed + ((c.b0 >> 2) - (chunks[0].b0 >> 2)) : all + (c.b0 - chunks[0].b0), src.up_from(c.b0),
                                              src.up_bytes(c.b0, c.nb), hipMemcpyHostToDevice, ix->pipe_up);
@@ -2070,11 +1985,11 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
                 return fail_hip(e, "uploading the reads");
             }
         } else {
-            (void)hipGetLastError();                          // no room for the call-wide staging: chunk by chunk, as before
+            (void)hipGetLastError();                          // no room for the call-wide staging: chunk by chunk (the plan's fall-back)
         }
     }
     for (size_t i = 0; i < n && rc == MOVI_OK; i++) {
-        for (; next_up < n && next_up < i + (size_t)movi_index::kPipeAhead && rc == MOVI_OK; next_up++) rc = up(chunks[next_up], (int)(next_up % S), next_up);
+        for (; next_up < n && next_up < i + (size_t)movi_index::kPipeAhead && rc == MOVI_OK; next_up++) rc = up((int)(next_up % S), next_up);
         if (rc == MOVI_OK) rc = down((int)(i % S));
         if (rc == MOVI_OK) rc = finish_arrived();
     }
@@ -2089,28 +2004,27 @@ int run_pipelined(movi_index *ix, const ReadSource &src, const uint64_t *h_offse
     }
     // (after the streams have drained: a stream's host function may hand work to the pool; also on errors: the workers write caller memory)
     for (int k = 0; k < S; k++) HostPool::get().wait(&grp[k]);
-    if (stats) *stats = acc;
+    *stats = acc;
     if (rc == MOVI_OK && total / n_reads >= 2ull * (uint64_t)(ix->cfg.seg_len > 0 ? ix->cfg.seg_len : 1)) ix->seg_seen = acc.segments != 0;
     return rc;
 }
 
-// Queries with per-read results (count, bins) only have their upload to hide.  A read takes as long as it takes: with
-// long reads the last chunk's walk starts when the last byte has arrived and lasts as long as the whole batch's would
-// (100 k x 10 kbp, bins: 43 ms overlapped, 38 ms synchronous); with short reads the walks are short against the
-// transfers and overlapping pays (1 M x 150 bp: count 20.6 -> 25.1, bins 21.8 -> 28.8 Gbases/s).
-bool worth_overlapping_small_results(const uint64_t *h_offsets, uint64_t n_reads) {
-    const uint64_t total = h_offsets[n_reads] - h_offsets[0];
-    return total != 0 && total / n_reads <= 2048;
+// The handle's options as the plan reads them.
+HostOptions host_options(const movi_index *ix) {
+    HostOptions o;
+    o.host_overlap = ix->host_overlap; o.host_autopin = ix->host_autopin; o.host_masks = ix->host_masks; o.host_mask_share = ix->host_mask_share;
+    o.pipe_chunk_bases = ix->pipe_chunk_bases; o.seg_seen = ix->seg_seen; o.seg_len = ix->cfg.seg_len;
+    return o;
 }
 
+// A settled call (movi_host_plan.hpp) through the loop it chose, over the chunks planned for it.
 template <typename Launch, typename Fetch, typename Harvest>
-int run_host(bool overlapped, movi_index *ix, const ReadSource &src, const uint64_t *h_offsets, uint64_t n_reads,
-             uint8_t *h_read_err, movi_query_stats_t *stats, Launch launch, Fetch fetch, Harvest harvest,
-             size_t small_bytes, size_t mask_word_bytes = 0, bool vector_down = false) {
+int run_host(movi_index *ix, const HostCall &call, const ReadSource &src, const uint64_t *h_offsets, uint8_t *h_read_err,
+             movi_query_stats_t *stats, Launch launch, Fetch fetch, Harvest harvest) {
     movi_query_stats_t local{};
-    overlapped = overlapped && ix->host_overlap;
-    int rc = overlapped ? run_pipelined(ix, src, h_offsets, n_reads, h_read_err, &local, launch, fetch, harvest, small_bytes, mask_word_bytes, vector_down)
-                        : run_chunked(ix, src, h_offsets, n_reads, h_read_err, &local, launch, fetch, harvest, small_bytes, mask_word_bytes);
+    const std::vector<HostChunk> chunks = plan_chunks(call, h_offsets, call.facts.n_reads);
+    int rc = call.overlapped ? run_pipelined(ix, call, src, h_offsets, chunks, h_read_err, &local, launch, fetch, harvest)
+                             : run_chunked(ix, src, h_offsets, chunks, h_read_err, &local, launch, fetch);
     if (stats) *stats = local;
     if (rc) return rc;
     if (local.errors)
@@ -2192,9 +2106,42 @@ struct AutoPin {
         g_err = keep;
     }
 };
-static bool autopin_worthwhile(const movi_index *ix, const uint64_t *h_offsets, uint64_t n_reads) {
-    // (the overlapped path cuts a call into pieces of >= 2^15 reads: it needs at least three of them to overlap anything)
-    return ix->host_autopin && ix->host_overlap && h_offsets[n_reads] - h_offsets[0] >= (1ull << 27) && n_reads >= 3 * kPipeMinReads;
+
+// A caller's buffer and the part of it one call touches.
+struct HostSpan {
+    const void *buf = nullptr, *from = nullptr;
+    size_t bytes = 0;
+};
+// A *_host call's plan in its two steps (movi_host_plan.hpp), with the acts between them: the runtime is asked which buffers are
+// page-locked -- only where the answer matters -- and page-locks for the call (`pins`, released by the entry point's scope) what
+// the plan finds worth trying.
+static HostCall plan_call(const movi_index *ix, HostFacts f, const HostSpan &reads, const HostSpan &vector, AutoPin (&pins)[2]) {
+    const HostOptions o = host_options(ix);
+    f.reads_pinned = overlap_possible(f) && is_pinned(reads.buf);
+    f.vector_pinned = f.reads_pinned && needs_pinned_vector(f, o) && is_pinned(vector.buf);
+    HostCall call = plan_host_call(f, o);
+    call.settle(call.pin_reads && pins[0].pin(const_cast<void *>(reads.from), reads.bytes) &&
+                (!call.pin_vector || pins[1].pin(const_cast<void *>(vector.from), vector.bytes)));
+    return call;
+}
+// every query but PML / ZML: only the reads matter; `small_bytes` of per-read results are page-locked per read of a chunk in flight
+static HostCall plan_reads_call(const movi_index *ix, HostQuery query, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads,
+                                   size_t small_bytes, bool want_vector, AutoPin (&pins)[2]) {
+    HostFacts f;
+    f.query = query;
+    f.total = h_offsets[n_reads] - h_offsets[0];
+    f.n_reads = n_reads;
+    f.want_vector = want_vector;
+    f.small_bytes = small_bytes;
+    return plan_call(ix, f, HostSpan{h_bases, h_bases ? h_bases + h_offsets[0] : nullptr, (size_t)f.total}, HostSpan{}, pins);
+}
+
+// What the host's worker threads expand: a chunk's reset-mask words into its part of the caller's vector (`out` is the whole call's).
+static ExpandJob expand_job(const uint32_t *words, const uint64_t *h_offsets, const HostChunk &c, uint16_t *out) {
+    ExpandJob j;
+    j.words = words; j.offs = h_offsets; j.o0 = c.b0; j.phase = c.phase; j.ibase = c.first; j.i0 = c.first; j.i1 = c.first + c.nr;
+    j.out = out;
+    return j;
 }
 
 // h_mask_words != NULL: the reset masks themselves are the result (movi_pml_mask_host).  Otherwise, PML with "host_masks": the
@@ -2232,117 +2179,77 @@ static int ml_host(bool zml, movi_index_t *ix, const ReadSource &src, const uint
     }
     HIP_TRY(hipSetDevice(ix->device));
     const uint64_t o0 = h_offsets[0], span = h_offsets[n_reads] - o0;
-    // The way down of the u16 vector, chunk by chunk: as it is (2 bytes per base over PCIe, no host work where the caller's vector is
-    // page-locked) or as reset masks (1/8 byte per base) that the host's worker threads expand into the caller's vector -- the DMA engine
-    // and the host's cores are two resources.  "host_masks": -1 = masks for calls of >= 2^22 bases (no page-locking of the vector; with the
-    // words handed to the pool by a host function on the chunk's stream and sixteen chunks per call this way alone runs at 33 - 34 Gbases/s
-    // on 1 M x 150 bp, the vector's at 22.7, the 1 B / base upload's floor is 36.7), 0 = never masks, 1 = masks for every call, 2 = both
-    // ways side by side, `host_mask_share` percent of the bases as masks (31 - 34: no better than masks alone since the host function;
-    // profiles/r06_host_path.txt).
-    enum { kVector = 0, kMasks = 1, kMixed = 2 };
-    int route = kVector;
-    if (h_mask_words) route = kMasks;
-    else if (!zml && h_out_pml) {
-        if (ix->host_masks > 0) route = ix->host_masks >= 2 ? kMixed : kMasks;
-        else if (ix->host_masks < 0 && span >= (1ull << 22)) route = kMasks;
-    }
-    // A chunk's way down: `masks` = reset masks + host expansion, else the vector by DMA; a mixed call deals its chunks by `host_mask_share`.
-    // (Tried: walks that leave both on the device and a choice at download time by the pool's backlog -- 28.1 against 29.9 Gbases/s for
-    // the plain deal; a call's tail cut into halving chunks -- 27.3 against 28.1: profiles/r06_host_path.txt.)
-    struct Way { bool masks = false, delivered = false; uint32_t phase = 0; };
-    uint64_t acc_all = 0, acc_mask = 0;                       // bases launched so far / of them by the mask route
-    std::unordered_map<uint64_t, Way> way_of;                 // first read of a chunk -> its way (launch, fetch and harvest run on the calling thread)
+    // The call's way down (the u16 vector as it is, as reset masks that the host expands, or both side by side), whether it overlaps and
+    // every chunk's own way: movi_host_plan.hpp
+    HostFacts facts;
+    facts.zml = zml;
+    facts.total = span;
+    facts.n_reads = n_reads;
+    facts.want_vector = h_out_pml != nullptr;
+    facts.want_words = h_mask_words != nullptr;
+    AutoPin pins[2];
+    const HostCall call = plan_call(ix, facts, HostSpan{src.two_bit ? src.packed : src.ascii, src.up_from(o0), src.up_bytes(o0, span)},
+                                    HostSpan{h_out_pml, h_out_pml ? h_out_pml + o0 : nullptr, (size_t)span * 2}, pins);
     const int threads = ix->host_threads > 0 ? ix->host_threads : host_threads_default();
-    auto phase_of = [&](uint64_t b0) { return (uint32_t)((b0 - o0) & 31u); };
-    auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
-        Way w;
-        w.phase = phase_of(c.b0);
-        if (route == kMasks) w.masks = true;
-        else if (route == kMixed) {                           // (the first chunk comes down as it is: its DMA starts when its walk ends)
-            w.masks = (acc_mask + nb) * 100 <= (uint64_t)ix->host_mask_share * (acc_all + nb);
-            acc_all += nb;
-            if (w.masks) acc_mask += nb;
-        }
-        way_of[c.first] = w;
-        MlRequest r = c.request(db, dof, nr, nb, derr);
-        if (w.masks) {
-            r.mask.phase = w.phase;
-            HIP_TRY(c.alloc(movi_index::kMask, (size_t)pml_mask_words(nr, nb, w.phase) * 4, &r.mask.words));
+    auto launch = [&](ChunkCtx &c, const HostChunk &k, const uint8_t *db, const uint64_t *dof, uint8_t *derr) -> int {
+        MlRequest r = c.request(k, db, dof, derr);
+        if (k.masks) {
+            r.mask.phase = k.phase;
+            HIP_TRY(c.alloc(movi_index::kMask, (size_t)pml_mask_words(k.nr, k.nb, k.phase) * 4, &r.mask.words));
             return pml_call(ix, r);
         }
-        HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &r.out));
+        HIP_TRY(c.alloc(movi_index::kOut, k.nb * 2, &r.out));
         if (zml) return zml_call(ix, r);
         r.lend_masks = true;      // (the vector itself comes down: on the device it is written through reset masks where the plan says so)
         return pml_call(ix, r);
     };
+    // a chunk's mask words in the layout of movi_pml_mask_words: how many, and where they belong in the caller's array
+    auto n_words = [](const HostChunk &k) { return (size_t)(((k.nb + k.phase) >> 5) + k.nr); };
+    auto words_dst = [&](const HostChunk &k) { return h_mask_words + ((k.b0 - o0) >> 5) + k.first; };
     // what a chunk's masks are to the host: the words land in `words`; they are the result, or the vector is expanded from them
-    auto deliver = [&](const uint32_t *words, uint64_t first, uint64_t nr, uint32_t ph, HostPool::Group *g) {
-        const uint64_t b0 = h_offsets[first], nb = h_offsets[first + nr] - b0;
-        if (h_mask_words) memcpy(h_mask_words + ((b0 - o0) >> 5) + first, words, (size_t)(((nb + ph) >> 5) + nr) * 4);
-        if (h_out_pml) {
-            ExpandJob j;
-            j.words = words; j.offs = h_offsets; j.o0 = b0; j.phase = ph; j.ibase = first; j.i0 = first; j.i1 = first + nr;
-            j.out = h_out_pml;
-            expand_parallel(j, threads, g);
-        }
+    auto deliver = [&](const uint32_t *words, const HostChunk &k, HostPool::Group *g) {
+        if (h_mask_words) memcpy(words_dst(k), words, n_words(k) * 4);
+        if (h_out_pml) expand_parallel(expand_job(words, h_offsets, k, h_out_pml), threads, g);
     };
     // (the results are found through the chunk's own staging: with chunks in flight, launch() of the next chunk has
     // run before fetch() of this one)
     std::vector<uint32_t> sync_words;                        // synchronous path: a chunk's words on their way through the host
-    auto fetch = [&](ChunkCtx &c, uint64_t first, uint64_t nr, uint64_t b0, uint64_t nb) -> int {
-        const Way w = way_of[first];
-        if (w.masks) {
-            const size_t nw = (size_t)(((nb + w.phase) >> 5) + nr);
+    auto fetch = [&](ChunkCtx &c, const HostChunk &k) -> int {
+        if (k.masks) {
+            const size_t nw = n_words(k);
             if (c.async) {
                 // into the slot's page-locked block, and on to the worker pool by a host function on the chunk's stream -- the moment the
                 // words have arrived, not when the calling thread's loop next comes by (with 8 chunks per call the pool ran at 2/3 duty)
                 HIP_TRY(c.down_small(nullptr, 0, c.d[movi_index::kMask].ptr(), nw * 4));
                 DeliverArg *a = new DeliverArg;
                 a->words = reinterpret_cast<const uint32_t *>(c.h_small);
-                a->mask_dst = h_mask_words ? h_mask_words + ((b0 - o0) >> 5) + first : nullptr;
+                a->mask_dst = h_mask_words ? words_dst(k) : nullptr;
                 a->mask_bytes = nw * 4;
                 a->expand = h_out_pml != nullptr;
-                a->job.words = a->words; a->job.offs = h_offsets; a->job.o0 = b0; a->job.phase = w.phase; a->job.ibase = first;
-                a->job.i0 = first; a->job.i1 = first + nr; a->job.out = h_out_pml;
+                a->job = expand_job(a->words, h_offsets, k, h_out_pml);
                 a->threads = threads;
                 a->group = c.grp;
                 const hipError_t eh = hipLaunchHostFunc(c.s, deliver_on_stream, a);
                 if (eh != hipSuccess) { delete a; (void)hipGetLastError(); return MOVI_OK; }   // harvest() does it instead
-                way_of[first].delivered = true;
+                c.delivered = true;
                 return MOVI_OK;
             }
             if (h_mask_words && !h_out_pml) {                 // straight to where they belong
-                HIP_TRY(hipMemcpy(h_mask_words + ((b0 - o0) >> 5) + first, c.d[movi_index::kMask].ptr(), nw * 4, hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(words_dst(k), c.d[movi_index::kMask].ptr(), nw * 4, hipMemcpyDeviceToHost));
                 return MOVI_OK;
             }
             sync_words.resize(nw);
             HIP_TRY(hipMemcpy(sync_words.data(), c.d[movi_index::kMask].ptr(), nw * 4, hipMemcpyDeviceToHost));
-            deliver(sync_words.data(), first, nr, w.phase, nullptr);
+            deliver(sync_words.data(), k, nullptr);
             return MOVI_OK;
         }
-        if (h_out_pml) HIP_TRY(c.down(h_out_pml + b0, c.d[movi_index::kOut].ptr(), nb * 2));
+        if (h_out_pml) HIP_TRY(c.down(h_out_pml + k.b0, c.d[movi_index::kOut].ptr(), k.nb * 2));
         return MOVI_OK;
     };
-    auto harvest = [&](const uint8_t *h_small, uint64_t first, uint64_t nr, HostPool::Group *g) {
-        const Way w = way_of[first];
-        if (!w.masks || w.delivered) return;
-        deliver(reinterpret_cast<const uint32_t *>(h_small), first, nr, w.phase, g);
+    auto harvest = [&](const uint8_t *h_small, const HostChunk &k, HostPool::Group *g, bool delivered) {
+        if (k.masks && !delivered) deliver(reinterpret_cast<const uint32_t *>(h_small), k, g);
     };
-    // masks: only the reads have to be page-locked for the overlapped path (the vector is written by host threads)
-    bool overlapped = span != 0 && is_pinned(src.two_bit ? src.packed : src.ascii) && (route == kMasks || !h_out_pml || is_pinned(h_out_pml));
-    // A big call on PAGEABLE buffers (what a std::vector-holding caller passes: INTEGRATION.md's stub): page-lock them for the
-    // duration of the call and take the overlapped path.  Registering touched memory runs at hundreds of GB/s (DESIGN.md section
-    // 5), so on >= 2^27 bases it is paid back several times over (the synchronous path: 12.4 Gbases/s PCIe-inclusive).
-    // "host_autopin" 0 turns it off; anything that fails here falls back to the synchronous path.
-    AutoPin pin_bases, pin_out;
-    if (!overlapped && autopin_worthwhile(ix, h_offsets, n_reads))
-        overlapped = pin_bases.pin(const_cast<uint8_t *>(src.up_from(o0)), src.up_bytes(o0, span)) &&
-                     (route == kMasks || !h_out_pml || pin_out.pin(h_out_pml + h_offsets[0], span * 2));
-    if (route == kMixed && !overlapped) route = kMasks;       // (the synchronous path: one way down for the whole call)
-    // (vector_down: 2 bytes per base come down by DMA -- the way down bounds such a call, and with every read going up at once beside
-    // it the downloads ran 8 % slower: those calls feed their uploads from the loop)
-    return run_host(overlapped, ix, src, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest, 0, route != kVector ? 4 : 0,
-                    route != kMasks && h_out_pml != nullptr);
+    return run_host(ix, call, src, h_offsets, h_read_err, stats, launch, fetch, harvest);
 }
 
 // ------------------------------------------------------------- reads packed two bits per base (movi_pack_host.cpp, movi_walk_pack.hip)
@@ -2392,10 +2299,9 @@ int movi_pml_expand_host(const uint32_t *h_mask_words, const uint64_t *h_offsets
     if (n_reads == 0) return MOVI_OK;
     if (!h_mask_words || !h_offsets || (h_offsets[n_reads] != h_offsets[0] && !h_out_pml)) return fail(MOVI_ERR_ARG, "NULL host buffer");
     if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
-    ExpandJob j;
-    j.words = h_mask_words; j.offs = h_offsets; j.o0 = h_offsets[0]; j.phase = 0; j.ibase = 0; j.i0 = 0; j.i1 = n_reads;
-    j.out = h_out_pml;
-    expand_parallel(j, n_threads, nullptr);
+    HostChunk all;                                           // the whole call as one chunk
+    all.nr = n_reads; all.b0 = h_offsets[0]; all.nb = h_offsets[n_reads] - h_offsets[0];
+    expand_parallel(expand_job(h_mask_words, h_offsets, all, h_out_pml), n_threads, nullptr);
     return MOVI_OK;
 }
 
@@ -2416,27 +2322,29 @@ int movi_pml_logs_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t 
     if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
     HIP_TRY(hipSetDevice(ix->device));
     uint16_t *d_out = nullptr, *d_ff = nullptr, *d_sc = nullptr;
-    auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
-        HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_out));
-        HIP_TRY(c.alloc(movi_index::kA, nb * 2, &d_ff));
-        HIP_TRY(c.alloc(movi_index::kS, nb * 2, &d_sc));
-        HIP_TRY(hipMemsetAsync(d_ff, 0, nb * 2, c.s));                 // a read of one base has no LF: its entry stays 0
-        HIP_TRY(hipMemsetAsync(d_sc, 0, nb * 2, c.s));
+    auto launch = [&](ChunkCtx &c, const HostChunk &k, const uint8_t *db, const uint64_t *dof, uint8_t *derr) -> int {
+        HIP_TRY(c.alloc(movi_index::kOut, k.nb * 2, &d_out));
+        HIP_TRY(c.alloc(movi_index::kA, k.nb * 2, &d_ff));
+        HIP_TRY(c.alloc(movi_index::kS, k.nb * 2, &d_sc));
+        HIP_TRY(hipMemsetAsync(d_ff, 0, k.nb * 2, c.s));               // a read of one base has no LF: its entry stays 0
+        HIP_TRY(hipMemsetAsync(d_sc, 0, k.nb * 2, c.s));
         MlRequest r;                                                   // (the handle's segment workspace: logs never reach the segment plan)
-        r.bases = db; r.offs = dof; r.n_reads = nr; r.n_bases = nb; r.out = d_out; r.err = derr; r.stream = c.s;
+        r.bases = db; r.offs = dof; r.n_reads = k.nr; r.n_bases = k.nb; r.out = d_out; r.err = derr; r.stream = c.s;
         r.stats = c.d_stats;
         r.cls.log_ff = d_ff;
         r.cls.log_scan = d_sc;
         return pml_call(ix, r);
     };
-    auto fetch = [&](ChunkCtx &c, uint64_t, uint64_t, uint64_t b0, uint64_t nb) -> int {
-        HIP_TRY(c.down(h_out_pml + b0, c.d[movi_index::kOut].ptr(), nb * 2));
-        HIP_TRY(c.down(h_fastforwards + b0, c.d[movi_index::kA].ptr(), nb * 2));
-        HIP_TRY(c.down(h_scans + b0, c.d[movi_index::kS].ptr(), nb * 2));
+    auto fetch = [&](ChunkCtx &c, const HostChunk &k) -> int {
+        HIP_TRY(c.down(h_out_pml + k.b0, c.d[movi_index::kOut].ptr(), k.nb * 2));
+        HIP_TRY(c.down(h_fastforwards + k.b0, c.d[movi_index::kA].ptr(), k.nb * 2));
+        HIP_TRY(c.down(h_scans + k.b0, c.d[movi_index::kS].ptr(), k.nb * 2));
         return MOVI_OK;
     };
-    auto harvest = [](const uint8_t *, uint64_t, uint64_t, HostPool::Group *) {};
-    return run_host(false, ix, h_bases, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest, 0);
+    auto harvest = [](const uint8_t *, const HostChunk &, HostPool::Group *, bool) {};
+    AutoPin pins[2];
+    return run_host(ix, plan_reads_call(ix, HostQuery::kLogs, h_bases, h_offsets, n_reads, 0, true, pins), h_bases, h_offsets, h_read_err, stats,
+                    launch, fetch, harvest);
 }
 
 int movi_zml_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads,
@@ -2509,32 +2417,30 @@ int movi_pml_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uint6
     HIP_TRY(hipSetDevice(ix->device));
     uint32_t *d_a = nullptr, *d_b = nullptr;
     uint64_t *d_s = nullptr;
-    auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
-        HIP_TRY(c.alloc(movi_index::kA, nr * 4, &d_a));
-        HIP_TRY(c.alloc(movi_index::kB, nr * 4, &d_b));
-        HIP_TRY(c.alloc(movi_index::kS, nr * 8, &d_s));
+    auto launch = [&](ChunkCtx &c, const HostChunk &k, const uint8_t *db, const uint64_t *dof, uint8_t *derr) -> int {
+        HIP_TRY(c.alloc(movi_index::kA, k.nr * 4, &d_a));
+        HIP_TRY(c.alloc(movi_index::kB, k.nr * 4, &d_b));
+        HIP_TRY(c.alloc(movi_index::kS, k.nr * 8, &d_s));
         // bins reduced inside the PML kernel; no PML vector is written at all
         // (a chunk in flight of the overlapped host path brings its own segment workspace, length hint and the call's probe verdict:
         // without them every chunk fell back to the handle's workspace -- shared by chunks on different streams -- and probed again)
-        return pml_classify_device(ix, c.request(db, dof, nr, nb, derr), bin_width, max_value_thr, d_a, d_b, d_s);
+        return pml_classify_device(ix, c.request(k, db, dof, derr), bin_width, max_value_thr, d_a, d_b, d_s);
     };
     // page-locked block of a chunk in flight: sum_max[nr] | above[nr] | below[nr]
-    auto fetch = [&](ChunkCtx &c, uint64_t first, uint64_t nr, uint64_t, uint64_t) -> int {
-        HIP_TRY(c.down_small(h_sum_max + first, 0, c.d[movi_index::kS].ptr(), nr * 8));
-        HIP_TRY(c.down_small(h_bins_above + first, nr * 8, c.d[movi_index::kA].ptr(), nr * 4));
-        HIP_TRY(c.down_small(h_bins_below + first, nr * 12, c.d[movi_index::kB].ptr(), nr * 4));
+    auto fetch = [&](ChunkCtx &c, const HostChunk &k) -> int {
+        HIP_TRY(c.down_small(h_sum_max + k.first, 0, c.d[movi_index::kS].ptr(), k.nr * 8));
+        HIP_TRY(c.down_small(h_bins_above + k.first, k.nr * 8, c.d[movi_index::kA].ptr(), k.nr * 4));
+        HIP_TRY(c.down_small(h_bins_below + k.first, k.nr * 12, c.d[movi_index::kB].ptr(), k.nr * 4));
         return MOVI_OK;
     };
-    auto harvest = [&](const uint8_t *h, uint64_t first, uint64_t nr, HostPool::Group *) {
-        memcpy(h_sum_max + first, h, nr * 8);
-        memcpy(h_bins_above + first, h + nr * 8, nr * 4);
-        memcpy(h_bins_below + first, h + nr * 12, nr * 4);
+    auto harvest = [&](const uint8_t *h, const HostChunk &k, HostPool::Group *, bool) {
+        memcpy(h_sum_max + k.first, h, k.nr * 8);
+        memcpy(h_bins_above + k.first, h + k.nr * 8, k.nr * 4);
+        memcpy(h_bins_below + k.first, h + k.nr * 12, k.nr * 4);
     };
-    bool overlapped = worth_overlapping_small_results(h_offsets, n_reads) && is_pinned(h_bases);
-    AutoPin pin_bases;
-    if (!overlapped && worth_overlapping_small_results(h_offsets, n_reads) && autopin_worthwhile(ix, h_offsets, n_reads))
-        overlapped = pin_bases.pin(const_cast<uint8_t *>(h_bases) + h_offsets[0], h_offsets[n_reads] - h_offsets[0]);
-    return run_host(overlapped, ix, h_bases, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest, 16);
+    AutoPin pins[2];
+    return run_host(ix, plan_reads_call(ix, HostQuery::kPerRead, h_bases, h_offsets, n_reads, 16, false, pins), h_bases, h_offsets, h_read_err, stats,
+                    launch, fetch, harvest);
 }
 
 // -------------------------------------------------------------------------- count
@@ -2664,26 +2570,24 @@ int movi_count_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_
     if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
     HIP_TRY(hipSetDevice(ix->device));
     uint64_t *d_m = nullptr, *d_c = nullptr;
-    auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
-        HIP_TRY(c.alloc(movi_index::kA, nr * 8, &d_m));
-        HIP_TRY(c.alloc(movi_index::kS, nr * 8, &d_c));
-        return count_device(ix, db, dof, nr, nb, d_m, d_c, derr, nullptr, c.s, c.d_stats);
+    auto launch = [&](ChunkCtx &c, const HostChunk &k, const uint8_t *db, const uint64_t *dof, uint8_t *derr) -> int {
+        HIP_TRY(c.alloc(movi_index::kA, k.nr * 8, &d_m));
+        HIP_TRY(c.alloc(movi_index::kS, k.nr * 8, &d_c));
+        return count_device(ix, db, dof, k.nr, k.nb, d_m, d_c, derr, nullptr, c.s, c.d_stats);
     };
     // page-locked block of a chunk in flight: matched[nr] | count[nr]
-    auto fetch = [&](ChunkCtx &c, uint64_t first, uint64_t nr, uint64_t, uint64_t) -> int {
-        HIP_TRY(c.down_small(h_matched + first, 0, c.d[movi_index::kA].ptr(), nr * 8));
-        HIP_TRY(c.down_small(h_count + first, nr * 8, c.d[movi_index::kS].ptr(), nr * 8));
+    auto fetch = [&](ChunkCtx &c, const HostChunk &k) -> int {
+        HIP_TRY(c.down_small(h_matched + k.first, 0, c.d[movi_index::kA].ptr(), k.nr * 8));
+        HIP_TRY(c.down_small(h_count + k.first, k.nr * 8, c.d[movi_index::kS].ptr(), k.nr * 8));
         return MOVI_OK;
     };
-    auto harvest = [&](const uint8_t *h, uint64_t first, uint64_t nr, HostPool::Group *) {
-        memcpy(h_matched + first, h, nr * 8);
-        memcpy(h_count + first, h + nr * 8, nr * 8);
+    auto harvest = [&](const uint8_t *h, const HostChunk &k, HostPool::Group *, bool) {
+        memcpy(h_matched + k.first, h, k.nr * 8);
+        memcpy(h_count + k.first, h + k.nr * 8, k.nr * 8);
     };
-    bool overlapped = worth_overlapping_small_results(h_offsets, n_reads) && is_pinned(h_bases);
-    AutoPin pin_bases;
-    if (!overlapped && worth_overlapping_small_results(h_offsets, n_reads) && autopin_worthwhile(ix, h_offsets, n_reads))
-        overlapped = pin_bases.pin(const_cast<uint8_t *>(h_bases) + h_offsets[0], h_offsets[n_reads] - h_offsets[0]);
-    return run_host(overlapped, ix, h_bases, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest, 16);
+    AutoPin pins[2];
+    return run_host(ix, plan_reads_call(ix, HostQuery::kPerRead, h_bases, h_offsets, n_reads, 16, false, pins), h_bases, h_offsets, h_read_err, stats,
+                    launch, fetch, harvest);
 }
 
 // -------------------------------------------------------------------------- MEM
@@ -3018,19 +2922,20 @@ int movi_sa_entries_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_
     HIP_TRY(hipSetDevice(ix->device));
     uint16_t *d_pml = nullptr;
     uint64_t *d_sa = nullptr;
-    auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
-        if (h_out_pml) HIP_TRY(c.alloc(movi_index::kOut, nb * 2, &d_pml));
-        HIP_TRY(c.alloc(movi_index::kS, nb * 8, &d_sa));
-        return sa_entries_device(ix, db, dof, nr, nb, h_out_pml ? d_pml : nullptr, d_sa, derr, nullptr, c.s, c.d_stats);
+    auto launch = [&](ChunkCtx &c, const HostChunk &k, const uint8_t *db, const uint64_t *dof, uint8_t *derr) -> int {
+        if (h_out_pml) HIP_TRY(c.alloc(movi_index::kOut, k.nb * 2, &d_pml));
+        HIP_TRY(c.alloc(movi_index::kS, k.nb * 8, &d_sa));
+        return sa_entries_device(ix, db, dof, k.nr, k.nb, h_out_pml ? d_pml : nullptr, d_sa, derr, nullptr, c.s, c.d_stats);
     };
-    auto fetch = [&](ChunkCtx &c, uint64_t, uint64_t, uint64_t b0, uint64_t nb) -> int {
-        if (h_out_pml) HIP_TRY(c.down(h_out_pml + b0, d_pml, nb * 2));
-        HIP_TRY(c.down(h_out_sa + b0, d_sa, nb * 8));
+    auto fetch = [&](ChunkCtx &c, const HostChunk &k) -> int {
+        if (h_out_pml) HIP_TRY(c.down(h_out_pml + k.b0, d_pml, k.nb * 2));
+        HIP_TRY(c.down(h_out_sa + k.b0, d_sa, k.nb * 8));
         return MOVI_OK;
     };
-    auto harvest = [](const uint8_t *, uint64_t, uint64_t, HostPool::Group *) {};
-    // (chunk by chunk, synchronously: 8 bytes per base come down, the locate walk is ~100 gathers per base -- nothing to overlap)
-    return run_host(false, ix, h_bases, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest, 0);
+    auto harvest = [](const uint8_t *, const HostChunk &, HostPool::Group *, bool) {};
+    AutoPin pins[2];                                         // (kSaEntries: chunk by chunk, synchronously)
+    return run_host(ix, plan_reads_call(ix, HostQuery::kSaEntries, h_bases, h_offsets, n_reads, 0, h_out_pml != nullptr, pins), h_bases, h_offsets,
+                    h_read_err, stats, launch, fetch, harvest);
 }
 
 }  // extern "C"
@@ -3291,7 +3196,8 @@ int movi_multi_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uin
     movi_mc_read_t *d_o = nullptr;
     uint32_t *d_c = nullptr;
     uint16_t *d_pml = nullptr;
-    auto launch = [&](ChunkCtx &c, const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, uint8_t *derr) -> int {
+    auto launch = [&](ChunkCtx &c, const HostChunk &k, const uint8_t *db, const uint64_t *dof, uint8_t *derr) -> int {
+        const uint64_t nr = k.nr, nb = k.nb;
         HIP_TRY(c.alloc(movi_index::kA, nr * sizeof(movi_mc_read_t), &d_o));
         // the chunk's own counters, from its own staging (chunks of the overlapped path walk side by side): the caller's rows whole,
         // or scratch within "color_scratch_bytes" through which the chunk's reads go in turn
@@ -3302,20 +3208,22 @@ int movi_multi_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uin
                                      c.d_stats, h_counts ? nullptr : d_c, h_counts ? 0 : cbytes);
     };
     // page-locked block of a chunk in flight: out[nr] | counts[nr * S]
-    auto fetch = [&](ChunkCtx &c, uint64_t first, uint64_t nr, uint64_t b0, uint64_t nb) -> int {
+    auto fetch = [&](ChunkCtx &c, const HostChunk &k) -> int {
+        const uint64_t first = k.first, nr = k.nr, b0 = k.b0, nb = k.nb;
         HIP_TRY(c.down_small(h_out + first, 0, c.d[movi_index::kA].ptr(), nr * sizeof(movi_mc_read_t)));
         if (h_counts) HIP_TRY(c.down_small(h_counts + first * S, nr * sizeof(movi_mc_read_t), c.d[movi_index::kS].ptr(), nr * S * 4));
         if (h_out_pml) HIP_TRY(c.down(h_out_pml + b0, c.d[movi_index::kOut].ptr(), nb * 2));
         return MOVI_OK;
     };
-    auto harvest = [&](const uint8_t *h, uint64_t first, uint64_t nr, HostPool::Group *) {
+    auto harvest = [&](const uint8_t *h, const HostChunk &k, HostPool::Group *, bool) {
+        const uint64_t first = k.first, nr = k.nr;
         memcpy(h_out + first, h, nr * sizeof(movi_mc_read_t));
         if (h_counts) memcpy(h_counts + first * S, h + nr * sizeof(movi_mc_read_t), nr * S * 4);
     };
     // chunked through the host loop like the count query; overlapped where the reads sit in page-locked memory and no vector comes down
-    const bool overlapped = !h_out_pml && worth_overlapping_small_results(h_offsets, n_reads) && is_pinned(h_bases);
-    return run_host(overlapped, ix, h_bases, h_offsets, n_reads, h_read_err, stats, launch, fetch, harvest,
-                    sizeof(movi_mc_read_t) + (h_counts ? S * 4 : 0));
+    AutoPin pins[2];
+    return run_host(ix, plan_reads_call(ix, HostQuery::kMultiClassify, h_bases, h_offsets, n_reads, sizeof(movi_mc_read_t) + (h_counts ? S * 4 : 0),
+                                        h_out_pml != nullptr, pins), h_bases, h_offsets, h_read_err, stats, launch, fetch, harvest);
 }
 
 }  // extern "C"
