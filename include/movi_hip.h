@@ -289,7 +289,8 @@ int movi_launch_log(char *buf, size_t cap, size_t *needed);
  * pangenome BWT, 0.51 on a uniformly random run sequence; -1 = not tallied yet), "device_scratch_bytes" (device scratch the
  * *_device calls hold: movi_pml_device's mask words -- retired buffers that captured graphs may still use included --, the u16 vector
  * of a movi_pml_mask_device call whose path has no mask output, the segment workspace, the park queue), "host_staging_bytes" (the
- * *_host calls' device staging), "park_lanes" (what the last PML call's mask walk parked at: 0 = it parked nothing), "ff_skip" (1 = the last PML call's walk ran with the fast-forward skip) and "parked_reads"
+ * *_host calls' device staging), "park_lanes" (what the last PML call's mask walk parked at: 0 = it parked nothing), "ff_skip" (1 = the last PML call's walk ran with the fast-forward skip), "deep_hint_bits" (width of a
+ * reposition hint in the deep rows the handle holds: 4 or 2; 0 = it holds none) and "parked_reads"
  * (reads the last movi_pml_device / movi_pml_mask_device call's first launch handed to its second; waits for the device, so not under a
  * stream capture).  Unknown key: MOVI_ERR_ARG. */
 int movi_index_info(const movi_index_t *ix, const char *key, double *value);
@@ -810,7 +811,14 @@ int movi_host_unregister(void *p);
  * row with what the walk reads at its LF target AND at that row's target: up to three bases per gather.  Left alone, the first PML query
  * (or movi_index_prepare) builds them, beside the look-ahead rows, for tables of at most 50 M rows whose positions mostly reach their LF
  * target without a fast-forward (real text); 1 = build now (tables of fewer than 2^28 - 1 rows), 0 = none (freed).  "ahead_rows" 0 / 1
- * frees them too: it is a statement about what the walk runs on), "deep" (-1, the default: batches whose mean read length is below
+ * frees them too: it is a statement about what the walk runs on), "deep_hint_bits" (width of the deep rows' reposition hints, one per
+ * threshold slot of a row: how many rows beyond the edge of the row's three-row window a reposition scan ends, so that the walk gathers
+ * the target's window next instead of walking there window by window.  4 = reach 15, held beside 26-bit row ids: tables of at most
+ * 2^26 - 1 rows, in the same bytes -- tables of 2^26 rows and more keep 28-bit ids and 2-bit hints whatever is asked; 2 = reach 3 with
+ * 28-bit ids; -1, the default: 4 (c2 89.6 -> 91.0 Gbases/s, c2mid 72.9 -> 74.9: profiles/deep_hints.txt).  It takes effect when the
+ * deep rows are next built ("deep_rows" 1, movi_index_prepare or the first PML query); movi_index_info "deep_hint_bits" says what the
+ * rows the handle holds were built with.  Building looks up to 15 rows past either edge instead of 3: 0.89 -> 1.18 ms for 14 M rows,
+ * once per handle.  Same vectors, error bytes and counters at either width; fewer lane and wavefront steps: A/B), "deep" (-1, the default: batches whose mean read length is below
  * 1024 walk on the deep rows where the handle holds them; 0 = never, 1 = always, the segment plan's launches included: A/B),
  * "ftab_k" (the count query's interval table -- the backward-search interval after the last K bases of a read by one lookup,
  * the reference's own ftab (src/move_structure_search.cpp:66-167) put to work for --count; left alone the first count query

@@ -107,6 +107,7 @@ struct movi_index {
     int kmer_auto = 12;              // K of the table the first PML query builds by itself (0 = none: "kmer_k" 0)
     DevPtr<uint8_t> d_rows2;         // look-ahead rows ("ahead_rows" option), 16 bytes per row
     DevPtr<uint8_t> d_rows3;         // deep rows ("deep_rows" option), 21.33 bytes per row: what the PML walk runs on where the policy builds them
+    int deep_hint_bits = -1;         // "deep_hint_bits": width of a reposition hint in the deep rows when they are next built: -1 = kDeepHintBitsDefault, 2 or 4
     int deep_auto = 1;               // 1: the first PML query builds them for tables of at most kDeepAutoRows rows (instead of the look-ahead rows)
     double ahead_no_ff = 0.0;        // share of the table's positions that arrive at their LF target without a fast-forward (build_ahead)
     bool ahead_tallied = false;
@@ -956,21 +957,31 @@ static int build_ahead(movi_index *ix, hipStream_t s, bool by_itself) {
 // Infinity Cache and the per-CU TLBs: profiles/r06_deep_rows.txt has the sizes measured), instead of the look-ahead rows, which the PML
 // walk no longer needs then; "deep_rows" 1 / 0 builds / frees them at any eligible size.
 constexpr uint64_t kDeepAutoRows = 48ull << 20;             // 50 M rows: a copy of 1 GiB
+// Width of a reposition hint in the deep rows ("deep_hint_bits" -1).  4 = narrow ids, reach 15: the builder looks up to 15 rows past
+// either edge of a window for each of a row's three slots instead of 3 (c2, 14 M rows: profiles/deep_hints.txt has the build time).
+constexpr int kDeepHintBitsDefault = 4;
 static bool deep_eligible(const movi_index *ix) {
     return ix->kmode == MOVI_MODE_REGULAR_THRESHOLDS && deep_rows_eligible(ix->desc.r);
 }
 static void drop_deep(movi_index *ix) {
     ix->dev.rows3 = nullptr;
+    ix->dev.deep_id_mask = ix->dev.deep_id_bits = ix->dev.deep_j3_shift = ix->dev.deep_hint_bits = 0;
     ix->d_rows3.reset();
 }
 static int build_deep(movi_index *ix, hipStream_t s) {
     DevPtr<uint8_t> rows3;
     HIP_TRY(dev_alloc(rows3, deep_rows_bytes(ix->desc.r)));
-    hipError_t e = build_deep_rows(ix->kmode, ix->dev, rows3.get(), s);
+    const int want = ix->deep_hint_bits < 0 ? kDeepHintBitsDefault : ix->deep_hint_bits;
+    const DeepMap map = deep_map_for(ix->desc.r, want);      // (4 bits need narrow ids: tables of 2^26 rows and more keep wide ids and 2 bits)
+    hipError_t e = build_deep_rows(ix->kmode, ix->dev, (int)map.hint_bits, rows3.get(), s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail_hip(e, "building the deep rows");
     ix->d_rows3 = std::move(rows3);
     ix->dev.rows3 = ix->d_rows3.get();
+    ix->dev.deep_id_mask = map.id_mask;
+    ix->dev.deep_id_bits = map.id_bits;
+    ix->dev.deep_j3_shift = map.j3_shift;
+    ix->dev.deep_hint_bits = map.hint_bits;
     return MOVI_OK;
 }
 
@@ -1268,6 +1279,11 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
         if (!deep_eligible(ix)) return fail(MOVI_ERR_ARG, "deep rows serve PML walks on *-thresholds indexes of fewer than 2^28 - 1 rows only");
         return build_deep(ix, nullptr);
     }
+    if (!strcmp(key, "deep_hint_bits")) {                    // width of a deep row's reposition hints: -1 = the default, 2 (reach 3, wide ids) or 4 (reach 15, narrow ids); takes effect when the deep rows are next built (A/B)
+        if (value != -1 && value != 2 && value != 4) return fail(MOVI_ERR_ARG, "deep_hint_bits must be -1, 2 or 4");
+        ix->deep_hint_bits = (int)value;
+        return MOVI_OK;
+    }
     if (!strcmp(key, "deep")) {                              // the walk on the deep rows the handle holds: -1 = batches of short reads, 0 never, 1 always (A/B)
         if (value < -1 || value > 1) return fail(MOVI_ERR_ARG, "deep must be -1, 0 or 1");
         ix->cfg.deep = (int)value;
@@ -1481,6 +1497,7 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     else if (!strcmp(key, "ftab_bytes")) *value = ftab;
     else if (!strcmp(key, "ahead_rows_bytes")) *value = ahead;
     else if (!strcmp(key, "deep_rows_bytes")) *value = deep;
+    else if (!strcmp(key, "deep_hint_bits")) *value = ix->d_rows3 ? (double)ix->dev.deep_hint_bits : 0.0;   // width of a hint in the deep rows the handle holds (0 = it holds none)
     else if (!strcmp(key, "ckpt_bytes")) *value = ckpt;
     else if (!strcmp(key, "color_bytes")) *value = color;
     else if (!strcmp(key, "color_taxa")) *value = (double)ix->color_taxa.size();      // to_taxon_id entries held (0 after a load)

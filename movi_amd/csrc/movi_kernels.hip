@@ -356,83 +356,67 @@ hipError_t build_ahead_rows(int kmode, const DevIndex &ix, uint8_t *d_rows2, uin
 }
 
 // ---- deep rows (DevIndex::rows3, round 6): thread i writes row i of the copy -- the row, what the walk reads at j = id(i) and at
-// j2 = id(j), and j3 = id(j2) (three dependent gathers) -- and its reposition hints for windows of three rows.
-__global__ __launch_bounds__(256) void deep_rows_kernel(DevIndex ix, uint32_t *__restrict__ out) {
+// j2 = id(j), and j3 = id(j2) (three dependent gathers) -- and its reposition hints for windows of three rows, in the field map `map`
+// (movi_deep_fields.hpp: wide ids with 2-bit hints, reach 3, or narrow ids with 4-bit hints, reach 15).
+__global__ __launch_bounds__(256) void deep_rows_kernel(DevIndex ix, DeepMap map, uint32_t *__restrict__ out) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t padded = ((ix.r + 2) / 3) * 3;
     if (i >= padded) return;
     uint32_t *W = out + (i / 3) * 16u;
     const uint32_t s = (uint32_t)(i % 3);
-    uint32_t d0 = 0x0FFFFFFFu, d1 = (7u << 22) | (7u << 25) | (7u << 28), d2 = 0x0FFFFFFFu, d3 = 0, d4 = 0x0FFFFFFFu, x = 0;
+    DeepFields f;                                         // a row beyond r - 1 (the last window's padding): no ids, c = 7, n = 0
+    f.j = f.j2 = f.j3 = 0xFFFFFFFFu;
+    f.thr = 0; f.n = 0; f.off = 0; f.c = 7u; f.cj = 7u; f.cj2 = 7u; f.nj = 0; f.offj = 0; f.nj2 = 0; f.offj2 = 0; f.hints = 0;
     if (i < ix.r) {
         const uint2 row = load_row<6>(ix.rows, i);
         const uint64_t j = row_id<6>(row, i, ix);
         const uint32_t c = row_c<6>(row);
-        d0 = (j < ix.r ? (uint32_t)j : 0x0FFFFFFFu) | (row_thr<6>(row, 0) << 28) | (row_thr<6>(row, 1) << 29) | (row_thr<6>(row, 2) << 30);
-        d1 = row_n<6>(row) | (row_off<6>(row) << 11) | (c << 22) | (7u << 25) | (7u << 28);
+        f.j = j < ix.r ? (uint32_t)j : 0xFFFFFFFFu;
+        f.thr = row_thr<6>(row, 0) | (row_thr<6>(row, 1) << 1) | (row_thr<6>(row, 2) << 2);
+        f.n = row_n<6>(row); f.off = row_off<6>(row); f.c = c;
         if (j < ix.r) {
             const uint2 rj = load_row<6>(ix.rows, j);
             const uint64_t j2 = row_id<6>(rj, j, ix);
             if (j2 < ix.r) {
                 const uint2 rj2 = load_row<6>(ix.rows, j2);
                 const uint64_t j3 = row_id<6>(rj2, j2, ix);
-                d1 = (d1 & ~(7u << 25)) | (row_c<6>(rj) << 25);
-                d2 = (uint32_t)j2;
-                d3 = row_n<6>(rj) | (row_off<6>(rj) << 11);
+                f.cj = row_c<6>(rj);
+                f.j2 = (uint32_t)j2;
+                f.nj = row_n<6>(rj); f.offj = row_off<6>(rj);
                 if (j3 < ix.r) {
-                    const uint32_t n2 = row_n<6>(rj2), o2 = row_off<6>(rj2);
-                    d1 = (d1 & ~(7u << 28)) | (row_c<6>(rj2) << 28);
-                    d3 |= (n2 & 0x3FFu) << 22;
-                    d4 = (uint32_t)j3 | ((n2 >> 10) << 28) | ((o2 & 7u) << 29);
-                    x = o2 >> 3;
+                    f.cj2 = row_c<6>(rj2);
+                    f.j3 = (uint32_t)j3;
+                    f.nj2 = row_n<6>(rj2); f.offj2 = row_off<6>(rj2);
                 }
             }
         }
-        // hints: the nearest run of each other base beyond the edges of the window the walk sees row i in (ahead_rows_kernel's rule, three-row windows, reach 3)
-        uint32_t h = 0;
+        // hints: the nearest run of each other base beyond the edges of the window the walk sees row i in (deep_hint_of; reach 2^B - 1)
         if (ix.sep == 0u && ix.sigma == 4u && i != ix.end_bwt_idx) {
-            const uint64_t wb = (i / 3) * 3;
+            const uint8_t *rows = ix.rows;
+            auto c_of = [rows](uint64_t t) { return row_c<6>(load_row<6>(rows, t)); };
+            const uint32_t reach = (1u << map.hint_bits) - 1u;
             for (uint32_t k = 0; k < 3u; ++k) {
                 const uint32_t a = k < c ? k : k + 1u;    // the base whose slot is k: alphamap_3[c][a] = a - (a > c), src/utils.cpp:5-8
                 if (a > 3u) continue;
-                uint32_t d = 0;
-                if (row_thr<6>(row, k) == 0u) {           // threshold 0 <= offset: reposition_down
-                    const uint64_t edge = wb + 2;
-                    bool inside = false;
-                    for (uint64_t t = i + 1; t <= edge && t < ix.r; ++t) inside = inside || row_c<6>(load_row<6>(ix.rows, t)) == a;
-                    if (!inside)
-                        for (uint64_t t = edge + 1; t <= edge + 3 && t < ix.r; ++t)
-                            if (row_c<6>(load_row<6>(ix.rows, t)) == a) { d = (uint32_t)(t - edge); break; }
-                } else {                                  // threshold n > offset: reposition_up
-                    bool inside = false;
-                    for (uint64_t t = wb; t < i; ++t) inside = inside || row_c<6>(load_row<6>(ix.rows, t)) == a;
-                    if (!inside)
-                        for (uint64_t t = 1; t <= 3 && t <= wb; ++t)
-                            if (row_c<6>(load_row<6>(ix.rows, wb - t)) == a) { d = (uint32_t)t; break; }
-                }
-                h |= d << (2u * k);
+                f.hints |= deep_hint_of(c_of, ix.r, i, a, row_thr<6>(row, k) == 0u, reach) << (map.hint_bits * k);
             }
         }
-        d2 |= (h & 15u) << 28;
-        x |= (h >> 4) << 8;
     }
-    W[5u * s + 0u] = d0;
-    W[5u * s + 1u] = d1;
-    W[5u * s + 2u] = d2;
-    W[5u * s + 3u] = d3;
-    W[5u * s + 4u] = d4;
+    uint32_t d[5], x;
+    deep_pack(map, f, d, x);
+    for (uint32_t t = 0; t < 5u; ++t) W[5u * s + t] = d[t];
     atomicOr(&W[15], x << (10u * s));                     // (the table is zeroed first; three rows share the dword)
 }
 
 uint64_t deep_rows_bytes(uint64_t r) { return ((r + 2) / 3) * 64; }
 bool deep_rows_eligible(uint64_t r) { return r >= 8 && r < 0x0FFFFFFFull; }
 
-hipError_t build_deep_rows(int kmode, const DevIndex &ix, uint8_t *d_rows3, hipStream_t stream) {
+hipError_t build_deep_rows(int kmode, const DevIndex &ix, int hint_bits, uint8_t *d_rows3, hipStream_t stream) {
     if (!d_rows3 || !deep_rows_eligible(ix.r) || kmode != 6) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(d_rows3, 0, deep_rows_bytes(ix.r), stream);
     if (e != hipSuccess) return e;
     const uint64_t blocks = (ix.r + 2 + 255) / 256;
-    hipLaunchKernelGGL(deep_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ix, reinterpret_cast<uint32_t *>(d_rows3));
+    hipLaunchKernelGGL(deep_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ix, deep_map_for(ix.r, hint_bits), reinterpret_cast<uint32_t *>(d_rows3));
     return hipGetLastError();
 }
 
@@ -885,7 +869,7 @@ static hipError_t launch_pml_segmented(const PmlCall &c, uint16_t *d_out, bool *
     DevIndex ixl = ix;
     ixl.inwin = cfg.inwin ? 1u : 0u;
     const bool seg_deep = ix.rows3 != nullptr && ix.idx32 != 0u && cfg.deep > 0 && cfg.stage_reads != 0;
-    ixl.hint_w = seg_deep ? (cfg.hints != 0 ? 2u : 0u) : ((cfg.hints != 0 && ix.hints != 0u && ix.rows2 != nullptr) ? 3u : 0u);
+    ixl.hint_w = seg_deep ? (cfg.hints != 0 ? ix.deep_hint_bits : 0u) : ((cfg.hints != 0 && ix.hints != 0u && ix.rows2 != nullptr) ? 3u : 0u);
     auto launch_seg = [&](int segv, uint64_t lanes, const PmlPlan &sp, LaunchInfo *li) -> hipError_t {
         ixl.stage_lds = sp.stage_lds;
         ixl.ff_skip = ff_skip_on(cfg, sp.use_deep, sp.use_ahead) ? 1u : 0u;
@@ -1074,7 +1058,7 @@ hipError_t launch_pml(const PmlCall &c, const PmlRoute &R) {
     DevIndex ixl = ix;
     ixl.stage_lds = P.stage_lds;
     ixl.inwin = cfg.inwin ? 1u : 0u;
-    ixl.hint_w = R.hint_w;
+    ixl.hint_w = (R.ahd == 2 && R.hint_w != 0u) ? ix.deep_hint_bits : R.hint_w;   // (the plan says "on" (2) for the deep rows: the width is the one they were built with)
     ixl.mask_phase = mask.phase & 31u;
     ixl.ff_skip = R.ff_skip ? 1u : 0u;
     ixl.expand_out = R.kind == PmlRouteKind::kVectorFused ? expand_out : nullptr;

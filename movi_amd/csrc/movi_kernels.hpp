@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "movi_launch_policy.hpp"   // LaunchCfg, the kCap* / k*ReadLen / k*Bytes constants, the launch plans
+#include "movi_deep_fields.hpp"     // the deep rows' two field maps (plain C++: host tests compile it too)
 #include "movi_buffers.hpp"         // the owning types (host side only); their two memory policies are below
 
 namespace movi {
@@ -91,23 +92,24 @@ struct DevIndex {
     // In this form ids in rows2 are 32 bits wide: x alone (a row whose id is not a row reads x = 0xFFFFFFFF), and every
     // reader of rows2 masks the hint bits off (tab_row / tab_entry / the walk kernel).
     uint32_t hints;
-    // set per launch: width of a hint field the walk looks at -- 3 = use the hints (2 on the deep rows), 0 = ignore them ("repo_hints" 0: A/B)
+    // set per launch: width of a hint field the walk looks at -- 3 = use the hints (on the deep rows: the width they were built with, deep_hint_bits), 0 = ignore them ("repo_hints" 0: A/B)
     uint32_t hint_w;
     // Round 6 -- DEEP ROWS ("deep_rows" option; nullptr = none; tables of fewer than 2^28 - 1 rows): a copy of the table in which every row
     // carries what the walk reads at its LF target j = id(i) AND at j2 = id(j) -- up to three bases per gather -- packed to 21.33 bytes
     // per row (round 4's chain rows held the same in 32 bytes per row and fell out of the Infinity Cache: profiles/r04_chain_rows.txt).
     // Window q = rows 3q .. 3q + 2 = 64 bytes at byte 64 q (two windows per 128-byte line, six rows per line); 16 dwords: row s at
-    // dwords 5s .. 5s + 4, its ten extra bits at [10s + 9 : 10s] of dword 15.  Row i, with j = id(i), j2 = id(j), j3 = id(j2):
-    //   D0 = j (28 bits; 0x0FFFFFFF = not a row) | thr0 << 28 | thr1 << 29 | thr2 << 30
-    //   D1 = n(i) | off(i) << 11 | c(i) << 22 | c(j) << 25 | c(j2) << 28          (c(j) = 7: no entry for j -- j or j2 is not a row; c(j2) = 7 likewise for j2 / j3)
-    //   D2 = j2 (28 bits) | hints[3:0] << 28
-    //   D3 = n(j) | off(j) << 11 | n(j2)[9:0] << 22
-    //   D4 = j3 (28 bits) | n(j2)[10] << 28 | off(j2)[2:0] << 29
-    //   X  = off(j2)[10:3] | hints[5:4] << 8
-    // hints: two bits per threshold slot k (bits 2k + 1 : 2k): rows beyond the edge of the row's three-row window at which the nearest run
-    // of the slot's base lies in the direction the threshold bit gives, 1 .. 3; 0 = inside the window, further, nowhere, or the '$' row.
+    // dwords 5s .. 5s + 4, its ten extra bits at [10s + 9 : 10s] of dword 15.  What the five dwords and the ten bits hold is written
+    // down, packed and unpacked in movi_deep_fields.hpp, in two FIELD MAPS that differ in three numbers only:
+    //   wide ids   (28-bit ids, 0x0FFFFFFF = not a row; three 2-bit hints, reach 3):  every eligible table; the only map from 2^26 rows on
+    //   narrow ids (26-bit ids, 0x03FFFFFF = not a row; three 4-bit hints, reach 15): tables of at most 2^26 - 1 rows ("deep_hint_bits" 4)
+    // hints: one field per threshold slot k: rows beyond the edge of the row's three-row window at which the nearest run of the slot's
+    // base lies in the direction the threshold bit gives, 1 .. reach; 0 = inside the window, further, nowhere, or the '$' row.  Scans
+    // that run past reach 3 are 3.7 % of c2's lane iterations, on the reads that set their wavefronts' length (profiles/deep_hints.txt).
     // The rows of the last window beyond r - 1 are padding (c = 7, n = 0, never reached).
     const uint8_t *rows3;
+    // the field map rows3 was built in (DeepMap; wave-uniform in the walk): mask of an id = the id that is no row, width of an id,
+    // shift of j3 in dword 4, width of a hint as built (the launchers copy it to hint_w, or 0 with "repo_hints" 0)
+    uint32_t deep_id_mask, deep_id_bits, deep_j3_shift, deep_hint_bits;
     // set per launch, reset-mask output (RING = 2) in blocks of one wavefront: non-null = every wavefront, when its 64 walks are over, turns
     // its reads' mask words into their u16 PML vectors here (through a tile in the LDS its reads were staged in: pml_kernel_flatp's tail)
     // -- the vector output at the mask walk's instruction count, the expansion hidden under the other wavefronts' gathers
@@ -375,7 +377,7 @@ uint64_t ahead_rows_bytes(uint64_t r);
 // Thresholds types (kmode 6), 8 <= r < 2^28 - 1.
 uint64_t deep_rows_bytes(uint64_t r);
 bool deep_rows_eligible(uint64_t r);
-hipError_t build_deep_rows(int kmode, const DevIndex &ix, uint8_t *d_rows3, hipStream_t stream);
+hipError_t build_deep_rows(int kmode, const DevIndex &ix, int hint_bits, uint8_t *d_rows3, hipStream_t stream);   // hint_bits: 2 or 4 (deep_map_for)
 bool ahead_rows_hinted(uint64_t r);    // the copy of a table of r rows carries reposition hints and 32-bit ids (DevIndex::hints)
 hipError_t build_ahead_rows(int kmode, const DevIndex &ix, uint8_t *d_rows2, uint64_t *tail, hipStream_t stream,
                             unsigned long long *d_tally = nullptr);   // d_tally: 2 * kTallySlots zeroed u64 (tally_add spreads the atomics by block; the caller sums the pairs), optional

@@ -489,11 +489,10 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
             const uint32_t scan_edge = scanning & (hit ^ 1u) & (isDown ? at_last : at_first);
             const uint32_t emit = (resolved & (illegal | match)) | landed;
             const uint32_t lf = emit & (uint32_t)(k + 1 != len);
-            const uint32_t jj = f0 & 0x0FFFFFFFu;                                           // id(row): 28 bits; 0x0FFFFFFF = not a row (r < 2^28)
+            const uint32_t jj = deep_get_j(f0, ix.deep_id_mask);                            // id(row): 28 or 26 bits, all ones = not a row (the table's field map: movi_deep_fields.hpp)
             const uint32_t lf_bad = lf & (uint32_t)(jj >= (uint32_t)ix.r);
-            // reposition hints: two bits per threshold slot (rows beyond the window's edge: 1 .. 3)
-            const uint32_t h6 = (f2 >> 28) | ((fx >> 8) << 4);
-            const uint32_t hd = __builtin_amdgcn_ubfe(h6, kc + kc, ix.hint_w);            // (hint_w: 2 here, or 0 = switched off)
+            // reposition hints: two or four bits per threshold slot (rows beyond the window's edge: 1 .. 3 or 1 .. 15)
+            const uint32_t hd = deep_get_hint(deep_get_hints(f2, f4, ix.deep_id_bits), kc, ix.hint_w);   // (hint_w: the width the rows were built with, or 0 = switched off)
             const uint32_t jump = far & (uint32_t)(hd != 0u);
             const uint32_t jtgt = down ? wbase + 2u + hd : wbase - hd;
             const uint32_t jdist = down ? jtgt - nd : nd - jtgt;
@@ -502,9 +501,9 @@ __global__ __launch_bounds__(256) void pml_kernel_flatp(DevIndex ix, const uint8
             uint32_t need_next = lf ? jj : (jump ? jtgt : nd + step_fwd - step_back);
             uint32_t st_next = (emit & (lf ^ 1u)) ? sDone : (lf ? sFF : (far ? (down ? sDown : sUp) : st));
             // the two bases after this one, at j and at j2 (read_processor.cpp:188-238 with match and no fast-forward: ml + 1, LF_move again)
-            const uint32_t e1n = f3 & 0x7FFu, e1off = (f3 >> 11) & 0x7FFu, e1c = (f1 >> 25) & 7u, jj2 = f2 & 0x0FFFFFFFu;
-            const uint32_t e2n = (f3 >> 22) | (((f4 >> 28) & 1u) << 10), e2off = ((f4 >> 29) & 7u) | ((fx & 0xFFu) << 3), e2c = (f1 >> 28) & 7u,
-                           jj3 = f4 & 0x0FFFFFFFu;
+            const uint32_t e1n = f3 & 0x7FFu, e1off = (f3 >> 11) & 0x7FFu, e1c = (f1 >> 25) & 7u, jj2 = deep_get_j2(f2, ix.deep_id_mask);
+            const uint32_t e2n = deep_get_nj2(f0, f3), e2off = deep_get_offj2(f1, fx), e2c = (f1 >> 28) & 7u,
+                           jj3 = deep_get_j3(f4, ix.deep_j3_shift);
             const uint32_t off_e = (landed ? (landed_down ? 0u : nf - 1u) : off) + rofff;
             const uint32_t dbl = lf & (uint32_t)(a1 == e1c) & (uint32_t)(off_e < e1n);    // (an invalid entry has c = 7: no base code equals it)
             const uint32_t lf2 = dbl & (uint32_t)(k + 2 != len);

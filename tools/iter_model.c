@@ -189,6 +189,9 @@ int main(int argc, char **argv) {
         {1, 4, 2, 7, 1, 0, 8}, {2, 4, 2, 7, 1, 0, 4}, {2, 3, 0, 0, 1, 0, 6}, {2, 3, 2, 7, 1, 0, 6}, {2, 3, 2, 3, 1, 0, 6}, {2, 6, 2, 7, 1, 0, 6}, {3, 3, 2, 7, 1, 0, 6},
         // the fast-forward skip on the two layouts that ship: deep rows (S = 2, W = 3, hints of 2 bits) and look-ahead rows (S = 1, W = 4, hints of 3 bits)
         {2, 3, 2, 3, 1, 0, 6, 1}, {1, 4, 2, 7, 1, 0, 8, 1},
+        // wider hints on the deep rows with the skip: 3, 4 and 6 bits per threshold slot (reach 7, 15, 63).  4 bits fit beside 26-bit ids
+        // ("deep_hint_bits" 4: tables of at most 2^26 - 1 rows) and are the knee: profiles/deep_hints.txt
+        {2, 3, 2, 7, 1, 0, 6, 1}, {2, 3, 2, 15, 1, 0, 6, 1}, {2, 3, 2, 63, 1, 0, 6, 1},
     };
     printf("r = %llu rows, %llu reads x %u, top-of-walk K = %u\n", (unsigned long long)r, (unsigned long long)n_reads, L, top_k);
     printf("%-40s %9s %9s | %7s %7s %7s %7s | %7s | %6s %6s %6s | %7s\n", "design", "iter/base", "SIMT", "arrive", "ff-win", "mismat", "scanwin",
