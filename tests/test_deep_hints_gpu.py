@@ -2,7 +2,8 @@
 at most 2^26 - 1 rows hold 26-bit ids and three 4-bit hints a row (reach 15) in the bytes that held 28-bit ids and 2-bit hints (reach 3).
 A hint only says where a reposition scan that leaves the window ends (reposition_up / _down, src/move_structure_query.cpp:188-232), so
 the u16 vector, the mask words, the per-read error bytes and the fast-forward / scan / reposition / error counters must be the oracle's
-with "deep_hint_bits" 4, with 2 and with "repo_hints" 0 -- only lane steps may differ.  Every case runs all three."""
+with "deep_hint_bits" 4, with 2 and with "repo_hints" 0 -- only lane steps may differ.  Every case runs all three.  The tables of 2^26
+rows and more, which have the wide map only, and the ids whose bits 27:26 are set: test_deep_wide_ids_gpu.py, with _set and _three_ways."""
 import os
 import subprocess
 
@@ -11,7 +12,7 @@ import pytest
 
 import deep_hint_texts as D
 from conftest import GOLDEN
-from test_gpu_parity import mutated_reads, pack
+from test_gpu_parity import check_segmented, mutated_reads, pack
 
 pytestmark = pytest.mark.gpu
 
@@ -31,21 +32,24 @@ def _dev(a):
     return torch.from_numpy(np.array(a)).to(torch.device("cuda", 0))
 
 
-def _set(gpu, bits, hints):
-    """Build the deep rows with hints of `bits` bits (the option takes effect when they are next built) and switch the hints on or off."""
+def _set(gpu, bits, hints, built=None):
+    """Build the deep rows with hints of `bits` bits (the option takes effect when they are next built) and switch the hints on or off.
+    `built`: the width the rows must then have -- `bits`, or 2 whatever is asked on a table of 2^26 rows and more, which keeps wide ids."""
     gpu.set_option("deep_hint_bits", bits)
     gpu.set_option("deep_rows", 1)
     gpu.set_option("repo_hints", hints)
-    assert int(gpu.info("deep_hint_bits")) == bits and gpu.info("deep_rows_bytes") == ((gpu.desc.r + 2) // 3) * 64
+    assert int(gpu.info("deep_hint_bits")) == (bits if built is None else built)
+    assert gpu.info("deep_rows_bytes") == ((gpu.desc.r + 2) // 3) * 64
 
 
-def _three_ways(gpu, bases, offs, exp, ff, sc, tag, want=None, sep=0):
+def _three_ways(gpu, bases, offs, exp, ff, sc, tag, want=None, sep=0, wide_only=False):
     """Vector, mask words, error bytes and counters under the three SETTINGS, against the oracle's (exp, ff, sc) or -- a table on which
-    reads fail -- against `want` = (vector, error bytes, rc, counters) of the walk on the plain rows.  Returns the lane steps by setting."""
+    reads fail -- against `want` = (vector, error bytes, rc, counters) of the walk on the plain rows.  `wide_only`: a table of 2^26 rows
+    and more, whose rows are built with 2-bit hints under every setting.  Returns the lane steps by setting."""
     from movi_amd import engine as E
     steps, repos, first_words = {}, set(), None
     for bits, hints in SETTINGS:
-        _set(gpu, bits, hints)
+        _set(gpu, bits, hints, 2 if wide_only else None)
         gpu.set_option("pml_via_mask", 0)                   # the vector from the walk itself
         gpu.set_option("host_masks", 0)
         out, st, err, rc = gpu.query_pml_packed(bases, offs, want_err=True)
@@ -111,6 +115,24 @@ def test_golden_index(golden_cases, mode, sep):
         if not sep:                                         # (an index with separators carries no hints)
             assert steps[(2, 1)] < steps[(4, 0)]
     finally:
+        gpu.close()
+
+
+@pytest.mark.parametrize("mode", [6, 8])
+def test_golden_index_segments(golden_cases, mode):
+    """The segment walk sets the width of a hint on a line of its own: the batch's long reads cut into 32-base segments, on the deep rows
+    ("deep" 1) under the three SETTINGS."""
+    import movi_amd
+    b = golden_cases[(mode, 0)]
+    gpu = movi_amd.MoveIndex.from_image(b["img"])
+    try:
+        gpu.set_option("deep", 1)
+        for bits, hints in SETTINGS:
+            _set(gpu, bits, hints)
+            check_segmented(gpu, b["bases"], b["offs"], b["exp"], b["ff"], b["sc"], (mode, bits, hints))
+            assert gpu.last_launch()["ahead"] == 2, (mode, bits, hints, gpu.last_launch())
+    finally:
+        gpu.set_option("deep", -1)
         gpu.close()
 
 
@@ -239,15 +261,18 @@ def test_targets_at_the_reach(built_lib, case):
 
 # ------------------------------------------------------------------------------------------------------------------ 4. corrupt ids
 def test_corrupt_ids(built_lib, golden_image):
-    """Ids that are no row -- the 26-bit "not a row" value itself, r, r + 5, 2^28 - 1, 2^32 - 1 -- at rows whose entries of depth one and
-    two become invalid at different places: the reads that fail, their error codes and everything else as on the plain rows."""
+    """Ids that are no row -- the 26-bit "not a row" value itself, r, r + 5, 2^28 - 1, 2^32 - 1, and 2^26 + 5, 2^28 + 5, 2^31 + 7, which
+    cut to 26 or 28 bits are rows 5 and 7: only the builder's comparison with r makes them "not a row", a mask would not -- at rows whose
+    entries of depth one and two become invalid at different places: the reads that fail, their error codes and everything else as on
+    the plain rows."""
     import movi_amd
     ref = _ref()
     img = bytearray(golden_image(6))
     d, _, off, _ = movi_amd.parse_index_image(bytes(img))
     rows = np.frombuffer(img, np.uint8, count=d.r * 8, offset=off).reshape(-1, 8).copy()
     ids = rows[:, 0:4].copy().view(np.uint32)[:, 0]
-    for start, bad_id in ((0, 0x03FFFFFF), (31, d.r), (57, d.r + 5), (71, 0x0FFFFFFF), (83, 0xFFFFFFFF)):
+    for start, bad_id in ((0, 0x03FFFFFF), (31, d.r), (57, d.r + 5), (71, 0x0FFFFFFF), (83, 0xFFFFFFFF),
+                          (13, (1 << 26) + 5), (43, (1 << 28) + 5), (91, 0x80000007)):
         ids[start::97] = bad_id
     rows[:, 0:4] = ids.view(np.uint8).reshape(-1, 4)
     img[off: off + rows.size] = rows.tobytes()
