@@ -5,6 +5,7 @@
 #include "../../include/movi_hip.h"
 #include "movi_kernels.hpp"
 #include "movi_host_plan.hpp"
+#include "movi_derived.hpp"
 #include "movi_expand_host.hpp"
 #include "movi_pack_host.hpp"
 #include "movi_build.hpp"
@@ -87,6 +88,53 @@ struct Reader {
 // the calling thread's message, for the entry points that live outside this file (movi_pack_host.cpp)
 int movi::set_last_error(int code, const char *msg) { return fail(code, msg); }
 
+// The handle's derived tables: one owner for the five device blocks and for what each publishes into the kernels' view of the index.
+// publish() is the only writer of those DevIndex fields: it runs after every build and every drop, and once when the handle is made.
+struct DerivedTables {
+    DevPtr<uint4> kmer;              // top-of-walk table ("kmer_k" option)
+    DevPtr<uint4> ftab;              // the count query's interval table ("ftab_k" option)
+    DevPtr<uint8_t> rows2;           // look-ahead rows ("ahead_rows" option), 16 bytes per row
+    DevPtr<uint8_t> rows3;           // deep rows ("deep_rows" option), 21.33 bytes per row: what the PML walk runs on where the policy builds them
+    DevPtr<uint64_t> ckpt;           // row-start checkpoints: built lazily by the first count query
+    uint32_t kmer_k = 0, ftab_k = 0;
+    uint64_t rows2_tail = 0;
+    uint32_t rows2_count = 0, hints = 0;
+    DeepMap deep{0, 0, 0, 0};        // the field map rows3 was built in
+    bool held(DerivedTable t) const {
+        return t == kTabKmer ? (bool)kmer : t == kTabFtab ? (bool)ftab : t == kTabAhead ? (bool)rows2 : t == kTabDeep ? (bool)rows3 : (bool)ckpt;
+    }
+    void reset(DerivedTable t) {
+        switch (t) {
+        case kTabKmer: kmer.reset(); kmer_k = 0; break;
+        case kTabFtab: ftab.reset(); ftab_k = 0; break;
+        case kTabAhead: rows2.reset(); rows2_tail = 0; rows2_count = hints = 0; break;
+        case kTabDeep: rows3.reset(); deep = DeepMap{0, 0, 0, 0}; break;
+        default: ckpt.reset(); break;
+        }
+    }
+    void publish(DevIndex &v) const {
+        v.kmer = kmer.get(); v.kmer_k = kmer_k;
+        v.ftab = ftab.get(); v.ftab_k = ftab_k;
+        v.rows2 = rows2.get(); v.rows2_tail = rows2_tail; v.rows2_count = rows2_count; v.hints = hints;
+        v.rows3 = rows3.get(); v.deep_id_mask = deep.id_mask; v.deep_id_bits = deep.id_bits; v.deep_j3_shift = deep.j3_shift; v.deep_hint_bits = deep.hint_bits;
+        v.row_start_ckpt = ckpt.get();
+    }
+    // One size per table of r rows (K: of the two lookup tables): what its builder allocates, and what movi_index_info reports of a table
+    // the handle holds -- but for the checkpoints, whose report has a formula of its own (below)
+    static size_t bytes(DerivedTable t, uint64_t r, uint32_t K) {
+        switch (t) {
+        case kTabKmer: case kTabFtab: return (size_t)16 << (2 * K);
+        case kTabAhead: return ahead_rows_bytes(r);
+        case kTabDeep: return deep_rows_bytes(r);
+        default: return (((r + (1ull << kPrefixShift) - 1) >> kPrefixShift) + 1) * sizeof(uint64_t);   // ceil(r / 32) + 1 entries
+        }
+    }
+    double held_bytes(DerivedTable t, uint64_t r) const { return held(t) ? (double)bytes(t, r, t == kTabKmer ? kmer_k : ftab_k) : 0.0; }
+    // "ckpt_bytes" has always reported r / 32 + 2 entries: 8 bytes more than are allocated where r is a multiple of 32, the same
+    // elsewhere.  The two formulas differ by up to 8 bytes and both stay as they are.
+    double ckpt_bytes_reported(uint64_t r) const { return ckpt ? (double)((r >> kPrefixShift) + 2) * 8.0 : 0.0; }
+};
+
 struct movi_index {
     int device = 0;
     movi_index_desc_t desc{};
@@ -102,21 +150,8 @@ struct movi_index {
     size_t rows_bytes = 0;
     DevPtr<uint8_t> d_code_of;
     DevPtr<uint32_t> d_id_blocks;
-    DevPtr<uint64_t> d_ckpt;         // built lazily by the first count query
-    DevPtr<uint4> d_kmer;            // top-of-walk table ("kmer_k" option), 16 << 2K bytes
-    int kmer_auto = 12;              // K of the table the first PML query builds by itself (0 = none: "kmer_k" 0)
-    DevPtr<uint8_t> d_rows2;         // look-ahead rows ("ahead_rows" option), 16 bytes per row
-    DevPtr<uint8_t> d_rows3;         // deep rows ("deep_rows" option), 21.33 bytes per row: what the PML walk runs on where the policy builds them
-    int deep_hint_bits = -1;         // "deep_hint_bits": width of a reposition hint in the deep rows when they are next built: -1 = kDeepHintBitsDefault, 2 or 4
-    int deep_auto = 1;               // 1: the first PML query builds them for tables of at most kDeepAutoRows rows (instead of the look-ahead rows)
-    double ahead_no_ff = 0.0;        // share of the table's positions that arrive at their LF target without a fast-forward (build_ahead)
-    bool ahead_tallied = false;
-    bool count_declined_ahead = false;   // the count query's auto-build found the copy not worth keeping (rows2_count == 0): do not build it per call
-    int ahead_auto = 1;              // 1: the first PML query builds them when the device has room for them (ahead_wanted)
-    int ahead_retry_in = 0;          // the copy was declined for lack of device memory: calls until the device is asked again (not every call)
-    bool prepared = false;           // movi_index_prepare has run: query calls build and allocate nothing any more (a declined copy is retried by movi_index_prepare only)
-    DevPtr<uint4> d_ftab;            // the count query's interval table ("ftab_k" option), 16 << 2K bytes
-    int ftab_auto = 12;              // K of the table the first count query builds by itself (0 = none)
+    DerivedTables tables;            // the derived tables and what they publish into `dev` ...
+    DerivedPolicy policy;            // ... and which of them are built when (movi_derived.hpp)
     DevPtr<DevStats> d_stats;
     // locate: the attached sampled suffix array (movi_ssa_build / movi_ssa_load) and the locate rows derived from the table for its rate
     DevPtr<uint4> d_loc;             // 16 bytes per row (movi_sa.hpp)
@@ -412,7 +447,7 @@ static int finish_create(movi_index *ix) {
     v.rows = ix->d_rows.get();
     v.id_blocks = ix->d_id_blocks.get();
     v.code_of = ix->d_code_of.get();
-    v.row_start_ckpt = nullptr;
+    ix->tables.publish(v);                                   // (none yet)
     v.r = d.r;
     v.end_bwt_idx = d.end_bwt_idx;
     v.n_blocks = d.n_blocks;
@@ -852,43 +887,9 @@ int movi_index_destroy(movi_index_t *ix) {
 
 }  // extern "C"
 
-// Top-of-walk table (DevIndex::kmer): 16 << 2K bytes, filled by one kernel; the call waits for it -- chunks of the
-// overlapped host path walk on other streams.
-static bool kmer_eligible(const movi_index *ix) {
-    return ix->kmode == MOVI_MODE_REGULAR_THRESHOLDS && ix->dev.sigma - ix->dev.sep == 4 && ix->desc.r >= 8;
-}
-static void drop_kmer(movi_index *ix) {
-    ix->dev.kmer_k = 0;
-    ix->dev.kmer = nullptr;
-    ix->d_kmer.reset();
-}
-static int build_kmer(movi_index *ix, uint32_t K, hipStream_t s) {
-    DevPtr<uint4> table;
-    HIP_TRY(dev_alloc(table, (size_t)16 << (2 * K)));
-    hipError_t e = build_kmer_table(ix->dev, K, table.get(), s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail_hip(e, "building the top-of-walk table");
-    ix->d_kmer = std::move(table);
-    ix->dev.kmer = ix->d_kmer.get();
-    ix->dev.kmer_k = K;
-    return MOVI_OK;
-}
+// ------------------------------------------------------------------ derived tables
+// Which tables exist when is decided in movi_derived.hpp; here is what its rules are handed: the facts of the handle, and the device.
 
-// Look-ahead rows (DevIndex::rows2): a second copy of the table, 16 bytes per row, built by itself by the first PML query
-// wherever the device has room for it.  History of the rule: round 3 built it up to 100 M rows only -- on a uniformly random
-// table, the worst case for it (the base after the LF fast-forwards more often than not), it was +14 % at 20 M rows, +8 % at
-// 100 M, -9 % at 200 M and -37 % at 1 B, where the two extra 16-byte loads per step cost more translation requests than the
-// skipped rows save (profiles/r03_ahead_rows_threshold.txt); round 4 first let the table's own statistic (share of positions
-// that arrive at their LF target without a fast-forward: 0.83 / 0.75 on real BWTs, 0.51 on random ones) extend it to 256 M
-// rows of real text (113 M rows: 42.3 -> 53.5 Gbases/s, profiles/r04_real_100M.txt).  The pair-shared gathers then removed
-// the translation cost the size rule was about (launch_pml: on for walked tables of 2 GB and more): on the look-ahead rows
-// the random table now runs 45.4 against 38.5 Gbases/s at 200 M rows, 43.4 / 36.3 at 350 M, 44.4 / 34.8 at 700 M and
-// 42.0 - 44.2 / 34.6 at 1 B (without the pairs: 21.4), the real 226 M-row BWT 50.8 / 38.6
-// (profiles/r04_pair_shared_gathers.txt) -- so the copy pays at every size measured, and only memory decides.
-// The statistic still steers the count query (kAheadCountRatio below) and is reported (movi_index_info "ahead_no_ff").
-static bool ahead_eligible(const movi_index *ix) {
-    return ix->kmode == MOVI_MODE_REGULAR_THRESHOLDS && ix->desc.r >= 8 && (ix->desc.r >> 36) == 0;
-}
 // A builder's tally: kTallySlots pairs of counters on the device (movi_kernels.hip: tally_add), added up here.
 constexpr size_t kTallyBytes = 2u * kTallySlots * sizeof(unsigned long long);
 static hipError_t read_tally(const unsigned long long *d_tally, unsigned long long (&sum)[2], hipStream_t s) {
@@ -899,150 +900,141 @@ static hipError_t read_tally(const unsigned long long *d_tally, unsigned long lo
     if (e == hipSuccess) for (uint32_t i = 0; i < kTallySlots; ++i) { sum[0] += h[2 * i]; sum[1] += h[2 * i + 1]; }
     return e;
 }
-// The statistic over a sample of the table's rows (every 16th), before anything is built.
-static void sample_no_ff(movi_index *ix, hipStream_t s) {
-    if (ix->ahead_tallied) return;
-    DevPtr<unsigned long long> tally;
-    unsigned long long h_tally[2] = {0, 0};
-    hipError_t e = dev_alloc(tally, kTallyBytes);
-    if (e == hipSuccess) e = hipMemsetAsync(tally.get(), 0, kTallyBytes, s);
-    if (e == hipSuccess) e = tally_no_ff_share(ix->kmode, ix->dev, 16, tally.get(), s);
-    if (e == hipSuccess) e = read_tally(tally.get(), h_tally, s);
-    if (e != hipSuccess) { (void)hipGetLastError(); return; }
-    ix->ahead_no_ff = h_tally[1] ? (double)h_tally[0] / (double)h_tally[1] : 0.0;
-    ix->ahead_tallied = true;
-}
-// Should the first query build the look-ahead rows by itself?  Yes, if they leave room for the query's own buffers.
-static bool ahead_wanted(movi_index *ix) {
-    const uint64_t bytes = ahead_rows_bytes(ix->desc.r);
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-    // (never more than a quarter of the device by itself: a handle's derived tables are the caller's HBM too -- "ahead_rows" 1
-    // builds them whatever their size, movi_index_info reports them)
-    return bytes <= total_b / 4 && free_b > bytes + std::max<uint64_t>(2ull << 30, bytes / 2);
-}
-// by_itself: built by the size policy, not on request -- then the count query uses the copy only where the table's own
-// statistic says it pays (DevIndex::rows2_count)
-constexpr double kAheadCountRatio = 0.67;
-static void drop_ahead(movi_index *ix) {
-    ix->dev.rows2 = nullptr;
-    ix->dev.rows2_tail = 0;
-    ix->dev.rows2_count = 0;
-    ix->dev.hints = 0;
-    ix->d_rows2.reset();
-}
-static int build_ahead(movi_index *ix, hipStream_t s, bool by_itself) {
-    DevPtr<uint8_t> rows2;
-    HIP_TRY(dev_alloc(rows2, ahead_rows_bytes(ix->desc.r)));
-    uint64_t tail = 0;
-    DevPtr<unsigned long long> tally;
-    unsigned long long h_tally[2] = {0, 0};
-    hipError_t e = dev_alloc(tally, kTallyBytes);
-    if (e == hipSuccess) e = hipMemsetAsync(tally.get(), 0, kTallyBytes, s);
-    if (e == hipSuccess) e = build_ahead_rows(ix->kmode, ix->dev, rows2.get(), &tail, s, tally.get());
-    if (e == hipSuccess) e = read_tally(tally.get(), h_tally, s);
-    if (e != hipSuccess) return fail_hip(e, "building the look-ahead rows");
-    ix->d_rows2 = std::move(rows2);
-    ix->dev.rows2 = ix->d_rows2.get();
-    ix->dev.rows2_tail = tail;
-    ix->dev.hints = ahead_rows_hinted(ix->desc.r) ? 1u : 0u;   // (the copy's ids are 32 bits wide and its spare bits hold reposition hints)
-    ix->ahead_no_ff = h_tally[1] ? (double)h_tally[0] / (double)h_tally[1] : 0.0;
-    ix->ahead_tallied = true;
-    ix->dev.rows2_count = (!by_itself || ix->ahead_no_ff >= kAheadCountRatio) ? 1u : 0u;
-    return MOVI_OK;
+
+static DerivedFacts derived_facts(const movi_index *ix) {
+    DerivedFacts f;
+    f.kmode = ix->kmode;
+    f.r = ix->desc.r;
+    f.dna = ix->dev.sigma - ix->dev.sep == 4;
+    f.count_variant = ix->cfg.count_variant;
+    f.ahead_bytes = ahead_rows_bytes(ix->desc.r);
+    f.deep_bytes = deep_rows_bytes(ix->desc.r);
+    for (int t = 0; t < kDerivedTables; t++) f.held[t] = ix->tables.held((DerivedTable)t);
+    return f;
 }
 
-// Deep rows (DevIndex::rows3; round 6): the PML walk's layout for tables of fewer than 2^28 - 1 rows -- 1.33 x the bytes of the look-ahead
-// rows for three bases per gather instead of two.  Built by itself up to kDeepAutoRows rows (the copy then stays within reach of the
-// Infinity Cache and the per-CU TLBs: profiles/r06_deep_rows.txt has the sizes measured), instead of the look-ahead rows, which the PML
-// walk no longer needs then; "deep_rows" 1 / 0 builds / frees them at any eligible size.
-constexpr uint64_t kDeepAutoRows = 48ull << 20;             // 50 M rows: a copy of 1 GiB
-// Width of a reposition hint in the deep rows ("deep_hint_bits" -1).  4 = narrow ids, reach 15: the builder looks up to 15 rows past
-// either edge of a window for each of a row's three slots instead of 3 (c2, 14 M rows: profiles/deep_hints.txt has the build time).
-constexpr int kDeepHintBitsDefault = 4;
-static bool deep_eligible(const movi_index *ix) {
-    return ix->kmode == MOVI_MODE_REGULAR_THRESHOLDS && deep_rows_eligible(ix->desc.r);
-}
-static void drop_deep(movi_index *ix) {
-    ix->dev.rows3 = nullptr;
-    ix->dev.deep_id_mask = ix->dev.deep_id_bits = ix->dev.deep_j3_shift = ix->dev.deep_hint_bits = 0;
-    ix->d_rows3.reset();
-}
-static int build_deep(movi_index *ix, hipStream_t s) {
-    DevPtr<uint8_t> rows3;
-    HIP_TRY(dev_alloc(rows3, deep_rows_bytes(ix->desc.r)));
-    const int want = ix->deep_hint_bits < 0 ? kDeepHintBitsDefault : ix->deep_hint_bits;
-    const DeepMap map = deep_map_for(ix->desc.r, want);      // (4 bits need narrow ids: tables of 2^26 rows and more keep wide ids and 2 bits)
-    hipError_t e = build_deep_rows(ix->kmode, ix->dev, (int)map.hint_bits, rows3.get(), s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail_hip(e, "building the deep rows");
-    ix->d_rows3 = std::move(rows3);
-    ix->dev.rows3 = ix->d_rows3.get();
-    ix->dev.deep_id_mask = map.id_mask;
-    ix->dev.deep_id_bits = map.id_bits;
-    ix->dev.deep_j3_shift = map.j3_shift;
-    ix->dev.deep_hint_bits = map.hint_bits;
-    return MOVI_OK;
-}
-
-// The count query's interval table (DevIndex::ftab): any DNA index, thresholds or not.
-static bool ftab_eligible(const movi_index *ix) {
-    return (ix->kmode == MOVI_MODE_REGULAR_THRESHOLDS || ix->kmode == MOVI_MODE_REGULAR) && ix->dev.sigma - ix->dev.sep == 4;
-}
-static void drop_ftab(movi_index *ix) {
-    ix->dev.ftab_k = 0;
-    ix->dev.ftab = nullptr;
-    ix->d_ftab.reset();
-}
-static int build_ftab_table(movi_index *ix, uint32_t K, hipStream_t s) {
-    DevPtr<uint4> table;
-    HIP_TRY(dev_alloc(table, (size_t)16 << (2 * K)));
-    hipError_t e = build_ftab(ix->kmode, ix->dev, K, table.get(), s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return fail_hip(e, "building the count query's interval table");
-    ix->d_ftab = std::move(table);
-    ix->dev.ftab = ix->d_ftab.get();
-    ix->dev.ftab_k = K;
-    return MOVI_OK;
-}
-
-// The derived tables of the PML walk -- top-of-walk table (256 MB at K = 12, a few ms), look-ahead rows (16 B per row) --:
-// built by movi_index_prepare, or by the first PML query on the handle.  Nothing here fails the query: a table there is no room
-// for (or a device in trouble, which the walk's own launch will report) is done without.
-static void ensure_pml_tables(movi_index *ix, hipStream_t s, bool from_prepare = false) {
-    if (ix->kmer_auto > 0 && !ix->d_kmer && kmer_eligible(ix)) {
-        if (build_kmer(ix, (uint32_t)ix->kmer_auto, s) != MOVI_OK) {
-            (void)hipGetLastError();
-            ix->kmer_auto = 0;
-        }
+// The device interface of movi_derived.hpp's rules on stream `s`: each builder allocates, launches, waits -- chunks of the overlapped host
+// path walk on other streams --, moves the table into the holder and publishes it; `facts.held` follows every build and drop.  A build
+// that fails leaves its message and code behind (rc) and the thread's last error cleared: the rules decide whether the caller hears of it.
+struct DerivedDev {
+    movi_index *ix;
+    hipStream_t s;
+    DerivedFacts &facts;
+    int rc = MOVI_OK;
+    bool failed(hipError_t e, const char *what) {
+        rc = fail_hip(e, what);
+        (void)hipGetLastError();
+        return false;
     }
-    // (after movi_index_prepare the header's promise holds: query calls allocate nothing and build nothing -- a copy that was declined
-    // for lack of memory is asked for again by the next explicit movi_index_prepare, never from inside a query, which may be under
-    // stream capture or in the middle of a streaming run)
-    if (ix->ahead_auto > 0 && !ix->d_rows2 && ahead_eligible(ix) && (from_prepare || !ix->prepared)) {
-        // (declined for lack of memory: the device is asked again after 64 calls, not in every one -- hipMemGetInfo per chunk of
-        // a streaming run -- and two processes sharing a GPU that both pass the check and then collide switch the auto-build off)
-        if (ix->ahead_retry_in > 0) ix->ahead_retry_in -= 1;
-        else if (!ahead_wanted(ix)) ix->ahead_retry_in = 63;
-        else if (build_ahead(ix, s, true) != MOVI_OK) {
-            (void)hipGetLastError();
-            ix->ahead_auto = 0;
-        }
+    bool published() {
+        ix->tables.publish(ix->dev);
+        for (int t = 0; t < kDerivedTables; t++) facts.held[t] = ix->tables.held((DerivedTable)t);
+        return true;
     }
-    // The deep rows, beside the look-ahead rows (batches of short reads walk on the one, long reads on the other: launch_pml): tables of up
-    // to kDeepAutoRows rows whose positions mostly reach their LF target without a fast-forward -- real text: the builder of the
-    // look-ahead rows has tallied it, else a sample does -- three bases per gather need two such arrivals in a row (uniformly random
-    // run sequences, 0.51: 62.4 -> 61.2 Gbases/s; the pangenome BWT, 0.83: 80.3 -> 89.6 with reset masks out)
-    if (ix->deep_auto > 0 && !ix->d_rows3 && deep_eligible(ix) && ix->desc.r <= kDeepAutoRows && (from_prepare || !ix->prepared)) {
-        if (!ix->ahead_tallied) sample_no_ff(ix, s);
-        size_t free_b = 0, total_b = 0;
-        const uint64_t bytes = deep_rows_bytes(ix->desc.r);
-        if (ix->ahead_tallied && ix->ahead_no_ff < kAheadCountRatio) {
-            ix->deep_auto = 0;                                 // (the table's own statistic declines, for good)
-        } else if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < bytes + (2ull << 30) || build_deep(ix, s) != MOVI_OK) {
-            (void)hipGetLastError();
-            ix->deep_auto = 0;                                 // (no room, or a device in trouble: the walk stays on the look-ahead rows)
-        }
+    bool mem_info(uint64_t &free_b, uint64_t &total_b) {
+        size_t f = 0, t = 0;
+        if (hipMemGetInfo(&f, &t) != hipSuccess) { (void)hipGetLastError(); return false; }
+        free_b = f; total_b = t;
+        return true;
+    }
+    // The statistic over a sample of the table's rows (every 16th), before anything is built.
+    bool sample_no_ff(double &share) {
+        DevPtr<unsigned long long> tally;
+        unsigned long long h_tally[2] = {0, 0};
+        hipError_t e = dev_alloc(tally, kTallyBytes);
+        if (e == hipSuccess) e = hipMemsetAsync(tally.get(), 0, kTallyBytes, s);
+        if (e == hipSuccess) e = tally_no_ff_share(ix->kmode, ix->dev, 16, tally.get(), s);
+        if (e == hipSuccess) e = read_tally(tally.get(), h_tally, s);
+        if (e != hipSuccess) { (void)hipGetLastError(); return false; }
+        share = h_tally[1] ? (double)h_tally[0] / (double)h_tally[1] : 0.0;
+        return true;
+    }
+    bool build_kmer(uint32_t K) {
+        DevPtr<uint4> table;
+        hipError_t e = dev_alloc(table, DerivedTables::bytes(kTabKmer, ix->desc.r, K));
+        if (e == hipSuccess) e = build_kmer_table(ix->dev, K, table.get(), s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return failed(e, "building the top-of-walk table");
+        ix->tables.kmer = std::move(table);
+        ix->tables.kmer_k = K;
+        return published();
+    }
+    bool build_ftab(uint32_t K) {
+        DevPtr<uint4> table;
+        hipError_t e = dev_alloc(table, DerivedTables::bytes(kTabFtab, ix->desc.r, K));
+        if (e == hipSuccess) e = movi::build_ftab(ix->kmode, ix->dev, K, table.get(), s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return failed(e, "building the count query's interval table");
+        ix->tables.ftab = std::move(table);
+        ix->tables.ftab_k = K;
+        return published();
+    }
+    bool build_ckpt() {
+        DevPtr<uint64_t> ckpt;
+        hipError_t e = dev_alloc(ckpt, DerivedTables::bytes(kTabCkpt, ix->desc.r, 0));
+        if (e == hipSuccess) e = build_row_start_ckpt(ix->kmode, ix->d_rows.get(), ix->desc.r, ckpt.get(), s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);        // other streams (the overlapped host path) may use it next
+        if (e != hipSuccess) return failed(e, "building the row-start checkpoints");
+        ix->tables.ckpt = std::move(ckpt);
+        return published();
+    }
+    // hint_bits: 2 or 4, as deep_map_for gives it for this table (deep_hint_width)
+    bool build_deep(int hint_bits) {
+        DevPtr<uint8_t> rows3;
+        hipError_t e = dev_alloc(rows3, DerivedTables::bytes(kTabDeep, ix->desc.r, 0));
+        if (e == hipSuccess) e = build_deep_rows(ix->kmode, ix->dev, hint_bits, rows3.get(), s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return failed(e, "building the deep rows");
+        ix->tables.rows3 = std::move(rows3);
+        ix->tables.deep = deep_map_for(ix->desc.r, hint_bits);
+        return published();
+    }
+    // share: the builder's tally over every row; serves_count: what the copy publishes as DevIndex::rows2_count
+    bool build_ahead(bool by_itself, double &share, bool &serves_count) {
+        DevPtr<uint8_t> rows2;
+        hipError_t e = dev_alloc(rows2, DerivedTables::bytes(kTabAhead, ix->desc.r, 0));
+        uint64_t tail = 0;
+        DevPtr<unsigned long long> tally;
+        unsigned long long h_tally[2] = {0, 0};
+        if (e == hipSuccess) e = dev_alloc(tally, kTallyBytes);
+        if (e == hipSuccess) e = hipMemsetAsync(tally.get(), 0, kTallyBytes, s);
+        if (e == hipSuccess) e = build_ahead_rows(ix->kmode, ix->dev, rows2.get(), &tail, s, tally.get());
+        if (e == hipSuccess) e = read_tally(tally.get(), h_tally, s);
+        if (e != hipSuccess) return failed(e, "building the look-ahead rows");
+        share = h_tally[1] ? (double)h_tally[0] / (double)h_tally[1] : 0.0;
+        serves_count = ahead_serves_count(by_itself, share);
+        ix->tables.rows2 = std::move(rows2);
+        ix->tables.rows2_tail = tail;
+        ix->tables.hints = ahead_rows_hinted(ix->desc.r) ? 1u : 0u;   // (the copy's ids are 32 bits wide and its spare bits hold reposition hints)
+        ix->tables.rows2_count = serves_count ? 1u : 0u;
+        return published();
+    }
+    void drop(DerivedTable which) {
+        ix->tables.reset(which);
+        published();
+    }
+};
+
+static void pml_tables(movi_index *ix, hipStream_t s, bool from_prepare = false) {
+    DerivedFacts f = derived_facts(ix);
+    DerivedDev dev{ix, s, f};
+    ensure_pml_tables(ix->policy, f, dev, from_prepare);
+}
+static int count_tables(movi_index *ix, hipStream_t s, bool from_prepare = false) {
+    DerivedFacts f = derived_facts(ix);
+    DerivedDev dev{ix, s, f};
+    return ensure_count_tables(ix->policy, f, dev, from_prepare) ? MOVI_OK : dev.rc;
+}
+// The four build-now options behind their range checks; `refusal`: what an ineligible index is told
+static int request_derived(movi_index *ix, DerivedTable which, int64_t value, const char *refusal) {
+    HIP_TRY(hipSetDevice(ix->device));
+    HIP_TRY(hipDeviceSynchronize());                         // no walk may be reading the table that goes away
+    DerivedFacts f = derived_facts(ix);
+    DerivedDev dev{ix, nullptr, f};
+    switch (request_table(ix->policy, f, dev, which, (uint32_t)value)) {
+    case TableRequest::kIneligible: return fail(MOVI_ERR_ARG, refusal);
+    case TableRequest::kBuildFailed: return dev.rc;
+    default: return MOVI_OK;
     }
 }
 
@@ -1248,40 +1240,19 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
     }
     if (!strcmp(key, "kmer_k")) {                            // top-of-walk table: 0 = none, K in [1, 12] = build it now
         if (value < 0 || value > 12) return fail(MOVI_ERR_ARG, "kmer_k must be in [0, 12]");
-        HIP_TRY(hipSetDevice(ix->device));
-        HIP_TRY(hipDeviceSynchronize());                     // no walk may be reading the table that goes away
-        drop_kmer(ix);
-        ix->kmer_auto = 0;                                   // the caller's choice from here on
-        if (value == 0) return MOVI_OK;
-        if (!kmer_eligible(ix))
-            return fail(MOVI_ERR_ARG, "the top-of-walk table serves PML walks on DNA (ACGT) *-thresholds indexes only");
-        return build_kmer(ix, (uint32_t)value, nullptr);
+        return request_derived(ix, kTabKmer, value, "the top-of-walk table serves PML walks on DNA (ACGT) *-thresholds indexes only");
     }
     if (!strcmp(key, "ahead_rows")) {                        // look-ahead rows: 0 = none (freed), 1 = build them now
         if (value < 0 || value > 1) return fail(MOVI_ERR_ARG, "ahead_rows must be 0 or 1");
-        HIP_TRY(hipSetDevice(ix->device));
-        HIP_TRY(hipDeviceSynchronize());                     // no walk may be reading the copy that goes away
-        drop_ahead(ix);
-        ix->ahead_auto = 0;                                  // the caller's choice from here on ...
-        drop_deep(ix);                                       // ... and it is about what the PML walk runs on: the deep rows, which would take precedence
-        ix->deep_auto = 0;                                   // over either answer, go (and are not built by themselves any more; "deep_rows" 1 brings them back)
-        if (value == 0) return MOVI_OK;
-        if (!ahead_eligible(ix)) return fail(MOVI_ERR_ARG, "look-ahead rows serve PML walks on *-thresholds indexes only");
-        return build_ahead(ix, nullptr, false);
+        return request_derived(ix, kTabAhead, value, "look-ahead rows serve PML walks on *-thresholds indexes only");   // (the deep rows go with them)
     }
     if (!strcmp(key, "deep_rows")) {                         // deep rows: 0 = none (freed), 1 = build them now
         if (value < 0 || value > 1) return fail(MOVI_ERR_ARG, "deep_rows must be 0 or 1");
-        HIP_TRY(hipSetDevice(ix->device));
-        HIP_TRY(hipDeviceSynchronize());                     // no walk may be reading the copy that goes away
-        drop_deep(ix);
-        ix->deep_auto = 0;                                   // the caller's choice from here on
-        if (value == 0) return MOVI_OK;
-        if (!deep_eligible(ix)) return fail(MOVI_ERR_ARG, "deep rows serve PML walks on *-thresholds indexes of fewer than 2^28 - 1 rows only");
-        return build_deep(ix, nullptr);
+        return request_derived(ix, kTabDeep, value, "deep rows serve PML walks on *-thresholds indexes of fewer than 2^28 - 1 rows only");
     }
     if (!strcmp(key, "deep_hint_bits")) {                    // width of a deep row's reposition hints: -1 = the default, 2 (reach 3, wide ids) or 4 (reach 15, narrow ids); takes effect when the deep rows are next built (A/B)
         if (value != -1 && value != 2 && value != 4) return fail(MOVI_ERR_ARG, "deep_hint_bits must be -1, 2 or 4");
-        ix->deep_hint_bits = (int)value;
+        ix->policy.deep_hint_bits = (int)value;
         return MOVI_OK;
     }
     if (!strcmp(key, "deep")) {                              // the walk on the deep rows the handle holds: -1 = batches of short reads, 0 never, 1 always (A/B)
@@ -1291,13 +1262,7 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
     }
     if (!strcmp(key, "ftab_k")) {                            // count query's interval table: 0 = none, K in [1, 12] = build it now
         if (value < 0 || value > 12) return fail(MOVI_ERR_ARG, "ftab_k must be in [0, 12]");
-        HIP_TRY(hipSetDevice(ix->device));
-        HIP_TRY(hipDeviceSynchronize());
-        drop_ftab(ix);
-        ix->ftab_auto = 0;
-        if (value == 0) return MOVI_OK;
-        if (!ftab_eligible(ix)) return fail(MOVI_ERR_ARG, "the count query's interval table serves DNA (ACGT) indexes only");
-        return build_ftab_table(ix, (uint32_t)value, nullptr);
+        return request_derived(ix, kTabFtab, value, "the count query's interval table serves DNA (ACGT) indexes only");
     }
     if (!strcmp(key, "kmer_lookahead")) {                    // k-mer query: -1 = by k and the text's length, 0 = no look-ahead, n in [2, 16] = split k / n
         if (value != 0 && value != -1 && (value < 2 || value > 16)) return fail(MOVI_ERR_ARG, "kmer_lookahead must be -1, 0 or in [2, 16]");
@@ -1375,7 +1340,7 @@ static int pml_call(movi_index_t *ix, const MlRequest &r) {
     if (int rc = ml_begin(ix, r.n_reads, c.stats, r.stream, &no_alloc)) return rc;
     // the first PML query on a handle builds its derived tables -- unless movi_index_prepare did (--logs runs on the first kernel, which
     // uses none of them)
-    if (r.cls.log_ff == nullptr) ensure_pml_tables(ix, r.stream);
+    if (r.cls.log_ff == nullptr) pml_tables(ix, r.stream);
     // what the caller wants: masks, or the vector -- with mask words lent where there is a vector to write, the option allows it and, under
     // a capture, the handle's words hold the batch already
     const size_t lent_bytes = (size_t)pml_mask_words(r.n_reads, r.n_bases, 0) * 4;
@@ -1484,11 +1449,10 @@ int movi_launch_log(char *buf, size_t cap, size_t *needed) {
 int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     if (!ix || !key || !value) return fail(MOVI_ERR_ARG, "NULL argument");
     const double rows = ix->kmode != (int)ix->desc.mode ? (double)ix->desc.r * 8.0 : (double)ix->rows_bytes;
-    const double kmer = ix->d_kmer ? (double)((size_t)16 << (2 * ix->dev.kmer_k)) : 0.0;
-    const double ftab = ix->d_ftab ? (double)((size_t)16 << (2 * ix->dev.ftab_k)) : 0.0;
-    const double ahead = ix->d_rows2 ? (double)ahead_rows_bytes(ix->desc.r) : 0.0;
-    const double deep = ix->d_rows3 ? (double)deep_rows_bytes(ix->desc.r) : 0.0;
-    const double ckpt = ix->d_ckpt ? (double)((ix->desc.r >> kPrefixShift) + 2) * 8.0 : 0.0;
+    const DerivedTables &tab = ix->tables;
+    const double kmer = tab.held_bytes(kTabKmer, ix->desc.r), ftab = tab.held_bytes(kTabFtab, ix->desc.r);
+    const double ahead = tab.held_bytes(kTabAhead, ix->desc.r), deep = tab.held_bytes(kTabDeep, ix->desc.r);
+    const double ckpt = tab.ckpt_bytes_reported(ix->desc.r);
     const double locate = ix->sa_rate ? (double)locate_rows_bytes(ix->desc.r) + (double)(ix->desc.length / ix->sa_rate + 1) * 8.0 : 0.0;
     const double color = ix->d_color_inds ? (double)ix->color_flat.size() * 2.0 + (double)ix->color_inds.size() * 8.0 : 0.0;
     if (!strcmp(key, "rows_bytes")) *value = rows;
@@ -1497,7 +1461,7 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     else if (!strcmp(key, "ftab_bytes")) *value = ftab;
     else if (!strcmp(key, "ahead_rows_bytes")) *value = ahead;
     else if (!strcmp(key, "deep_rows_bytes")) *value = deep;
-    else if (!strcmp(key, "deep_hint_bits")) *value = ix->d_rows3 ? (double)ix->dev.deep_hint_bits : 0.0;   // width of a hint in the deep rows the handle holds (0 = it holds none)
+    else if (!strcmp(key, "deep_hint_bits")) *value = tab.rows3 ? (double)tab.deep.hint_bits : 0.0;   // width of a hint in the deep rows the handle holds (0 = it holds none)
     else if (!strcmp(key, "ckpt_bytes")) *value = ckpt;
     else if (!strcmp(key, "color_bytes")) *value = color;
     else if (!strcmp(key, "color_taxa")) *value = (double)ix->color_taxa.size();      // to_taxon_id entries held (0 after a load)
@@ -1506,7 +1470,7 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     else if (!strcmp(key, "color_sort_seconds")) *value = ix->color_seconds[1];
     else if (!strcmp(key, "color_number_seconds")) *value = ix->color_seconds[2];
     else if (!strcmp(key, "derived_bytes")) *value = kmer + ftab + ahead + deep + ckpt + locate + color;
-    else if (!strcmp(key, "ahead_no_ff")) *value = ix->ahead_tallied ? ix->ahead_no_ff : -1.0;
+    else if (!strcmp(key, "ahead_no_ff")) *value = ix->policy.ahead_tallied ? ix->policy.ahead_no_ff : -1.0;
     else if (!strcmp(key, "device_scratch_bytes")) {         // device scratch the *_device calls hold: mask words (retired ones too), vector, segment workspace
         *value = (double)ix->dmask.held_bytes() + (double)ix->dpark.cap() + (double)ix->scratch[movi_index::kTmp].cap() + (double)ix->seg_ws.cap() +
                  (double)ix->color_scratch.cap();      // (held_bytes: the live words and the handle's retired blocks, queues among them)
@@ -2462,49 +2426,6 @@ int movi_pml_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uint6
 
 // -------------------------------------------------------------------------- count
 
-static int ensure_ckpt(movi_index *ix, hipStream_t s) {
-    if (ix->d_ckpt) return MOVI_OK;
-    const uint64_t n_chunks = (ix->desc.r + (1ull << kPrefixShift) - 1) >> kPrefixShift;
-    DevPtr<uint64_t> ckpt;
-    HIP_TRY(dev_alloc(ckpt, (n_chunks + 1) * sizeof(uint64_t)));
-    hipError_t e = build_row_start_ckpt(ix->kmode, ix->d_rows.get(), ix->desc.r, ckpt.get(), s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);        // other streams (the overlapped host path) may use it next
-    if (e != hipSuccess) return fail_hip(e, "building the row-start checkpoints");
-    ix->d_ckpt = std::move(ckpt);
-    ix->dev.row_start_ckpt = ix->d_ckpt.get();
-    return MOVI_OK;
-}
-
-// The derived tables of the count query -- row-start checkpoints, interval table, and the look-ahead rows where the table's own
-// statistic says the search will use them --: built by movi_index_prepare, or by the first count query on the handle.
-static int ensure_count_tables(movi_index *ix, hipStream_t s, bool from_prepare = false) {
-    int rc = ensure_ckpt(ix, s);
-    if (rc) return rc;
-    if (ix->ftab_auto > 0 && !ix->d_ftab && ftab_eligible(ix)) {       // the interval table (256 MB at K = 12)
-        if (build_ftab_table(ix, (uint32_t)ix->ftab_auto, s) != MOVI_OK) { (void)hipGetLastError(); ix->ftab_auto = 0; }
-    }
-    // (round 5: the count query's default is the lane state machine on the PLAIN rows, launch_count; the look-ahead copy serves
-    // count_kernel_v0 only, i.e. "count_variant" 0)
-    if (ix->cfg.count_variant == 0 && ix->ahead_auto > 0 && !ix->d_rows2 && !ix->count_declined_ahead && ahead_eligible(ix) &&
-        (from_prepare || !ix->prepared)) {
-        // sampled first, so that a table that will not use the copy is not copied (16 B per row) to find out.  Only the table's
-        // statistic declines for good; a device short of memory is asked again later (ahead_retry_in).
-        sample_no_ff(ix, s);
-        if (!ix->ahead_tallied) { /* the sample failed: the next call tries again */ }
-        else if (ix->ahead_no_ff < kAheadCountRatio) ix->count_declined_ahead = true;
-        else if (ix->ahead_retry_in > 0) ix->ahead_retry_in -= 1;
-        else if (!ahead_wanted(ix)) ix->ahead_retry_in = 63;
-        else if (build_ahead(ix, s, true) != MOVI_OK) { (void)hipGetLastError(); ix->ahead_auto = 0; }
-        else if (ix->dev.rows2_count == 0u) {
-            // (the copy's own tally -- every row, not a sample -- says the count query is better off on the plain rows: the copy
-            // is not kept for a caller who may never ask for PMLs; the first PML query builds it again, 85 us per 14 M rows)
-            drop_ahead(ix);
-            ix->count_declined_ahead = true;
-        }
-    }
-    return MOVI_OK;
-}
-
 static int count_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
                         uint64_t n_bases, uint64_t *d_matched, uint64_t *d_count, uint8_t *d_read_err,
                         const uint32_t *d_read_order, void *stream, DevStats *d_stats) {
@@ -2514,7 +2435,7 @@ static int count_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t
     if (!d_stats) d_stats = ix->d_stats.get();
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = ensure_count_tables(ix, s);
+    int rc = count_tables(ix, s);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(DevStats), s));
     if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
@@ -2538,9 +2459,9 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
     if ((what & MOVI_PREPARE_COLOR) && !ix->d_color_inds) return fail(MOVI_ERR_ARG, kNoColor);
     HIP_TRY(hipSetDevice(ix->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    ix->ahead_retry_in = 0;                                           // an explicit call asks the device now
+    on_prepare(ix->policy);                                           // an explicit call asks the device now
     if ((what & MOVI_PREPARE_PML) && mode_has_thresholds(ix->desc.mode)) {
-        ensure_pml_tables(ix, s, true);
+        pml_tables(ix, s, true);
         // the walk kernels live in translation units of their own: their code objects are loaded here, not by the first walk
         (void)(ix->dev.idx32 ? preload_walk_u32() : preload_walk_u64());
         (void)(ix->dev.idx32 ? preload_walkseg_u32() : preload_walkseg_u64());
@@ -2553,7 +2474,7 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
         if (park_lanes_wanted(ix) > 0 && grow(ix->dpark, park_queue_bytes(kPrepareMaskReads, park_lanes_wanted(ix))) != hipSuccess) (void)hipGetLastError();
     }
     if (what & MOVI_PREPARE_COUNT) {
-        const int rc = ensure_count_tables(ix, s, true);
+        const int rc = count_tables(ix, s, true);
         if (rc) return rc;
     }
     if (what & MOVI_PREPARE_SA) {
@@ -2567,7 +2488,7 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
         (void)preload_color(ix->kmode, ix->dev.idx32 != 0);
         (void)hipGetLastError();
     }
-    ix->prepared = true;
+    on_prepared(ix->policy);
     // (MOVI_PREPARE_ZML: the parse walks on the plain rows and derives nothing -- accepted so that callers need not know)
     HIP_TRY(hipStreamSynchronize(s));
     if (derived_bytes) {
@@ -2636,7 +2557,7 @@ int mem_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_offsets
     if (!d_offsets || !d_n_mems || (n_bases && (!d_bases || !d_mems))) return fail(MOVI_ERR_ARG, "NULL device buffer");
     if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
     HIP_TRY(hipSetDevice(ix->device));
-    int rc = ensure_count_tables(ix, s);
+    int rc = count_tables(ix, s);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(ix->d_stats.get(), 0, sizeof(DevStats), s));
     MemArgs a{};
@@ -2705,7 +2626,7 @@ int kmer_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_offset
     if (!d_offsets || !d_n_runs || (n_bases && (!d_bases || !d_runs))) return fail(MOVI_ERR_ARG, "NULL device buffer");
     if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
     HIP_TRY(hipSetDevice(ix->device));
-    int rc = ensure_count_tables(ix, s);
+    int rc = count_tables(ix, s);
     if (rc) return rc;
     HIP_TRY(hipMemsetAsync(ix->d_stats.get(), 0, sizeof(DevStats), s));
     KmerArgs a{};
