@@ -269,7 +269,7 @@ typedef struct movi_launch_info {
     int32_t idx64;                    /* 1 = the 64-bit row-index instantiation                                     */
     int32_t staged;                   /* > 0: every lane keeps the next `staged` bases of its read in LDS ("stage_reads";
                                          336 at the default occupancy cap, 256 on the look-ahead rows); 0: no staging */
-    int32_t ahead;                    /* 1 = the walk ran on the look-ahead rows ("ahead_rows") */
+    int32_t ahead;                    /* 1 = the walk ran on the look-ahead rows ("ahead_rows"), 2 = on the deep rows ("deep_rows"), 3 = on the chain rows ("chain_rows") */
     int32_t reserved_;
 } movi_launch_info_t;
 int movi_last_launch(const movi_index_t *ix, movi_launch_info_t *info);
@@ -807,6 +807,14 @@ int movi_host_unregister(void *p);
  * for the mask words of movi_pml_device calls of up to this many bases, reserved now instead of inside the first such call; grow-only,
  * beside what movi_index_prepare reserves),
  * "host_threads" (worker threads of the host-side expansion, 0 = three quarters of the CPUs the process may use -- affinity mask capped by the cgroup's quota --, at most 24),
+ * "chain_rows" (a fourth layout of the table for the PML walk of short reads -- 32 bytes per row, windows of two rows, every row with
+ * what the walk reads at its next THREE LF targets: up to four bases per gather, in a kernel of its own name, pml_kernel_chain;
+ * movi_last_launch "ahead" 3.  -1, the default: the first PML query (or movi_index_prepare) builds them BESIDE the deep rows -- which
+ * long reads and segment plans keep walking on -- where the deep rows' own conditions hold, the table has at least 12 Mi rows, its
+ * share of positions that reach their LF target without a fast-forward ("ahead_no_ff") is at least 0.80 and the device has room for
+ * them and 2 GiB more; 1 = build now (thresholds types of fewer than 2^28 - 1 rows, else refused), 0 = none (freed).  "ahead_rows"
+ * 0 / 1 frees them too.  movi_index_info "chain_rows_bytes" = ((r + 1) / 2) * 64 where the handle holds them, counted in
+ * "derived_bytes".  Same vectors, mask words, error bytes and counters as on every other layout: profiles/chain_rows.txt),
  * "deep_rows" (round 6: a third layout of the table for the PML walk of short reads -- 21.33 bytes per row, windows of three rows, every
  * row with what the walk reads at its LF target AND at that row's target: up to three bases per gather.  Left alone, the first PML query
  * (or movi_index_prepare) builds them, beside the look-ahead rows, for tables of at most 50 M rows whose positions mostly reach their LF

@@ -96,12 +96,13 @@ struct DerivedTables {
     DevPtr<uint8_t> rows2;           // look-ahead rows ("ahead_rows" option), 16 bytes per row
     DevPtr<uint8_t> rows3;           // deep rows ("deep_rows" option), 21.33 bytes per row: what the PML walk runs on where the policy builds them
     DevPtr<uint64_t> ckpt;           // row-start checkpoints: built lazily by the first count query
+    DevPtr<uint8_t> rows4;           // chain rows ("chain_rows" option), 32 bytes per row: pml_kernel_chain walks on them (the kernels' view has no field for them: PmlCall::chain_rows)
     uint32_t kmer_k = 0, ftab_k = 0;
     uint64_t rows2_tail = 0;
     uint32_t rows2_count = 0, hints = 0;
     DeepMap deep{0, 0, 0, 0};        // the field map rows3 was built in
     bool held(DerivedTable t) const {
-        return t == kTabKmer ? (bool)kmer : t == kTabFtab ? (bool)ftab : t == kTabAhead ? (bool)rows2 : t == kTabDeep ? (bool)rows3 : (bool)ckpt;
+        return t == kTabChain ? (bool)rows4 : t == kTabKmer ? (bool)kmer : t == kTabFtab ? (bool)ftab : t == kTabAhead ? (bool)rows2 : t == kTabDeep ? (bool)rows3 : (bool)ckpt;
     }
     void reset(DerivedTable t) {
         switch (t) {
@@ -109,6 +110,7 @@ struct DerivedTables {
         case kTabFtab: ftab.reset(); ftab_k = 0; break;
         case kTabAhead: rows2.reset(); rows2_tail = 0; rows2_count = hints = 0; break;
         case kTabDeep: rows3.reset(); deep = DeepMap{0, 0, 0, 0}; break;
+        case kTabChain: rows4.reset(); break;
         default: ckpt.reset(); break;
         }
     }
@@ -126,6 +128,7 @@ struct DerivedTables {
         case kTabKmer: case kTabFtab: return (size_t)16 << (2 * K);
         case kTabAhead: return ahead_rows_bytes(r);
         case kTabDeep: return deep_rows_bytes(r);
+        case kTabChain: return chain_rows_bytes(r);
         default: return (((r + (1ull << kPrefixShift) - 1) >> kPrefixShift) + 1) * sizeof(uint64_t);   // ceil(r / 32) + 1 entries
         }
     }
@@ -909,6 +912,7 @@ static DerivedFacts derived_facts(const movi_index *ix) {
     f.count_variant = ix->cfg.count_variant;
     f.ahead_bytes = ahead_rows_bytes(ix->desc.r);
     f.deep_bytes = deep_rows_bytes(ix->desc.r);
+    f.chain_bytes = chain_rows_bytes(ix->desc.r);
     for (int t = 0; t < kDerivedTables; t++) f.held[t] = ix->tables.held((DerivedTable)t);
     return f;
 }
@@ -989,6 +993,15 @@ struct DerivedDev {
         ix->tables.deep = deep_map_for(ix->desc.r, hint_bits);
         return published();
     }
+    bool build_chain() {
+        DevPtr<uint8_t> rows4;
+        hipError_t e = dev_alloc(rows4, DerivedTables::bytes(kTabChain, ix->desc.r, 0));
+        if (e == hipSuccess) e = build_chain_rows(ix->kmode, ix->dev, rows4.get(), s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) return failed(e, "building the chain rows");
+        ix->tables.rows4 = std::move(rows4);
+        return published();
+    }
     // share: the builder's tally over every row; serves_count: what the copy publishes as DevIndex::rows2_count
     bool build_ahead(bool by_itself, double &share, bool &serves_count) {
         DevPtr<uint8_t> rows2;
@@ -1019,6 +1032,7 @@ static void pml_tables(movi_index *ix, hipStream_t s, bool from_prepare = false)
     DerivedFacts f = derived_facts(ix);
     DerivedDev dev{ix, s, f};
     ensure_pml_tables(ix->policy, f, dev, from_prepare);
+    ensure_chain_rows(ix->policy, f, dev, from_prepare);     // (beside the deep rows, from the tally the rules above have taken)
 }
 static int count_tables(movi_index *ix, hipStream_t s, bool from_prepare = false) {
     DerivedFacts f = derived_facts(ix);
@@ -1244,11 +1258,31 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
     }
     if (!strcmp(key, "ahead_rows")) {                        // look-ahead rows: 0 = none (freed), 1 = build them now
         if (value < 0 || value > 1) return fail(MOVI_ERR_ARG, "ahead_rows must be 0 or 1");
+        if (ix->tables.rows4 || ix->policy.chain_auto > 0) {     // a statement about what the PML walk runs on: the chain rows go like the deep rows, and come back on request only
+            HIP_TRY(hipSetDevice(ix->device));
+            HIP_TRY(hipDeviceSynchronize());
+            DerivedFacts f = derived_facts(ix);
+            DerivedDev dev{ix, nullptr, f};
+            (void)request_chain(ix->policy, f, dev, 0);
+        }
         return request_derived(ix, kTabAhead, value, "look-ahead rows serve PML walks on *-thresholds indexes only");   // (the deep rows go with them)
     }
     if (!strcmp(key, "deep_rows")) {                         // deep rows: 0 = none (freed), 1 = build them now
         if (value < 0 || value > 1) return fail(MOVI_ERR_ARG, "deep_rows must be 0 or 1");
         return request_derived(ix, kTabDeep, value, "deep rows serve PML walks on *-thresholds indexes of fewer than 2^28 - 1 rows only");
+    }
+    if (!strcmp(key, "chain_rows")) {                        // chain rows: -1 = the policy's own rule again (ensure_chain_rows), 0 = none (freed), 1 = build them now
+        if (value < -1 || value > 1) return fail(MOVI_ERR_ARG, "chain_rows must be -1, 0 or 1");
+        if (value < 0) { ix->policy.chain_auto = 1; return MOVI_OK; }
+        HIP_TRY(hipSetDevice(ix->device));
+        HIP_TRY(hipDeviceSynchronize());                     // no walk may be reading the table that goes away
+        DerivedFacts f = derived_facts(ix);
+        DerivedDev dev{ix, nullptr, f};
+        switch (request_chain(ix->policy, f, dev, (uint32_t)value)) {
+        case TableRequest::kIneligible: return fail(MOVI_ERR_ARG, "chain rows serve PML walks on *-thresholds indexes of fewer than 2^28 - 1 rows only");
+        case TableRequest::kBuildFailed: return dev.rc;
+        default: return MOVI_OK;
+        }
     }
     if (!strcmp(key, "deep_hint_bits")) {                    // width of a deep row's reposition hints: -1 = the default, 2 (reach 3, wide ids) or 4 (reach 15, narrow ids); takes effect when the deep rows are next built (A/B)
         if (value != -1 && value != 2 && value != 4) return fail(MOVI_ERR_ARG, "deep_hint_bits must be -1, 2 or 4");
@@ -1350,7 +1384,8 @@ static int pml_call(movi_index_t *ix, const MlRequest &r) {
     PmlAsk ask = pml_ask(c, masks ? PmlWant::kMasks : lends ? PmlWant::kVectorLendsMasks : PmlWant::kVector, ix->pml_via_mask);
     ask.park_cap = r.chunk ? 0 : park_queue_offer(ix, r.n_reads, no_alloc);
     ask.park_queue = ask.park_cap > 0;
-    PmlRoute route = plan_pml(facts(ix->dev), ix->cfg, r.n_reads, r.n_bases, ask);
+    c.chain_rows = ix->tables.rows4.get();
+    PmlRoute route = plan_pml(facts(ix->dev, c.chain_rows != nullptr), ix->cfg, r.n_reads, r.n_bases, ask);
     if (route.lent_masks()) {
         HIP_TRY(r.chunk ? grow(r.chunk[movi_index::kMask], lent_bytes) : grow(ix->dmask, lent_bytes));
         if (!r.chunk && no_alloc) ix->dmask.mark_in_graph();
@@ -1452,7 +1487,7 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     const DerivedTables &tab = ix->tables;
     const double kmer = tab.held_bytes(kTabKmer, ix->desc.r), ftab = tab.held_bytes(kTabFtab, ix->desc.r);
     const double ahead = tab.held_bytes(kTabAhead, ix->desc.r), deep = tab.held_bytes(kTabDeep, ix->desc.r);
-    const double ckpt = tab.ckpt_bytes_reported(ix->desc.r);
+    const double ckpt = tab.ckpt_bytes_reported(ix->desc.r), chain = tab.held_bytes(kTabChain, ix->desc.r);
     const double locate = ix->sa_rate ? (double)locate_rows_bytes(ix->desc.r) + (double)(ix->desc.length / ix->sa_rate + 1) * 8.0 : 0.0;
     const double color = ix->d_color_inds ? (double)ix->color_flat.size() * 2.0 + (double)ix->color_inds.size() * 8.0 : 0.0;
     if (!strcmp(key, "rows_bytes")) *value = rows;
@@ -1461,6 +1496,7 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     else if (!strcmp(key, "ftab_bytes")) *value = ftab;
     else if (!strcmp(key, "ahead_rows_bytes")) *value = ahead;
     else if (!strcmp(key, "deep_rows_bytes")) *value = deep;
+    else if (!strcmp(key, "chain_rows_bytes")) *value = chain;
     else if (!strcmp(key, "deep_hint_bits")) *value = tab.rows3 ? (double)tab.deep.hint_bits : 0.0;   // width of a hint in the deep rows the handle holds (0 = it holds none)
     else if (!strcmp(key, "ckpt_bytes")) *value = ckpt;
     else if (!strcmp(key, "color_bytes")) *value = color;
@@ -1469,7 +1505,7 @@ int movi_index_info(const movi_index_t *ix, const char *key, double *value) {
     else if (!strcmp(key, "color_walk_seconds")) *value = ix->color_seconds[0];
     else if (!strcmp(key, "color_sort_seconds")) *value = ix->color_seconds[1];
     else if (!strcmp(key, "color_number_seconds")) *value = ix->color_seconds[2];
-    else if (!strcmp(key, "derived_bytes")) *value = kmer + ftab + ahead + deep + ckpt + locate + color;
+    else if (!strcmp(key, "derived_bytes")) *value = kmer + ftab + ahead + deep + chain + ckpt + locate + color;
     else if (!strcmp(key, "ahead_no_ff")) *value = ix->policy.ahead_tallied ? ix->policy.ahead_no_ff : -1.0;
     else if (!strcmp(key, "device_scratch_bytes")) {         // device scratch the *_device calls hold: mask words (retired ones too), vector, segment workspace
         *value = (double)ix->dmask.held_bytes() + (double)ix->dpark.cap() + (double)ix->scratch[movi_index::kTmp].cap() + (double)ix->seg_ws.cap() +
@@ -2465,7 +2501,8 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
         // the walk kernels live in translation units of their own: their code objects are loaded here, not by the first walk
         (void)(ix->dev.idx32 ? preload_walk_u32() : preload_walk_u64());
         (void)(ix->dev.idx32 ? preload_walkseg_u32() : preload_walkseg_u64());
-        (void)preload_pack();                                         // (movi_reads_unpack_device in front of a captured walk)
+        if (ix->tables.rows4) (void)preload_walk_chain();
+        (void)preload_pack();                                        // (movi_reads_unpack_device in front of a captured walk)
         (void)hipGetLastError();
         // movi_pml_device's mask words for a default batch (a bigger "reserve_device_masks" stays): its first call allocates nothing.
         // No room is no failure -- an uncaptured call grows them, a captured one takes the packer route

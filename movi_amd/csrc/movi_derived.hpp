@@ -10,10 +10,11 @@
 #include <algorithm>
 
 #include "movi_deep_fields.hpp"   // kDeepWideMaxRows
+#include "movi_chain_fields.hpp"  // kChainMaxRows
 
 namespace movi {
 
-enum DerivedTable { kTabKmer = 0, kTabFtab, kTabAhead, kTabDeep, kTabCkpt, kDerivedTables };
+enum DerivedTable { kTabKmer = 0, kTabFtab, kTabAhead, kTabDeep, kTabCkpt, kTabChain, kDerivedTables };
 
 // The policy's state, one per handle.
 struct DerivedPolicy {
@@ -27,6 +28,7 @@ struct DerivedPolicy {
     bool ahead_tallied = false;
     double ahead_no_ff = 0.0;        // share of the table's positions that arrive at their LF target without a fast-forward (sampled, or tallied by the builder of the look-ahead rows)
     bool prepared = false;           // movi_index_prepare has run: query calls build and allocate nothing any more (a declined copy is retried by movi_index_prepare only)
+    int chain_auto = 1;              // 1: the first PML query builds the chain rows beside the deep rows where ensure_chain_rows says so ("chain_rows" -1)
 };
 
 // What the rules read of the handle.  `held` is refreshed by the device interface after every build and every drop: the rules hold a
@@ -38,6 +40,7 @@ struct DerivedFacts {
     int count_variant = -1;          // "count_variant": the look-ahead copy serves count_kernel_v0 only, i.e. 0
     uint64_t ahead_bytes = 0, deep_bytes = 0;   // what the two row copies of a table of r rows take (ahead_rows_bytes, deep_rows_bytes)
     bool held[kDerivedTables] = {false, false, false, false, false};
+    uint64_t chain_bytes = 0;        // what the chain rows of a table of r rows take (chain_rows_bytes)
 };
 
 // Top-of-walk table (DevIndex::kmer): 16 << 2K bytes, filled by one kernel; the call waits for it -- chunks of the
@@ -77,6 +80,31 @@ inline int deep_hint_width(const DerivedPolicy &p, const DerivedFacts &f) {
     return (int)deep_map_for(f.r, p.deep_hint_bits < 0 ? kDeepHintBitsDefault : p.deep_hint_bits).hint_bits;
 }
 
+// Chain rows (pml_kernel_chain): 32 bytes per row, up to four bases per gather in half-line windows of two rows.  1.5 x the bytes of the deep
+// rows for 11 % fewer fabric lines per base where chains run deep (c2: tools/iter_model.c 0.447 -> 0.396 lines per base, lane iterations per
+// base 0.4888 -> 0.4394 measured; the 450 MB table's line rate is 8 % lower than the 300 MB one's and the launch 2.2 % faster, every run above
+// the deep rows' fastest: profiles/chain_rows.txt); where every other base fast-forwards the deeper chain is rarely ridden and the bigger
+// table only costs cache reach (c2mid, modelled: 0.534 -> 0.514 lines for + 50 % bytes).  Built by itself BESIDE the deep rows -- long reads
+// and segment plans keep walking there -- where the deep rows' own conditions hold and
+//   * the table has at least kChainMinRows rows: 12 Mi rows are the deep rows that fill the 256 MiB Infinity Cache (64 bytes per three rows);
+//     a smaller table's launch is not bound by fabric lines, and every index of the test suite but the two pangenomes lies below it;
+//   * the tallied no-fast-forward share is at least kChainNoFfShare: c2 0.834, c2mid 0.732;
+//   * the device has room for the rows and 2 GiB beside them.
+// kChainMinRows = kChainNoTable would switch the auto-build off; "chain_rows" 1 builds the rows on any eligible index.
+constexpr uint64_t kChainNoTable = ~0ull;
+constexpr uint64_t kChainMinRows = 12ull << 20;
+constexpr double kChainNoFfShare = 0.80;
+inline bool chain_rows_fit(uint64_t r) { return r >= 8 && r <= kChainMaxRows; }
+inline bool chain_eligible(const DerivedFacts &f) { return f.kmode == 6 && chain_rows_fit(f.r); }
+// The auto-build (after ensure_pml_tables, whose tally it reads): a failed or declined build leaves the deep rows in charge.
+template <class Dev>
+void ensure_chain_rows(DerivedPolicy &p, const DerivedFacts &f, Dev &dev, bool from_prepare) {
+    if (p.chain_auto <= 0 || f.held[kTabChain] || !chain_eligible(f) || !(from_prepare || !p.prepared)) return;
+    if (!f.held[kTabDeep] || f.r > kDeepAutoRows) return;                  // beside the deep rows, where the policy builds those
+    if (f.r < kChainMinRows || !p.ahead_tallied || p.ahead_no_ff < kChainNoFfShare) { p.chain_auto = 0; return; }
+    uint64_t free_b = 0, total_b = 0;
+    if (!dev.mem_info(free_b, total_b) || free_b < f.chain_bytes + (2ull << 30) || !dev.build_chain()) p.chain_auto = 0;
+}
 // The count query's interval table (DevIndex::ftab): any DNA index, thresholds or not.
 inline bool ftab_eligible(const DerivedFacts &f) { return (f.kmode == 6 || f.kmode == 3) && f.dna; }
 
@@ -204,6 +232,16 @@ TableRequest request_table(DerivedPolicy &p, const DerivedFacts &f, Dev &dev, De
     default: built = dev.build_deep(deep_hint_width(p, f)); break;
     }
     return built ? TableRequest::kDone : TableRequest::kBuildFailed;
+}
+
+// "chain_rows" 0 / 1: dropped and not built by itself any more, then built where asked.
+template <class Dev>
+TableRequest request_chain(DerivedPolicy &p, const DerivedFacts &f, Dev &dev, uint32_t value) {
+    dev.drop(kTabChain);
+    p.chain_auto = 0;
+    if (value == 0) return TableRequest::kDone;
+    if (!chain_eligible(f)) return TableRequest::kIneligible;
+    return dev.build_chain() ? TableRequest::kDone : TableRequest::kBuildFailed;
 }
 
 // movi_index_prepare: an explicit call asks the device now, whatever an earlier one was told ...

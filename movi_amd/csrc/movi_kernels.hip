@@ -420,6 +420,47 @@ hipError_t build_deep_rows(int kmode, const DevIndex &ix, int hint_bits, uint8_t
     return hipGetLastError();
 }
 
+// ---- chain rows (pml_kernel_chain): thread i writes row i of the copy -- the row, what the walk reads at j1 = id(i), j2 and j3, the ids
+// up to j4, n(j4) (four dependent gathers) -- and its reposition hints for windows of two rows (movi_chain_fields.hpp has the map and
+// the rule that says which entries are valid).  Every thread writes its own 32 bytes: no zeroing, no atomics.
+__global__ __launch_bounds__(256) void chain_rows_kernel(DevIndex ix, uint32_t *__restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t padded = ((ix.r + 1) / 2) * 2;
+    if (i >= padded) return;
+    const uint8_t *rows = ix.rows;
+    const DevIndex *ixp = &ix;
+    auto row_of = [rows, ixp](uint64_t t, uint64_t &id, uint32_t &n, uint32_t &off, uint32_t &c, uint32_t &thr) {
+        const uint2 row = load_row<6>(rows, t);
+        id = row_id<6>(row, t, *ixp);
+        n = row_n<6>(row); off = row_off<6>(row); c = row_c<6>(row);
+        thr = row_thr<6>(row, 0) | (row_thr<6>(row, 1) << 1) | (row_thr<6>(row, 2) << 2);
+    };
+    ChainFields f = chain_fields_of(row_of, ix.r, ix.end_bwt_idx, i);
+    if (i < ix.r && ix.sep == 0u && ix.sigma == 4u && i != ix.end_bwt_idx) {
+        auto c_of = [rows](uint64_t t) { return row_c<6>(load_row<6>(rows, t)); };
+        for (uint32_t k = 0; k < 3u; ++k) {
+            const uint32_t a = k < f.c ? k : k + 1u;      // the base whose slot is k: alphamap_3[c][a] = a - (a > c), src/utils.cpp:5-8
+            if (a > 3u) continue;
+            f.hints |= chain_hint_of(c_of, ix.r, i, a, ((f.thr >> k) & 1u) == 0u, kChainHintReach) << (kChainHintBits * k);
+        }
+    }
+    uint32_t d[8];
+    chain_pack(f, d);
+    uint4 *W = reinterpret_cast<uint4 *>(out + i * 8u);
+    W[0] = make_uint4(d[0], d[1], d[2], d[3]);
+    W[1] = make_uint4(d[4], d[5], d[6], d[7]);
+}
+
+uint64_t chain_rows_bytes(uint64_t r) { return chain_rows_bytes_of(r); }
+bool chain_rows_eligible(uint64_t r) { return r >= 8 && r <= kChainMaxRows; }
+
+hipError_t build_chain_rows(int kmode, const DevIndex &ix, uint8_t *d_rows4, hipStream_t stream) {
+    if (!d_rows4 || !chain_rows_eligible(ix.r) || kmode != 6) return hipErrorInvalidValue;
+    const uint64_t blocks = (ix.r + 1 + 255) / 256;
+    hipLaunchKernelGGL(chain_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, ix, reinterpret_cast<uint32_t *>(d_rows4));
+    return hipGetLastError();
+}
+
 hipError_t build_kmer_table(const DevIndex &ix, uint32_t K, uint4 *d_table, hipStream_t stream) {
     if (K < 1 || K > 12 || !d_table || ix.sigma - ix.sep != 4) return hipErrorInvalidValue;
     const uint64_t n = 1ull << (2 * K);
@@ -700,8 +741,8 @@ __global__ __launch_bounds__(256) void seg_finalize_kernel(const uint32_t *__res
     }
 }
 
-TableFacts facts(const DevIndex &ix) {   // what the launch policy (movi_launch_policy.hpp) reads of the index
-    return {ix.r, ix.idx32 != 0u, ix.sep != 0u, ix.rows2 != nullptr, ix.rows3 != nullptr, ix.hints != 0u, ix.rows2_count != 0u};
+TableFacts facts(const DevIndex &ix, bool chain_rows) {   // what the launch policy (movi_launch_policy.hpp) reads of the index
+    return {ix.r, ix.idx32 != 0u, ix.sep != 0u, ix.rows2 != nullptr, ix.rows3 != nullptr, ix.hints != 0u, ix.rows2_count != 0u, chain_rows};
 }
 
 namespace {
@@ -1060,6 +1101,12 @@ hipError_t launch_pml(const PmlCall &c, const PmlRoute &R) {
     ixl.inwin = cfg.inwin ? 1u : 0u;
     ixl.hint_w = (R.ahd == 2 && R.hint_w != 0u) ? ix.deep_hint_bits : R.hint_w;   // (the plan says "on" (2) for the deep rows: the width is the one they were built with)
     ixl.mask_phase = mask.phase & 31u;
+    // the chain rows: pml_kernel_chain reads its table where the deep-row walk reads the deep rows (the kernels' view has one pointer for both)
+    const bool chain = R.ahd == 3;
+    if (chain) {
+        if (!c.chain_rows || !chain_rows_eligible(ix.r) || !ix.idx32 || cm != 0 || v != 14 || R.ring == 1 || R.psh != 0) return hipErrorInvalidValue;
+        ixl.rows3 = c.chain_rows;
+    }
     ixl.ff_skip = R.ff_skip ? 1u : 0u;
     ixl.expand_out = R.kind == PmlRouteKind::kVectorFused ? expand_out : nullptr;
     // Parked lanes (DevIndex::park_at; the route's park_lanes): the queue's counter is zeroed by a kernel on the stream (park_reset_kernel),
@@ -1081,7 +1128,7 @@ hipError_t launch_pml(const PmlCall &c, const PmlRoute &R) {
             hipLaunchKernelGGL(park_reset_kernel, dim3(1), dim3(64), 0, c.stream, ixl.park_count, c.stats);
             e = hipGetLastError();
         }
-        if (e == hipSuccess) e = ix.idx32 ? launch_walk_u32(L, info) : launch_walk_u64(L, info);
+        if (e == hipSuccess) e = chain ? launch_walk_chain(L, info) : ix.idx32 ? launch_walk_u32(L, info) : launch_walk_u64(L, info);
         if (e == hipSuccess && R.park_lanes > 0) {
             // the second launch: the same kernel resumes the parked reads, 64 to a wavefront -- a grid for every record the first can have
             // written, the same dynamic LDS, the same stream (stream order is all the synchronisation there is); `info` names the first
@@ -1089,7 +1136,7 @@ hipError_t launch_pml(const PmlCall &c, const PmlRoute &R) {
             L.ix.park_at = 0u;
             L.ix.resume = 1u;
             L.order = nullptr;                             // (a record names its read)
-            e = ix.idx32 ? launch_walk_u32(L, nullptr) : launch_walk_u64(L, nullptr);
+            e = chain ? launch_walk_chain(L, nullptr) : ix.idx32 ? launch_walk_u32(L, nullptr) : launch_walk_u64(L, nullptr);
         }
     } else {
         // the base-synchronous kernels (every one takes at most 64 KiB of dynamic LDS: the cap's padding)

@@ -5,6 +5,7 @@
 
 #include "movi_launch_policy.hpp"   // LaunchCfg, the kCap* / k*ReadLen / k*Bytes constants, the launch plans
 #include "movi_deep_fields.hpp"     // the deep rows' two field maps (plain C++: host tests compile it too)
+#include "movi_chain_fields.hpp"    // the chain rows' field map, likewise
 #include "movi_buffers.hpp"         // the owning types (host side only); their two memory policies are below
 
 namespace movi {
@@ -151,7 +152,7 @@ struct LaunchInfo {
     int waves_per_cu = 0;    // resident-wavefront cap applied (0 = none)
     int segmented = 0;       // 1 = the segment-parallel plan ran (K1 + stitch + finalize around the named kernel)
     int idx64 = 0;           // 1 = the 64-bit row-index instantiation
-    int ahead = 0;           // 1 = the walk ran on the look-ahead rows (two bases per gather where the next base matches)
+    int ahead = 0;           // 1 = the walk ran on the look-ahead rows (two bases per gather where the next base matches), 2 = on the deep rows (three), 3 = on the chain rows (four)
     int staged = 0;          // > 0: every lane keeps the next `staged` bases of its read in LDS (pml_kernel_flatp<..., STG = 1>)
     int park_lanes = 0;      // > 0: the mask walk parked a wavefront's last `park_lanes` lanes and a second launch of the named kernel resumed them
     int ff_skip = 0;         // 1 = the PML walk ran with the fast-forward skip (DevIndex::ff_skip)
@@ -296,7 +297,7 @@ struct MaskArgs {
     uint64_t park_cap = 0;
 };
 uint64_t pml_mask_words(uint64_t n_reads, uint64_t n_bases, uint32_t phase);          // words a batch's masks take (gap words included)
-TableFacts facts(const DevIndex &ix);     // what the launch policy reads of the index
+TableFacts facts(const DevIndex &ix, bool chain_rows = false);   // what the launch policy reads of the index (chain_rows: the handle holds them)
 // u16 vector <-> masks, streaming (one lane per read; a wavefront per read from a mean length of 2048 bases)
 hipError_t launch_pml_expand(const uint32_t *d_words, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t phase,
                              uint16_t *d_out, hipStream_t stream);
@@ -332,6 +333,7 @@ struct PmlCall {
     int *seg_verdict = nullptr;
     LaunchInfo *info = nullptr;
     MaskArgs mask;
+    const uint8_t *chain_rows = nullptr;  // the handle's chain rows (null: it holds none): what a route with ahd == 3 walks on
     int cls_mode() const { return cls.bin_width == 0 ? 0 : (out ? 1 : 2); }   // 0 = PML vector only, 1 = vector + classification bins, 2 = bins only
     bool logging() const { return cls.log_ff != nullptr || cls.log_scan != nullptr; }
 };
@@ -378,6 +380,14 @@ uint64_t ahead_rows_bytes(uint64_t r);
 uint64_t deep_rows_bytes(uint64_t r);
 bool deep_rows_eligible(uint64_t r);
 hipError_t build_deep_rows(int kmode, const DevIndex &ix, int hint_bits, uint8_t *d_rows3, hipStream_t stream);   // hint_bits: 2 or 4 (deep_map_for)
+// Chain rows (pml_kernel_chain; "chain_rows" option): chain_rows_bytes(r) bytes at d_rows4, every byte written by one kernel (four dependent
+// gathers per row).  Thresholds types (kmode 6), 8 <= r < 2^28 - 1.  The kernels' view of the index has no field for them: a launch that
+// walks on them hands the table over in PmlCall::chain_rows and launch_pml puts it where that kernel reads its rows (DevIndex::rows3).
+uint64_t chain_rows_bytes(uint64_t r);
+bool chain_rows_eligible(uint64_t r);
+hipError_t build_chain_rows(int kmode, const DevIndex &ix, uint8_t *d_rows4, hipStream_t stream);
+hipError_t launch_walk_chain(const WalkLaunch &L, LaunchInfo *info);   // pml_kernel_chain<SEP, RING> (movi_walk_chain.hip): L.sep, L.ring 0 / 2
+hipError_t preload_walk_chain();
 bool ahead_rows_hinted(uint64_t r);    // the copy of a table of r rows carries reposition hints and 32-bit ids (DevIndex::hints)
 hipError_t build_ahead_rows(int kmode, const DevIndex &ix, uint8_t *d_rows2, uint64_t *tail, hipStream_t stream,
                             unsigned long long *d_tally = nullptr);   // d_tally: 2 * kTallySlots zeroed u64 (tally_add spreads the atomics by block; the caller sums the pairs), optional

@@ -14,6 +14,8 @@ constexpr int kCountCapWaves = 16;   // the count kernel's cap on cache-resident
 constexpr int kCapWaves = 7;   // resident wavefronts per CU of the lane state machine on big batches (round 2: 9, optimum 8-10; round 3, with the reads staged in LDS and the top-of-walk table: 6-8, profiles/r03_occupancy_sweep.txt)
 constexpr int kCapWavesAhead = 9;    // ... when the walk runs on the look-ahead rows: fewer lines per base, more walks in flight pay (profiles/r03_ahead_rows_ab.txt)
 constexpr int kCapWavesDeep = 13;    // ... on the deep rows: fewer lines per base again and more instructions per iteration (c2, cap 9 / 11 / 13 / 14 / 16: vector out 71.8 / 75.7 / 78.4 / 78.7 / 77.9, reset masks out 87.3 / 89.9 / 89.4 / 89.5 / 87.8 Gbases/s: profiles/r06_deep_rows.txt)
+constexpr int kCapWavesChain = 13;   // ... on the chain rows: the deep rows' cap (a sweep of 11 / 13 / 14 on c2 is in profiles/chain_rows.txt)
+constexpr uint32_t kChainHintW = 4;  // width of a reposition hint in the chain rows (movi_chain_fields.hpp)
 constexpr uint32_t kOutRingBytes = 4096;          // pml_kernel_flatp<..., RING = 1>: the ring in the block's dynamic LDS its PMLs leave through (32 per lane)
 constexpr uint64_t kOutRingReadLen = 1024;        // ... on by itself for batches whose mean read length is at least this (plan_pml)
 constexpr size_t kZmlStageBytes = 10240;          // zml_kernel_flat: dynamic LDS per one-wavefront block for its staged reads (160 bases per lane; 16 wavefronts per CU)
@@ -58,6 +60,7 @@ struct TableFacts {
     bool idx32 = false, sep = false;
     bool rows2 = false, rows3 = false, hints = false;   // the look-ahead rows / the deep rows / reposition hints exist
     bool rows2_count = false;                           // the count query walks on the look-ahead rows too
+    bool rows4 = false;                                 // the chain rows exist (pml_kernel_chain: four bases per gather)
 };
 
 // Occupancy cap: enforced by the dispatcher through the block's LDS allocation (160 KiB per CU); blocks beyond the cap queue and start
@@ -95,6 +98,7 @@ struct PmlPlan {
     bool use_ring = false, use_ahead = false, use_pair = false;
     bool use_deep = false;           // the walk runs on the deep rows (DevIndex::rows3: three bases per gather)
     int park_lanes = 0;              // > 0: a mask walk of this plan parks a wavefront's last lanes for a second launch (plan_pml: where a queue is lent and, for the vector, the expansion is fused)
+    bool use_chain = false;          // the walk runs on the chain rows (pml_kernel_chain: 32-byte rows, four bases per gather); use_deep is false then
 };
 
 // Where the results of one PML call leave the walk, and everything launch_pml needs to act on it: decided once, by plan_pml.
@@ -197,24 +201,28 @@ inline PmlPlan plan_pml_walk(const TableFacts &ix, const LaunchCfg &cfg, uint64_
     // text (c2: fabric lines per base 0.584 -> 0.477, 80.3 -> 89.6 Gbases/s with reset masks out); 10 kbp reads with 8 % substitutions spend
     // their iterations on repositions, which three-row windows serve worse than four-row ones (59.3 -> 44.4): profiles/r06_deep_rows.txt
     const bool deep_ok = stage_ok && ix.rows3 && ix.idx32 && (cfg.deep > 0 || (cfg.deep < 0 && n_bases / n_reads < kDeepReadLen));
-    const bool ahead_ok = stage_ok && (ix.rows2 || deep_ok);                            // ... or on the look-ahead rows
+    // ... on the chain rows where the handle holds them: the same batches of short reads, plain queries (no bins) through the register packer
+    // or as reset masks (the kernel has no LDS ring); "deep" 0 keeps a launch off both copies
+    const bool chain_ok = stage_ok && ix.rows4 && ix.idx32 && cm == 0 && cfg.deep != 0 && n_bases / n_reads < kDeepReadLen;
+    const bool ahead_ok = stage_ok && (ix.rows2 || deep_ok || chain_ok);                // ... or on the look-ahead rows
     if (cfg.waves_per_cu == 0 && v == 14 && big_batch)
-        wpc = deep_ok ? kCapWavesDeep : (ahead_ok ? kCapWavesAhead : kCapWaves);     // the auto policy above
+        wpc = chain_ok ? kCapWavesChain : (deep_ok ? kCapWavesDeep : (ahead_ok ? kCapWavesAhead : kCapWaves));     // the auto policy above
     P.wpc = wpc;
     // cfg.stage_reads: 1 = whenever it fits (default), 0 = never.
     // cfg.out_ring: -1 = batches of long reads, 0 / 1 = never / wherever it fits (A/B).  (Reset masks out: no PML leaves, no ring.)
     const bool ring_wanted = stage_ok && !want_mask && (cfg.out_ring > 0 || (cfg.out_ring < 0 && n_bases / n_reads >= kOutRingReadLen));
     // (`uncapped`: no cap was asked for or picked -- a cap of 32 wavefronts and more pads nothing and leaves the launch unstaged)
     stage_budget(P, wpc > 0 ? cap_lds(wpc / (bt / 64), 1) : 0, wpc == 0, stage_ok, ring_wanted, blocks, cfg.num_cus);
-    P.use_deep = deep_ok && P.stage_lds != 0u;
-    P.use_ahead = ahead_ok && P.stage_lds != 0u;
+    P.use_chain = chain_ok && P.stage_lds != 0u && !P.use_ring;
+    P.use_deep = deep_ok && P.stage_lds != 0u && !P.use_chain;
+    P.use_ahead = (ix.rows2 || P.use_deep || P.use_chain) && stage_ok && P.stage_lds != 0u;
     // pair-shared gathers (pml_kernel_flatp<..., PSH = 1>): the staged default walk on the plain or the look-ahead rows
     // Where: on tables beyond the reach of the per-CU TLBs (~2 GB), where a lane's two (four) 16-byte loads are as many
     // translation requests and the L2 TLB's request rate bounds the walk -- real BWT of 226 M rows on the look-ahead rows (3.6 GB
     // copy) 39.4 -> 50.8 Gbases/s, the random 1 B-row table 32.6 -> 34.7 on its plain rows and 21.4 -> 44.2 on the look-ahead
     // copy (16 GB); below that the exchange costs about what the merged accesses give (random 25 / 50 / 100 M rows +4 / +5 / -2 %,
     // real 113 M rows +1.5 %, c2 -2.5 %, c3 -9 %: profiles/r04_pair_shared_gathers.txt).  "pair_loads" 1 / 0 forces it.
-    P.use_pair = pair_wanted(cfg, ix.r * (P.use_ahead ? 16ull : 8ull)) && P.stage_lds != 0u && v == 14 && !P.use_deep;
+    P.use_pair = pair_wanted(cfg, ix.r * (P.use_ahead ? 16ull : 8ull)) && P.stage_lds != 0u && v == 14 && !P.use_deep && !P.use_chain;
     // Parked lanes (DevIndex::park_at): only where the walk writes reset masks itself -- the staged default walk, whole reads, no bins.
     // By itself ("park_lanes" -1) only for batches of kParkMinRounds rounds of wavefronts and more (a capped launch: `rounds` of wpc
     // wavefronts per CU) and of short reads: long reads roll through their staged stretch and a resumed lane would stage again mid-read
@@ -267,9 +275,9 @@ inline PmlRoute plan_pml(const TableFacts &ix, const LaunchCfg &cfg, uint64_t n_
         R.park_lanes = park;
         R.park_grid = park_grid_lanes / bt;
     }
-    R.hint_w = P.use_deep ? (cfg.hints != 0 ? 2u : 0u) : ((cfg.hints != 0 && ix.hints && ix.rows2) ? 3u : 0u);
-    R.ff_skip = P.v == 14 && ff_skip_on(cfg, P.use_deep, P.use_ahead);
-    R.ahd = P.use_deep ? 2 : (P.use_ahead ? 1 : 0);
+    R.hint_w = P.use_chain ? (cfg.hints != 0 ? kChainHintW : 0u) : P.use_deep ? (cfg.hints != 0 ? 2u : 0u) : ((cfg.hints != 0 && ix.hints && ix.rows2) ? 3u : 0u);
+    R.ff_skip = P.v == 14 && ff_skip_on(cfg, P.use_deep || P.use_chain, P.use_ahead);
+    R.ahd = P.use_chain ? 3 : (P.use_deep ? 2 : (P.use_ahead ? 1 : 0));
     R.psh = P.use_pair ? 1 : 0;
     R.ring = native ? 2 : (P.use_ring ? 1 : 0);
     return R;

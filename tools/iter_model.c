@@ -12,7 +12,8 @@
 //   * look-ahead chains, depth S: after a base is resolved at row i, up to S following bases ride along while
 //     they match c(j_s) and arrive without a fast-forward (entry of row i holds the chain j_1 .. j_S);
 //   * fast-forward skip (skip = 1): where the entry of j_s shows that the offset arrives at or beyond n(j_s), the first window
-//     charged is the one that holds j_s + 1, not j_s.
+//     charged is the one that holds j_s + 1, not j_s.  skip = 2: the row also stores n(j_{S+1}), so the same holds for the LF behind the
+//     chain's LAST ride (the chain rows, S = 3: movi_chain_fields.hpp).
 // Output: lane iterations per base, the share of iterations by kind, SIMT efficiency for waves of 64 consecutive
 // reads (wave iterations = max over lanes), and the distributions the designs depend on.
 //
@@ -55,9 +56,12 @@ static uint32_t walk(const uint8_t *rd, uint32_t len, uint32_t top_k, const Desi
     uint64_t last_line = ~0ull;
 #define FETCH(row) do { const uint64_t ln_ = (uint64_t)(row) / RPL; if (ln_ != last_line) { t->lines++; last_line = ln_; } } while (0)
     int chain_left = 0;                              // bases that may still ride on the current entry
+    int last_rode = 0;                               // the base before this one rode (with chain_left == 0: the chain was ridden to its end)
     for (uint32_t k = 0; k < len; k++) {
         const int a = code_of(rd[len - 1 - k]);
         int rode = 0, arr_ff = 0;
+        const int prev_rode = last_rode;
+        last_rode = 0;
         if (k != 0) {                                // LF_move + fast_forward
             const uint64_t j = rid(idx);
             off += roff(idx);
@@ -65,7 +69,7 @@ static uint32_t walk(const uint8_t *rd, uint32_t len, uint32_t top_k, const Desi
             uint32_t ff = 0;
             while (jj < r - 1 && off >= rn(jj)) { off -= rn(jj); jj++; ff++; }
             t->ff_rows += ff; arr_ff = ff != 0;
-            const int alive = chain_left > 0;        // the LF was taken from an entry that holds n(j): the kernel knows `ff != 0` before it gathers
+            const int alive = chain_left > 0 || (d->skip == 2 && prev_rode);   // the LF was taken from an entry that holds n(j) (skip = 2: or from the chain's end, which holds it too): the kernel knows `ff != 0` before it gathers
             // does this base ride on the look-ahead chain? (match at j, no fast-forward)
             if (chain_left > 0 && ff == 0 && a >= 0 && (int)rc(j) == a && k >= top_k) { rode = 1; chain_left--; }
             else chain_left = 0;
@@ -77,7 +81,7 @@ static uint32_t walk(const uint8_t *rd, uint32_t len, uint32_t top_k, const Desi
             }
             idx = jj;
         } else if (top_k == 0) { it++; t->it_arrive++; FETCH(idx); }
-        if (rode) { t->chained++; continue; }        // matched by construction
+        if (rode) { t->chained++; last_rode = 1; continue; }        // matched by construction
         if (a < 0) { chain_left = (k >= top_k && !(d->own && arr_ff)) ? d->S : 0; continue; }
         if ((int)rc(idx) == a) { chain_left = (k >= top_k && !(d->own && arr_ff)) ? d->S : 0; continue; }
         // reposition
@@ -192,6 +196,9 @@ int main(int argc, char **argv) {
         // wider hints on the deep rows with the skip: 3, 4 and 6 bits per threshold slot (reach 7, 15, 63).  4 bits fit beside 26-bit ids
         // ("deep_hint_bits" 4: tables of at most 2^26 - 1 rows) and are the knee: profiles/deep_hints.txt
         {2, 3, 2, 7, 1, 0, 6, 1}, {2, 3, 2, 15, 1, 0, 6, 1}, {2, 3, 2, 63, 1, 0, 6, 1},
+        // chain rows: entries THREE rows deep in 32-byte rows (4 rows per line, windows of 2 rows = half a line), 4-bit hints: with the skip as the
+        // deep rows have it, with the skip behind the chain's last ride as well (what pml_kernel_chain does), and that with 6-bit hints
+        {3, 2, 2, 15, 1, 0, 4, 1}, {3, 2, 2, 15, 1, 0, 4, 2}, {3, 2, 2, 63, 1, 0, 4, 2},
     };
     printf("r = %llu rows, %llu reads x %u, top-of-walk K = %u\n", (unsigned long long)r, (unsigned long long)n_reads, L, top_k);
     printf("%-40s %9s %9s | %7s %7s %7s %7s | %7s | %6s %6s %6s | %7s\n", "design", "iter/base", "SIMT", "arrive", "ff-win", "mismat", "scanwin",
@@ -213,7 +220,7 @@ int main(int argc, char **argv) {
         if (df) fclose(df);
         char name[96];
         snprintf(name, sizeof name, "S=%d W=%d side=%d(%d) inwin=%d own=%d rpl=%d%s", designs[di].S, designs[di].W, designs[di].side, designs[di].side_reach, designs[di].inwin, designs[di].own, designs[di].rpl ? designs[di].rpl : 8,
-                 designs[di].skip ? " sk" : "");
+                 designs[di].skip == 2 ? " sk+" : designs[di].skip ? " sk" : "");
         const double b = (double)t.bases;
         printf("%-40s %9.4f %9.3f | %7.4f %7.4f %7.4f %7.4f | %7.4f | %6.3f %6.3f %6.4f | %7.4f\n", name, t.iters / b, (double)t.iters / t.waves_iters,
                t.it_arrive / b, t.it_ffwin / b, t.it_mism / b, t.it_scanwin / b, t.chained / b, t.ff_rows / b, t.scan_rows / b, t.repos / b, t.lines / b);
