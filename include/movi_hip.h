@@ -21,6 +21,7 @@
  *   MoveStructure::get_SA_entries  src/move_structure.cpp:35-48  movi_locate_device / movi_sa_entries_host / movi_sa_entries_device
  *   MoveStructure::find_sampled_SA_entries  src/move_structure_build.cpp:1174-1212  movi_ssa_build
  *   MoveStructure::build (--preprocessed)  src/move_structure_build.cpp:17-72, :240-324  movi_build_from_rlbwt
+ *   prepare_ref + pfp-thresholds + MoveStructure::build  src/movi_launcher.cpp:190-242, src/prepare_ref.cpp  movi_rlbwt_from_text / movi_build_from_text
  *   MoveStructure::serialize_sampled_SA / deserialize_sampled_SA  src/move_structure_io.cpp:710-744  movi_ssa_save / movi_ssa_load
  *   MoveStructure::build_doc_pats / build_doc_sets  src/move_structure_color.cpp:4-72  movi_color_build
  *   MoveStructure::flat_and_serialize_colors_vectors / deserialize_doc_sets_flat  src/move_structure_io.cpp:513-548,587-607  movi_color_save / movi_color_load
@@ -695,6 +696,47 @@ int movi_multi_classify_host(movi_index_t *ix, const uint8_t *h_bases, const uin
  * Not a capture-safe entry point: it allocates, reads sizes back and waits. */
 int movi_build_from_rlbwt(int device, uint32_t mode, const uint8_t *h_heads, const uint64_t *h_lens, const uint64_t *h_thr /* NULL for modes 2, 3, 5 */,
                           uint64_t original_r, void **h_image, size_t *image_bytes);      /* release with movi_host_free */
+
+/* ---- the run-length BWT, the thresholds and index.movi from a text ---------------- */
+
+/* What the reference's external pipeline (prepare_ref, then pfp-thresholds: src/movi_launcher.cpp:190-242, src/prepare_ref.cpp) hands to
+ * MoveStructure::build(), from the text itself, on the device.  h_text: the cleaned text of n characters as prepare_ref leaves it
+ * (records, reverse complements, separators); any byte 1 .. 255 is a character here, the DNA scope is the table builder's check.  The
+ * builder appends the terminator 0: N = n + 1 BWT positions.
+ * Stages: the suffix array by prefix doubling (a radix sort of one 64-bit key per suffix and round, the first round on 8 characters;
+ * every round sorts all suffixes), the BWT and its maximal runs, the LCP array by Kasai's algorithm with one lane per lcp_chunk
+ * neighbouring text positions (exact; at most N + lanes x the longest repeat character comparisons, 8 per step), and the thresholds in
+ * pfp-thresholds' .thr_pos convention: for run k with head c starting at s, the previous run of c ending at e, the LEFTMOST position
+ * of the minimum of lcp[e + 1 .. s]; 0 where c has not occurred before.  The terminator and '%' are characters like the others.
+ * verify = 1: the suffix array is a permutation and the rank array its inverse; every neighbouring pair is in order by its first
+ * characters and, those being equal, by the ranks of the suffixes one further on; the LCP equals a direct comparison at 4096 seeded
+ * positions (only where the LCP is computed).  A finding is MOVI_ERR_INVARIANT and nothing is returned.
+ * Checked on the host before any device call, MOVI_ERR_ARG with the argument in the message: a NULL pointer, n = 0, a byte 0 in the
+ * text (with its position), n above MOVI_TEXT_MAX_CHARS (ranks and positions are 32 bits).
+ * Memory: the plan's peak is a formula over N alone (movi_text_device_bytes; 29.1 bytes per character and hipcub's scratch: min(N, 2^30) + 32 MiB).  It is compared with the
+ * device's free memory, or with max_device_bytes, before the first allocation; a refusal is MOVI_ERR_ARG and names both figures.
+ * Every device allocation is freed on every return path; a failed call leaves the outputs NULL.  The three arrays are page-locked:
+ * release each with movi_host_free.  Not capture-safe entry points: they allocate, read sizes back and wait.
+ * movi_build_from_text: movi_rlbwt_from_text, the checks of movi_build_from_rlbwt (alphabet, run counts) and its table builder; for the
+ * types without thresholds (2, 3, 5) the LCP and threshold passes are skipped.  stats may be NULL. */
+#define MOVI_TEXT_MAX_CHARS 4293918720ull   /* 2^32 - 2^20 */
+typedef struct movi_text_build_opts {   /* NULL = all defaults */
+    uint32_t lcp_chunk;          /* text positions per lane of the LCP pass, 0 = default (N / 2^17 held to 64 .. 1024) */
+    uint32_t verify;             /* 1 = the verify stage */
+    uint64_t max_device_bytes;   /* 0 = what the device reports free; else plan as if only this much were */
+    uint64_t reserved_[3];
+} movi_text_build_opts_t;
+typedef struct movi_text_build_stats {
+    uint64_t n_positions, original_r, device_bytes;   /* N, the runs, the peak of device bytes held */
+    uint32_t rounds, verified;                        /* sorts of the prefix doubling; 1 = the verify stage ran and found nothing */
+    double seconds[6];                                /* upload | suffix sort | BWT and runs | LCP | thresholds | verify */
+} movi_text_build_stats_t;
+int movi_text_device_bytes(uint64_t n, uint64_t *bytes);   /* the plan's device bytes for a text of n characters; host only */
+int movi_rlbwt_from_text(int device, const uint8_t *h_text, uint64_t n, const movi_text_build_opts_t *opts,
+                         uint8_t **h_heads, uint64_t **h_lens, uint64_t **h_thr, uint64_t *original_r,
+                         movi_text_build_stats_t *stats /* may be NULL */);       /* release the three with movi_host_free */
+int movi_build_from_text(int device, uint32_t mode, const uint8_t *h_text, uint64_t n, const movi_text_build_opts_t *opts,
+                         void **h_image, size_t *image_bytes, movi_text_build_stats_t *stats);
 
 /* ---- page-locked host memory --------------------------------------------------- */
 

@@ -67,6 +67,26 @@ class LaunchInfoC(C.Structure):
     ]
 
 
+class TextBuildOptsC(C.Structure):
+    _fields_ = [
+        ("lcp_chunk", C.c_uint32),
+        ("verify", C.c_uint32),
+        ("max_device_bytes", C.c_uint64),
+        ("reserved_", C.c_uint64 * 3),
+    ]
+
+
+class TextBuildStatsC(C.Structure):
+    _fields_ = [
+        ("n_positions", C.c_uint64),
+        ("original_r", C.c_uint64),
+        ("device_bytes", C.c_uint64),
+        ("rounds", C.c_uint32),
+        ("verified", C.c_uint32),
+        ("seconds", C.c_double * 6),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/movi_hip.h one to one.
 SYMBOLS = {
     "movi_last_error": (C.c_char_p, []),
@@ -157,6 +177,12 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(QueryStatsC)]),
     "movi_build_from_rlbwt": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "movi_text_device_bytes": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "movi_rlbwt_from_text": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.POINTER(TextBuildOptsC), C.POINTER(C.c_void_p),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64),
+                                       C.POINTER(TextBuildStatsC)]),
+    "movi_build_from_text": (C.c_int, [C.c_int, C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(TextBuildOptsC),
+                                       C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(TextBuildStatsC)]),
     "movi_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "movi_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "movi_host_free": (C.c_int, [C.c_void_p]),

@@ -9,6 +9,7 @@
 #include "movi_expand_host.hpp"
 #include "movi_pack_host.hpp"
 #include "movi_build.hpp"
+#include "movi_text.hpp"
 
 #include <algorithm>
 #include <cstdio>
@@ -2087,6 +2088,75 @@ int movi_build_from_rlbwt(int device, uint32_t mode, const uint8_t *h_heads, con
     HIP_TRY(hipSetDevice(device));
     const int rc = build_from_rlbwt(mode, h_heads, h_lens, mode_has_thresholds(mode) ? h_thr : nullptr, original_r, info, h_image, image_bytes, why);
     return rc == MOVI_OK ? MOVI_OK : fail(rc, why);
+}
+
+// ------------------------------------------------------------- the run-length BWT and index.movi from a text (movi_walk_text.hip)
+
+namespace {
+int text_build_checked(int device, const uint8_t *h_text, uint64_t n, const movi_text_build_opts_t *opts, bool with_thr,
+                       uint8_t **heads, uint64_t **lens, uint64_t **thr, uint64_t *original_r, movi_text_build_stats_t *stats) {
+    std::string why;
+    if (!text_check(h_text, n, why)) return fail(MOVI_ERR_ARG, why);         // before any device call
+    HIP_TRY(hipSetDevice(device));
+    TextBuildStats st;
+    const int rc = rlbwt_from_text(h_text, n, with_thr, opts ? opts->lcp_chunk : 0u, opts && opts->verify != 0u,
+                                   opts ? opts->max_device_bytes : 0ull, heads, lens, thr, original_r, st, why);
+    if (stats) {
+        stats->n_positions = st.n_positions; stats->original_r = st.original_r; stats->device_bytes = st.device_bytes;
+        stats->rounds = st.rounds; stats->verified = st.verified;
+        for (int k = 0; k < 6; k++) stats->seconds[k] = st.seconds[k];
+    }
+    return rc == MOVI_OK ? MOVI_OK : fail(rc, why);
+}
+}  // namespace
+
+int movi_text_device_bytes(uint64_t n, uint64_t *bytes) {
+    if (!bytes) return fail(MOVI_ERR_ARG, "bytes is NULL");
+    *bytes = 0;
+    if (n == 0 || n > kTextMaxChars) return fail(MOVI_ERR_ARG, "n is " + std::to_string(n) + ": 1 .. " + std::to_string(kTextMaxChars) + " characters are served");
+    *bytes = text_device_bytes(n + 1);
+    return MOVI_OK;
+}
+
+int movi_rlbwt_from_text(int device, const uint8_t *h_text, uint64_t n, const movi_text_build_opts_t *opts, uint8_t **h_heads,
+                         uint64_t **h_lens, uint64_t **h_thr, uint64_t *original_r, movi_text_build_stats_t *stats) {
+    if (h_heads) *h_heads = nullptr;
+    if (h_lens) *h_lens = nullptr;
+    if (h_thr) *h_thr = nullptr;
+    if (original_r) *original_r = 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!h_heads) return fail(MOVI_ERR_ARG, "h_heads is NULL");
+    if (!h_lens) return fail(MOVI_ERR_ARG, "h_lens is NULL");
+    if (!h_thr) return fail(MOVI_ERR_ARG, "h_thr is NULL");
+    if (!original_r) return fail(MOVI_ERR_ARG, "original_r is NULL");
+    return text_build_checked(device, h_text, n, opts, true, h_heads, h_lens, h_thr, original_r, stats);
+}
+
+int movi_build_from_text(int device, uint32_t mode, const uint8_t *h_text, uint64_t n, const movi_text_build_opts_t *opts,
+                         void **h_image, size_t *image_bytes, movi_text_build_stats_t *stats) {
+    if (h_image) *h_image = nullptr;
+    if (image_bytes) *image_bytes = 0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!h_image) return fail(MOVI_ERR_ARG, "h_image is NULL");
+    if (!image_bytes) return fail(MOVI_ERR_ARG, "image_bytes is NULL");
+    if (!mode_supported(mode)) return fail(MOVI_ERR_ARG, "mode " + std::to_string(mode) + " is not supported");
+    uint8_t *heads = nullptr;
+    uint64_t *lens = nullptr, *thr = nullptr, R = 0;
+    const bool with_thr = mode_has_thresholds(mode);
+    int rc = text_build_checked(device, h_text, n, opts, with_thr, &heads, &lens, &thr, &R, stats);
+    if (rc == MOVI_OK) {
+        RlbwtInfo info;
+        RlbwtArray which;
+        std::string why;
+        if (!rlbwt_check(heads, lens, thr, R, info, which, why)) rc = fail(MOVI_ERR_ARG, "h_text: its run-length BWT is out of the table builder's scope: " + why);
+        else {
+            rc = build_from_rlbwt(mode, heads, lens, thr, R, info, h_image, image_bytes, why);
+            if (rc != MOVI_OK) rc = fail(rc, why);
+        }
+    }
+    for (void *p : {(void *)heads, (void *)lens, (void *)thr})
+        if (p) (void)hipHostFree(p);
+    return rc;
 }
 
 int movi_host_register(void *p, size_t bytes) {

@@ -10,6 +10,7 @@ Reference seam (file:line under /root/reference) -> here:
   MoveStructure::get_SA_entries       src/move_structure.cpp:35-48       -> MoveIndex.locate / query_sa_entries
   MoveStructure::find_sampled_SA_entries src/move_structure_build.cpp:1174 -> MoveIndex.build_ssa (save_ssa / load_ssa: ssa.movi)
   MoveStructure::build (--preprocessed) src/move_structure_build.cpp:17-72 -> build_image
+  prepare_ref + pfp-thresholds + build  src/movi_launcher.cpp:190-242    -> rlbwt_from_text / build_image_from_text
 
 All compute happens in libmovi_hip.so on the GPU; this file only marshals
 buffers.  Errors are MoviError (the reference throws std::runtime_error).
@@ -18,7 +19,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import IndexDescC, LaunchInfoC, QueryStatsC, check, lib
+from ._lib import IndexDescC, LaunchInfoC, QueryStatsC, TextBuildOptsC, TextBuildStatsC, check, lib
 
 
 # movi_mem_t: one maximal exact match, end exclusive; count = occurrences of the match's reverse complement (64 bits)
@@ -73,6 +74,62 @@ def build_image(heads, lens, thr, mode, device=0):
     img, nbytes = C.c_void_p(), C.c_size_t(0)
     check(lib().movi_build_from_rlbwt(int(device), int(mode), heads.ctypes.data, lens.ctypes.data,
                                       thr.ctypes.data if thr is not None else None, heads.size, C.byref(img), C.byref(nbytes)))
+    try:
+        return C.string_at(img.value, nbytes.value)
+    finally:
+        lib().movi_host_free(img)
+
+
+class TextBuildStats:
+    """Python view of movi_text_build_stats_t."""
+    STAGES = ("upload", "suffix_sort", "bwt_runs", "lcp", "thresholds", "verify")
+
+    def __init__(self, c):
+        self.n_positions = int(c.n_positions)
+        self.original_r = int(c.original_r)
+        self.device_bytes = int(c.device_bytes)
+        self.rounds = int(c.rounds)
+        self.verified = int(c.verified)
+        self.seconds = dict(zip(self.STAGES, (float(x) for x in c.seconds)))
+
+
+def _text_args(text, lcp_chunk, verify, max_device_bytes):
+    text = np.ascontiguousarray(np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else text, np.uint8)
+    opts = TextBuildOptsC(lcp_chunk=int(lcp_chunk), verify=1 if verify else 0, max_device_bytes=int(max_device_bytes))
+    return text, opts
+
+
+def text_device_bytes(n):
+    """movi_text_device_bytes: the device bytes the plan of a text of n characters needs.  Host only."""
+    out = C.c_uint64(0)
+    check(lib().movi_text_device_bytes(int(n), C.byref(out)))
+    return out.value
+
+
+def rlbwt_from_text(text, lcp_chunk=0, verify=False, max_device_bytes=0, device=0):
+    """movi_rlbwt_from_text: (heads uint8, lens uint64, thr uint64, TextBuildStats) of the cleaned text (bytes or uint8, no byte 0,
+    without the terminator), built on the GPU: suffix array, BWT, LCP, thresholds in the .thr_pos convention."""
+    text, opts = _text_args(text, lcp_chunk, verify, max_device_bytes)
+    heads, lens, thr, r, st = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64(0), TextBuildStatsC()
+    check(lib().movi_rlbwt_from_text(int(device), text.ctypes.data, text.size, C.byref(opts), C.byref(heads), C.byref(lens), C.byref(thr),
+                                     C.byref(r), C.byref(st)))
+    try:
+        return (np.frombuffer(C.string_at(heads.value, r.value), np.uint8), np.frombuffer(C.string_at(lens.value, r.value * 8), np.uint64),
+                np.frombuffer(C.string_at(thr.value, r.value * 8), np.uint64), TextBuildStats(st))
+    finally:
+        for p in (heads, lens, thr):
+            lib().movi_host_free(p)
+
+
+def build_image_from_text(text, mode, lcp_chunk=0, verify=False, max_device_bytes=0, device=0, stats=None):
+    """movi_build_from_text: the bytes of index.movi of the cleaned text, everything on the GPU.  stats (optional): a list that
+    receives the call's TextBuildStats."""
+    text, opts = _text_args(text, lcp_chunk, verify, max_device_bytes)
+    img, nbytes, st = C.c_void_p(), C.c_size_t(0), TextBuildStatsC()
+    check(lib().movi_build_from_text(int(device), int(mode), text.ctypes.data, text.size, C.byref(opts), C.byref(img), C.byref(nbytes),
+                                     C.byref(st)))
+    if stats is not None:
+        stats.append(TextBuildStats(st))
     try:
         return C.string_at(img.value, nbytes.value)
     finally:

@@ -5,6 +5,8 @@
 // `movi build --preprocessed`: REF.bwt.heads + REF.bwt.len (+ REF.thr_pos) -> DIR/index.movi, the reference's route for texts the
 // in-memory constructor cannot take (an external BWT tool, then `movi rlbwt`, then this; src/move_structure_build.cpp:143-202,
 // src/utils.cpp:150-200).  The files are parsed and checked here; the table is built on the GPU (movi_build_from_rlbwt).
+// `movi build --gpu-build`: the FASTA's text as above, then suffix array, BWT, LCP, thresholds and the table on the GPU
+// (movi_build_from_text): texts up to 2^32 - 2^20 characters, no external tool.
 // `movi rlbwt`: build_rlbwt, src/movi.cpp:505-559.
 #define MOVI_BUILD_INDEX_NO_MAIN 1
 #include "../../tools/build_index.cpp"
@@ -84,6 +86,68 @@ int run_build_preprocessed(const Options &o, int mode) {
     return 0;
 }
 
+// `movi build --gpu-build`: the text as the CPU constructor cleans it, everything after it on the GPU.
+int run_build_gpu(const Options &o, int mode) {
+    std::vector<uint8_t> text;
+    std::vector<uint64_t> doc_ends;
+    if (!text_from_fasta(o.ref_file, o.separators, text, &doc_ends)) throw std::runtime_error("cannot open " + o.ref_file);
+    if (text.empty()) throw std::runtime_error("no sequence in " + o.ref_file);
+    movi_text_build_opts_t opts;
+    memset(&opts, 0, sizeof(opts));
+    opts.verify = o.verify ? 1u : 0u;
+    movi_text_build_stats_t st;
+    memset(&st, 0, sizeof(st));
+    const auto t0 = std::chrono::steady_clock::now();
+    void *image = nullptr;
+    size_t image_bytes = 0;
+    if (o.keep) {                                                  // the three arrays come down, are written, and go up again
+        uint8_t *heads = nullptr;
+        uint64_t *lens = nullptr, *thr = nullptr, R = 0;
+        if (movi_rlbwt_from_text(o.device, text.data(), text.size(), &opts, &heads, &lens, &thr, &R, &st) != MOVI_OK)
+            throw std::runtime_error(std::string("building the run-length BWT on the GPU: ") + movi_last_error());
+        std::ofstream hf(o.ref_file + ".bwt.heads", std::ios::binary), lf(o.ref_file + ".bwt.len", std::ios::binary),
+            tf(o.ref_file + ".thr_pos", std::ios::binary);
+        hf.write(reinterpret_cast<const char *>(heads), (std::streamsize)R);
+        for (uint64_t k = 0; k < R; k++) {                         // five little-endian bytes per run, as tools/build_index --emit-rlbwt
+            lf.write(reinterpret_cast<const char *>(&lens[k]), 5);
+            tf.write(reinterpret_cast<const char *>(&thr[k]), 5);
+        }
+        hf.close(); lf.close(); tf.close();
+        const bool files_ok = hf.good() && lf.good() && tf.good();
+        const int rc = files_ok ? movi_build_from_rlbwt(o.device, (uint32_t)mode, heads, lens, thr, R, &image, &image_bytes) : MOVI_OK;
+        (void)movi_host_free(heads);
+        (void)movi_host_free(lens);
+        (void)movi_host_free(thr);
+        if (!files_ok) throw std::runtime_error("cannot write " + o.ref_file + ".bwt.heads / .bwt.len / .thr_pos");
+        if (rc != MOVI_OK) throw std::runtime_error(std::string("building the index on the GPU: ") + movi_last_error());
+    } else if (movi_build_from_text(o.device, (uint32_t)mode, text.data(), text.size(), &opts, &image, &image_bytes, &st) != MOVI_OK) {
+        throw std::runtime_error(std::string("building the index on the GPU: ") + movi_last_error());
+    }
+    const auto t1 = std::chrono::steady_clock::now();
+    mkdir(o.index_dir.c_str(), 0777);
+    const std::string name = o.index_dir + "/index.movi";
+    std::ofstream f(name, std::ios::binary);
+    f.write(static_cast<const char *>(image), (std::streamsize)image_bytes);
+    f.close();
+    const bool ok = f.good();
+    (void)movi_host_free(image);
+    if (!ok) throw std::runtime_error("cannot write " + name);
+    if (o.color) {
+        std::ofstream d(o.index_dir + "/ref.fa.doc_offsets");
+        for (uint64_t e : doc_ends) d << e << "\n";
+        d.close();
+        if (!d.good()) throw std::runtime_error("cannot write " + o.index_dir + "/ref.fa.doc_offsets");
+    }
+    std::cerr << "[movi] The " << o.index_type << " index is written to " << name << "\n";
+    if (o.color) std::cerr << "[movi] The document offsets are written to " << o.index_dir << "/ref.fa.doc_offsets\n";
+    if (o.keep) std::cerr << "[movi] The run-length BWT and the thresholds are kept in " << o.ref_file << ".bwt.heads, .bwt.len and .thr_pos\n";
+    std::cerr << "[movi] built on the GPU: " << text.size() << " characters, " << st.original_r << " BWT runs, " << st.rounds
+              << " doubling rounds" << (st.verified ? ", verified" : "") << "; seconds: upload " << st.seconds[0] << ", suffix sort " << st.seconds[1]
+              << ", BWT and runs " << st.seconds[2] << ", LCP " << st.seconds[3] << ", thresholds " << st.seconds[4] << ", verify " << st.seconds[5]
+              << ", whole build " << std::chrono::duration<double>(t1 - t0).count() << "\n";
+    return 0;
+}
+
 }  // namespace
 
 // build_rlbwt, src/movi.cpp:505-559: FILE.heads (one byte per maximal run) and FILE.len (five little-endian bytes per run).  As there,
@@ -138,6 +202,7 @@ int run_build(const Options &o) {
         throw UsageError("index type '" + o.index_type + "' is not supported (regular-thresholds, blocked-thresholds, "
                          "sampled-thresholds, regular, blocked, sampled)");
     if (o.preprocessed) return run_build_preprocessed(o, mode);
+    if (o.gpu_build) return run_build_gpu(o, mode);
     const std::string err = movi_build_index_from_fasta(o.ref_file, mode, o.index_dir, o.separators, o.color);
     if (!err.empty()) throw std::runtime_error(err);
     std::cerr << "[movi] The " << o.index_type << " index is written to " << o.index_dir << "/index.movi\n";

@@ -29,6 +29,7 @@ const Spec kSpecs[] = {
     {"logs", 0, false},          {"mmap", 0, false},        {"gen-reads", 0, false},
     {"fasta", 'f', true},          {"separators", 0, false},  {"seg-len", 0, true},
     {"ahead-rows", 0, true},        {"sample-rate", 0, true},
+    {"gpu-build", 0, false},     {"verify", 0, false},      {"keep", 0, false},   // build on the GPU from the FASTA; the reference's --verify / --keep (src/movi_parser.cpp:105, :113)
     {"preprocessed", 0, false},  {"bwt-file", 0, true},     // build from a run-length BWT; movi rlbwt (src/movi_parser.cpp:112, :202-203)
     // Movi Color, default colour mode (src/movi_parser.cpp:119-121, 164-179, 193-199)
     {"multi-classify", 0, false}, {"min-len", 0, true},     {"report-all", 0, false},
@@ -98,6 +99,9 @@ std::string usage() {
            "       movi null -i DIR [--gen-reads -f REF.fasta] [--pml|--zml]\n"
            "       movi build -i DIR -f REF.fasta [--type regular-thresholds|blocked-thresholds|sampled-thresholds|regular|blocked|sampled]\n"
            "                  [--separators] [--color]\n"
+           "       movi build -i DIR -f REF.fasta --gpu-build [--type ...] [--separators] [--color] [--device D] [--verify] [--keep]\n"
+           "                  (suffix array, BWT, LCP and thresholds on the GPU: texts up to 2^32 - 2^20 characters; --verify checks them there;\n"
+           "                  --keep writes REF.fasta.bwt.heads, .bwt.len and .thr_pos for a later --preprocessed build of another type)\n"
            "       movi build -i DIR -f REF --preprocessed [--type ...] [--device D]   (REF.bwt.heads + REF.bwt.len [+ REF.thr_pos] -> DIR/index.movi,\n"
            "                  built on the GPU; --separators is recognised from the alphabet)\n"
            "       movi rlbwt --bwt-file FILE   (FILE -> FILE.heads + FILE.len)\n";
@@ -285,6 +289,13 @@ Options parse_args(int argc, char **argv) {
         o.preprocessed = has("preprocessed");                     // src/movi_parser.cpp:289-291
         if (o.preprocessed && o.color)
             throw UsageError("--color cannot be combined with --preprocessed: the document offsets come from the FASTA, which is not read");
+        o.gpu_build = has("gpu-build");
+        o.verify = has("verify");
+        o.keep = has("keep");
+        if (o.gpu_build && o.preprocessed)
+            throw UsageError("--gpu-build cannot be combined with --preprocessed: one builds from the FASTA, the other from a run-length BWT");
+        if ((o.verify || o.keep) && !o.gpu_build)
+            throw UsageError(std::string(o.verify ? "--verify" : "--keep") + " belongs to --gpu-build");
     } else if (o.command == "rlbwt") {
         // src/movi_parser.cpp:440-446
         if (seen["bwt-file"].size() != 1) throw UsageError("Please specify one bwt file.");

@@ -19,6 +19,9 @@ struct Options {
     std::string index_type = "regular-thresholds";   // build --type (DEFAULT_INDEX_TYPE, src/movi_launcher.cpp:17)
     bool separators = false;      // build --separators
     bool preprocessed = false;    // build --preprocessed: REF.bwt.heads + REF.bwt.len (+ REF.thr_pos) instead of a FASTA, built on the GPU
+    bool gpu_build = false;       // build --gpu-build: suffix array, BWT, LCP and thresholds of the FASTA's text on the GPU, then the table there too
+    bool verify = false;          // build --gpu-build --verify: the builder's verify stage (src/movi_parser.cpp:105)
+    bool keep = false;            // build --gpu-build --keep: REF.bwt.heads, REF.bwt.len and REF.thr_pos stay beside the FASTA (:113)
     std::string bwt_file;         // rlbwt --bwt-file
     bool gen_reads = false;       // null --gen-reads
     bool pml = true;              // default query type (movi_options.hpp:243)
@@ -72,7 +75,7 @@ struct UsageError : std::runtime_error {
 // Throws UsageError with the reference's message texts where they exist.
 Options parse_args(int argc, char **argv);
 std::string usage();
-int run_build(const Options &o);  // build_cmd.cpp (writes DIR/ref.fa.doc_offsets too when o.color; --preprocessed: from a run-length BWT)
+int run_build(const Options &o);  // build_cmd.cpp (writes DIR/ref.fa.doc_offsets too when o.color; --preprocessed: from a run-length BWT; --gpu-build: from the FASTA on the GPU)
 int run_rlbwt(const Options &o);  // build_cmd.cpp
 
 }  // namespace movi_host
