@@ -1,20 +1,20 @@
 // build_cmd.cpp -- `movi build`: FASTA -> DIR/index.movi, in memory, without the reference's external pipeline
 // (prepare_ref + pfp-thresholds + movi-<type> build, src/movi_launcher.cpp:190-242).  The constructor is the one the tests
-// hold to the reference's index-size known answers (tools/build_index.cpp: SA-IS, Kasai LCP, leftmost-minimum
-// thresholds, rows, blocked / sampled ids), compiled into the host binary; texts up to 2^31 characters.
+// hold to the reference's index-size known answers (constructor.hpp: SA-IS, Kasai LCP, leftmost-minimum thresholds, the
+// run-length BWT, rows, blocked / sampled ids), compiled into the host binary; texts up to 2^31 characters.
 // `movi build --preprocessed`: REF.bwt.heads + REF.bwt.len (+ REF.thr_pos) -> DIR/index.movi, the reference's route for texts the
 // in-memory constructor cannot take (an external BWT tool, then `movi rlbwt`, then this; src/move_structure_build.cpp:143-202,
 // src/utils.cpp:150-200).  The files are parsed and checked here; the table is built on the GPU (movi_build_from_rlbwt).
 // `movi build --gpu-build`: the FASTA's text as above, then suffix array, BWT, LCP, thresholds and the table on the GPU
 // (movi_build_from_text): texts up to 2^32 - 2^20 characters, no external tool.
 // `movi rlbwt`: build_rlbwt, src/movi.cpp:505-559.
-#define MOVI_BUILD_INDEX_NO_MAIN 1
-#include "../../tools/build_index.cpp"
-
 #include <chrono>
+#include <iostream>
+#include <memory>
 
 #include "../../include/movi_hip.h"
 #include "../csrc/movi_build.hpp"
+#include "constructor.hpp"
 #include "options.hpp"
 #include "reads.hpp"
 
@@ -22,129 +22,99 @@ namespace movi_host {
 
 namespace {
 
-uint64_t get5(const uint8_t *p) {                                  // a 5-byte little-endian value
-    uint64_t v = 0;
-    memcpy(&v, p, 5);
-    return v;
+using namespace movi_constructor;
+
+struct HostFree { void operator()(void *p) const { (void)movi_host_free(p); } };   // what the engine hands out (movi_host_alloc)
+template <typename T> using HostPtr = std::unique_ptr<T, HostFree>;
+
+double seconds_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+
+// The FASTA's text as the CPU constructor cleans it, and where its documents end.
+std::vector<uint8_t> read_text(const Options &o, std::vector<uint64_t> &doc_ends) {
+    std::vector<uint8_t> text;
+    if (!text_from_fasta(o.ref_file, o.separators, text, &doc_ends)) throw std::runtime_error("cannot open " + o.ref_file);
+    if (text.empty()) throw std::runtime_error("no sequence in " + o.ref_file);
+    return text;
+}
+
+// The table of a run-length BWT that has passed rlbwt_check, built on the GPU.
+HostPtr<void> gpu_image(const Options &o, int mode, const uint8_t *heads, const uint64_t *lens, const uint64_t *thr, uint64_t R, size_t &bytes) {
+    void *image = nullptr;
+    if (movi_build_from_rlbwt(o.device, (uint32_t)mode, heads, lens, thr, R, &image, &bytes) != MOVI_OK)
+        throw std::runtime_error(std::string("building the index on the GPU: ") + movi_last_error());
+    return HostPtr<void>(image);
+}
+
+void report(const Options &o) {
+    std::cerr << "[movi] The " << o.index_type << " index is written to " << o.index_dir << "/index.movi\n";
+    if (o.color) std::cerr << "[movi] The document offsets are written to " << o.index_dir << "/ref.fa.doc_offsets\n";
+}
+
+int run_build_cpu(const Options &o, int mode) {
+    std::vector<uint64_t> doc_ends;
+    std::vector<uint8_t> text = read_text(o, doc_ends);
+    if ((uint64_t)text.size() + 1 >= (1ull << 31))
+        throw std::runtime_error("text too long for the in-memory constructor (2^31 characters, reverse complements included)");
+    const std::vector<uint8_t> image = image_from_rlbwt(rlbwt_from_text(text), mode);
+    write_index_dir(o.index_dir, image.data(), image.size(), o.color ? &doc_ends : nullptr);
+    report(o);
+    return 0;
 }
 
 int run_build_preprocessed(const Options &o, int mode) {
-    const std::string heads_path = o.ref_file + ".bwt.heads", len_path = o.ref_file + ".bwt.len", thr_path = o.ref_file + ".thr_pos";
     const bool with_thr = movi::build_mode_thresholds((uint32_t)mode);
-    // compute_length_from_bwt, src/move_structure_build.cpp:152-181
-    InputMapping heads_map, len_map, thr_map;
-    if (!std::ifstream(heads_path).good()) throw std::runtime_error("[build] Failed to open the heads file: " + heads_path);
-    if (!heads_map.map(heads_path)) throw std::runtime_error(heads_path + ": holds no run");
-    if (!std::ifstream(len_path).good()) throw std::runtime_error("[build] Failed to open the len file: " + len_path);
-    (void)len_map.map(len_path);
-    const uint64_t R = heads_map.n, len_bytes = len_map.p != MAP_FAILED ? len_map.n : 0;
-    if (len_bytes % 5 != 0) throw std::runtime_error(len_path + ": " + std::to_string(len_bytes) + " bytes is not a multiple of 5 (one 5-byte length per run)");
-    if (len_bytes / 5 != R)
-        throw std::runtime_error(len_path + " holds " + std::to_string(len_bytes / 5) + " lengths but " + heads_path + " holds " + std::to_string(R) + " run heads");
-    std::vector<uint64_t> lens(R), thr;
-    for (uint64_t k = 0; k < R; k++) lens[k] = get5(len_map.bytes() + 5 * k);
-    if (with_thr) {                                                // read_thresholds, src/utils.cpp:150-200; not opened for the other types
-        if (!std::ifstream(thr_path).good()) throw std::runtime_error("[read_thresholds] open() file " + thr_path + " failed");
-        (void)thr_map.map(thr_path);
-        const uint64_t thr_bytes = thr_map.p != MAP_FAILED ? thr_map.n : 0;
-        if (thr_bytes % 5 != 0)
-            throw std::runtime_error("[read_thresholds] invilid file " + thr_path + ": " + std::to_string(thr_bytes) + " bytes is not a multiple of 5");
-        if (thr_bytes / 5 != R)
-            throw std::runtime_error(thr_path + " holds " + std::to_string(thr_bytes / 5) + " thresholds but " + heads_path + " holds " + std::to_string(R) + " run heads");
-        thr.resize(R);
-        // when the thresholds overflow 5 bytes the reference recovers the true values: a sudden drop to less than a tenth of the last
-        // value, which was not small itself, is one more wrap (:172-196; unsigned arithmetic as there)
-        const uint64_t kMax5 = 1ull << 40;
-        uint64_t wraps = 0;
-        for (uint64_t k = 0; k < R; k++) {
-            const uint64_t t = get5(thr_map.bytes() + 5 * k);
-            if (k > 0 && t != 0 && t < (thr[k - 1] - wraps * kMax5) / 10 && (thr[k - 1] - wraps * kMax5) > kMax5 / 10) wraps += 1;
-            thr[k] = t + wraps * kMax5;
-        }
-    }
+    const Rlbwt rl = read_rlbwt_files(o.ref_file, with_thr);
+    const uint64_t R = rl.heads.size(), *thr = with_thr ? rl.thr.data() : nullptr;
     movi::RlbwtInfo info;
     movi::RlbwtArray which;
     std::string why;
-    if (!movi::rlbwt_check(heads_map.bytes(), lens.data(), with_thr ? thr.data() : nullptr, R, info, which, why))
-        throw std::runtime_error((which == movi::kRlbwtHeads ? heads_path : which == movi::kRlbwtLens ? len_path : thr_path) + ": " + why);
+    if (!movi::rlbwt_check(rl.heads.data(), rl.lens.data(), thr, R, info, which, why))
+        throw std::runtime_error(o.ref_file + (which == movi::kRlbwtHeads ? ".bwt.heads" : which == movi::kRlbwtLens ? ".bwt.len" : ".thr_pos") + ": " + why);
     const auto t0 = std::chrono::steady_clock::now();
-    void *image = nullptr;
     size_t image_bytes = 0;
-    if (movi_build_from_rlbwt(o.device, (uint32_t)mode, heads_map.bytes(), lens.data(), with_thr ? thr.data() : nullptr, R, &image, &image_bytes) != MOVI_OK)
-        throw std::runtime_error(std::string("building the index on the GPU: ") + movi_last_error());
-    const auto t1 = std::chrono::steady_clock::now();
-    mkdir(o.index_dir.c_str(), 0777);
-    const std::string name = o.index_dir + "/index.movi";
-    std::ofstream f(name, std::ios::binary);
-    f.write(static_cast<const char *>(image), (std::streamsize)image_bytes);
-    f.close();
-    const bool ok = f.good();
-    (void)movi_host_free(image);
-    if (!ok) throw std::runtime_error("cannot write " + name);
+    const HostPtr<void> image = gpu_image(o, mode, rl.heads.data(), rl.lens.data(), thr, R, image_bytes);
+    const double build_s = seconds_since(t0);
+    write_index_dir(o.index_dir, image.get(), image_bytes, nullptr);
     std::cerr << "[movi] The " << o.index_type << " index (" << R << " BWT runs, " << info.n << " characters" << (info.sep ? ", separators" : "")
-              << ") is written to " << name << " (build on the GPU " << std::chrono::duration<double>(t1 - t0).count() << " s)\n";
+              << ") is written to " << o.index_dir << "/index.movi (build on the GPU " << build_s << " s)\n";
     return 0;
 }
 
 // `movi build --gpu-build`: the text as the CPU constructor cleans it, everything after it on the GPU.
 int run_build_gpu(const Options &o, int mode) {
-    std::vector<uint8_t> text;
     std::vector<uint64_t> doc_ends;
-    if (!text_from_fasta(o.ref_file, o.separators, text, &doc_ends)) throw std::runtime_error("cannot open " + o.ref_file);
-    if (text.empty()) throw std::runtime_error("no sequence in " + o.ref_file);
+    const std::vector<uint8_t> text = read_text(o, doc_ends);
     movi_text_build_opts_t opts;
     memset(&opts, 0, sizeof(opts));
     opts.verify = o.verify ? 1u : 0u;
     movi_text_build_stats_t st;
     memset(&st, 0, sizeof(st));
     const auto t0 = std::chrono::steady_clock::now();
-    void *image = nullptr;
+    HostPtr<void> image;
     size_t image_bytes = 0;
     if (o.keep) {                                                  // the three arrays come down, are written, and go up again
         uint8_t *heads = nullptr;
         uint64_t *lens = nullptr, *thr = nullptr, R = 0;
         if (movi_rlbwt_from_text(o.device, text.data(), text.size(), &opts, &heads, &lens, &thr, &R, &st) != MOVI_OK)
             throw std::runtime_error(std::string("building the run-length BWT on the GPU: ") + movi_last_error());
-        std::ofstream hf(o.ref_file + ".bwt.heads", std::ios::binary), lf(o.ref_file + ".bwt.len", std::ios::binary),
-            tf(o.ref_file + ".thr_pos", std::ios::binary);
-        hf.write(reinterpret_cast<const char *>(heads), (std::streamsize)R);
-        for (uint64_t k = 0; k < R; k++) {                         // five little-endian bytes per run, as tools/build_index --emit-rlbwt
-            lf.write(reinterpret_cast<const char *>(&lens[k]), 5);
-            tf.write(reinterpret_cast<const char *>(&thr[k]), 5);
-        }
-        hf.close(); lf.close(); tf.close();
-        const bool files_ok = hf.good() && lf.good() && tf.good();
-        const int rc = files_ok ? movi_build_from_rlbwt(o.device, (uint32_t)mode, heads, lens, thr, R, &image, &image_bytes) : MOVI_OK;
-        (void)movi_host_free(heads);
-        (void)movi_host_free(lens);
-        (void)movi_host_free(thr);
-        if (!files_ok) throw std::runtime_error("cannot write " + o.ref_file + ".bwt.heads / .bwt.len / .thr_pos");
-        if (rc != MOVI_OK) throw std::runtime_error(std::string("building the index on the GPU: ") + movi_last_error());
-    } else if (movi_build_from_text(o.device, (uint32_t)mode, text.data(), text.size(), &opts, &image, &image_bytes, &st) != MOVI_OK) {
-        throw std::runtime_error(std::string("building the index on the GPU: ") + movi_last_error());
+        const HostPtr<uint8_t> heads_owner(heads);
+        const HostPtr<uint64_t> lens_owner(lens), thr_owner(thr);
+        write_rlbwt_files(o.ref_file, heads, lens, thr, R);
+        image = gpu_image(o, mode, heads, lens, thr, R, image_bytes);
+    } else {
+        void *p = nullptr;
+        if (movi_build_from_text(o.device, (uint32_t)mode, text.data(), text.size(), &opts, &p, &image_bytes, &st) != MOVI_OK)
+            throw std::runtime_error(std::string("building the index on the GPU: ") + movi_last_error());
+        image.reset(p);
     }
-    const auto t1 = std::chrono::steady_clock::now();
-    mkdir(o.index_dir.c_str(), 0777);
-    const std::string name = o.index_dir + "/index.movi";
-    std::ofstream f(name, std::ios::binary);
-    f.write(static_cast<const char *>(image), (std::streamsize)image_bytes);
-    f.close();
-    const bool ok = f.good();
-    (void)movi_host_free(image);
-    if (!ok) throw std::runtime_error("cannot write " + name);
-    if (o.color) {
-        std::ofstream d(o.index_dir + "/ref.fa.doc_offsets");
-        for (uint64_t e : doc_ends) d << e << "\n";
-        d.close();
-        if (!d.good()) throw std::runtime_error("cannot write " + o.index_dir + "/ref.fa.doc_offsets");
-    }
-    std::cerr << "[movi] The " << o.index_type << " index is written to " << name << "\n";
-    if (o.color) std::cerr << "[movi] The document offsets are written to " << o.index_dir << "/ref.fa.doc_offsets\n";
+    const double build_s = seconds_since(t0);
+    write_index_dir(o.index_dir, image.get(), image_bytes, o.color ? &doc_ends : nullptr);
+    report(o);
     if (o.keep) std::cerr << "[movi] The run-length BWT and the thresholds are kept in " << o.ref_file << ".bwt.heads, .bwt.len and .thr_pos\n";
     std::cerr << "[movi] built on the GPU: " << text.size() << " characters, " << st.original_r << " BWT runs, " << st.rounds
               << " doubling rounds" << (st.verified ? ", verified" : "") << "; seconds: upload " << st.seconds[0] << ", suffix sort " << st.seconds[1]
               << ", BWT and runs " << st.seconds[2] << ", LCP " << st.seconds[3] << ", thresholds " << st.seconds[4] << ", verify " << st.seconds[5]
-              << ", whole build " << std::chrono::duration<double>(t1 - t0).count() << "\n";
+              << ", whole build " << build_s << "\n";
     return 0;
 }
 
@@ -203,11 +173,7 @@ int run_build(const Options &o) {
                          "sampled-thresholds, regular, blocked, sampled)");
     if (o.preprocessed) return run_build_preprocessed(o, mode);
     if (o.gpu_build) return run_build_gpu(o, mode);
-    const std::string err = movi_build_index_from_fasta(o.ref_file, mode, o.index_dir, o.separators, o.color);
-    if (!err.empty()) throw std::runtime_error(err);
-    std::cerr << "[movi] The " << o.index_type << " index is written to " << o.index_dir << "/index.movi\n";
-    if (o.color) std::cerr << "[movi] The document offsets are written to " << o.index_dir << "/ref.fa.doc_offsets\n";
-    return 0;
+    return run_build_cpu(o, mode);
 }
 
 }  // namespace movi_host

@@ -1,5 +1,5 @@
-"""CPU suite: the C++ index constructor (tools/build_index.cpp: SA-IS + Kasai + thresholds + rows)
-against the KAT-pinned fixtures and against the numpy constructor of the oracle."""
+"""CPU suite: the C++ index constructor (movi_amd/host/constructor.hpp: SA-IS + Kasai + thresholds -> run-length BWT -> rows), through
+its stand-alone tool tools/build_index, against the KAT-pinned fixtures and against the numpy constructor of the oracle."""
 import os
 import subprocess
 
@@ -106,6 +106,37 @@ def test_regular_and_blocked_known_answers_and_numpy_agreement(tool, tmp_path, m
     assert len(img) == size
     ref = B.read_fasta(os.path.join(GOLDEN, "ref.fasta"))[0][1]
     assert img == B.build_index_from_seqs([ref], mode, separators=separators)
+
+
+def test_long_runs_cut_from_run_starts_and_from_thresholds(tool, tmp_path):
+    """Two records with T stretches of 4200 and 6400: BWT runs longer than every type's MAX_RUN_LENGTH (4095 at most), so every type
+    cuts rows by length, and one threshold that lies one position inside a run of 2200, so the types with thresholds count 511 / 1023 /
+    2047 from that cut and not from the run's start.  (The shorter stretch starts behind a G and ends in CA, the longer one ends in CC:
+    behind that G's suffix the LCP is 4201, then 4200, then rises to the end of the BWT, where the longer stretch's own G gets the
+    position of the 4200 as its threshold.)  Images against the numpy constructor, the run files against its BWT and thresholds."""
+    from oracle import build_index as B
+    from test_build_rlbwt_cpu import five, rle
+    rng = np.random.default_rng(5)
+    a, b, c = (bytes(rng.choice(list(b"ACGT"), k).astype(np.uint8)) for k in (500, 300, 200))
+    seqs = [a + b"G" + b"T" * 4200 + b"CA" + b, c + b"G" + b"T" * 6400 + b"CC" + a[:100]]
+    fa = tmp_path / "long.fa"
+    fa.write_bytes(b"".join(b">r%d\n%s\n" % (i, s) for i, s in enumerate(seqs)))
+    bwt, thr = B.bwt_and_thresholds(B.clean_text(seqs))
+    heads, lens = rle(bwt)
+    t, ends = np.asarray(thr, np.int64), np.cumsum(lens.astype(np.int64))
+    starts = ends - lens.astype(np.int64)
+    run_of = np.searchsorted(starts, t, side="right") - 1
+    inside = t - starts[run_of]                                       # how far into its run a threshold lies
+    assert lens.max() > 4095 and ((inside > 0) & (ends[run_of] - t > 2047) & (inside % 511 != 0)).any()
+    prefix = str(tmp_path / "ref")
+    for mode in (6, 7, 8, 3, 2, 5):
+        out = str(tmp_path / ("o%d" % mode))
+        subprocess.check_call([tool, "fasta", str(fa), str(mode), out, "--emit-rlbwt", prefix], stderr=subprocess.DEVNULL)
+        assert open(os.path.join(out, "index.movi"), "rb").read() == B.build_index_from_seqs(seqs, mode), mode
+        assert open(prefix + ".bwt.heads", "rb").read() == heads.tobytes() and open(prefix + ".bwt.len", "rb").read() == five(lens)
+        assert open(prefix + ".thr_pos", "rb").read() == five(thr)
+        for ext in (".bwt.heads", ".bwt.len", ".thr_pos"):
+            os.remove(prefix + ext)
 
 
 def test_pangenome_mode_is_queryable(tool, tmp_path):
