@@ -542,6 +542,49 @@ int movi_kmer_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_o
                    uint32_t *h_n_runs, uint32_t *h_found, movi_kmer_run_t *h_runs, uint64_t runs_cap, uint64_t *n_runs_total,
                    movi_query_stats_t *stats);
 
+/* ---- k-mer occurrences ------------------------------------------------------------ */
+
+/* `movi query --kmer-occ [-k K]`: how often every k-mer of a read occurs in the indexed text.  This is NOT the reference's
+ * --kmer-count (src/sequitur.cpp:14-255: a bidirectional-search experiment on a --separators index that prints two totals and
+ * its skipping counters), which stays refused; the contract here is stated on occurrences in the text.
+ *
+ * Terms.  Read P of length m, k >= 1, all = max(0, m - k + 1).  A base is legal when the search would look it up (A, C, G, T).
+ * For 0 <= p < all:
+ *     occ[p] = the number of occurrences of P[p .. p+k) in the indexed text   if its k bases are all legal
+ *            = 0                                                              otherwise
+ * -- the `count` movi_count_device reports for that k-mer as a read of its own when its `matched` is k, and 0 when matched < k.
+ * Occurrences across the record junctions of an index built without --separators count, exactly as they do there.
+ *     found = #{ p : occ[p] > 0 },   sum = the sum of occ[p] (64 bits).
+ * The answers depend neither on whether an interval table is used ("ftab_k"), nor on its K, nor on the row-index width ("idx64").
+ *
+ * Device layout: d_occ[offsets[i] + p] = occ[p] of read i for p < all; the read's other k - 1 slots are 0, so every one of the
+ * n_bases slots is defined.  n_bases must EQUAL offsets[n_reads], as for movi_sa_entries_device.  (The offsets live on the device,
+ * so a wrong n_bases cannot be refused; the call stays inside its buffers whatever it is: no slot at or past n_bases is touched, no
+ * base there is read, a read that reaches past n_bases gets no k-mer and 0xFF in d_read_err, and slots past offsets[n_reads] are
+ * left as they were.)  d_found, d_sum and d_read_err (per read) are each optional.  There is no d_read_order: work is handed out
+ * per k-mer, not per read -- a lane owns the slots lane, lane + stride, ... and takes up its next slot when a search ends, like
+ * movi_locate_device's lists --, so there is nothing to reorder.
+ * A k-mer whose search hits one of the reference's LF throws (a corrupt table) becomes an ERROR SLOT: ~0xFF | the code, bit 63
+ * set, which no count has (MOVI_OCC_IS_ERROR); it is counted in movi_last_stats' `errors`, and its read reports that code -- its
+ * first error slot's -- in d_read_err[i] and found = sum = 0.  A corrupt table ends the call, it does not hang it.
+ * k == 0, NULL required buffers and more than 2^32 reads: MOVI_ERR_ARG.  Asynchronous on `stream`.  The call uses the count query's
+ * derived tables only (row-start checkpoints, interval table) and no scratch: after movi_index_prepare(MOVI_PREPARE_COUNT) it
+ * allocates and builds nothing and may be captured into a graph without a warm-up call.  movi_last_launch names the occurrence
+ * kernel; movi_last_stats: lane_steps = interval steps taken, wave_steps = iterations of the wavefronts (lane_steps /
+ * (64 * wave_steps) = the occupancy of the strided lists). */
+#define MOVI_OCC_IS_ERROR(v) (((uint64_t)(v) >> 63) != 0)    /* an error slot: ~0xFF | kErr code of the LF move that threw */
+
+int movi_kmer_occ_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                         uint32_t k, uint64_t *d_occ, uint32_t *d_found, uint64_t *d_sum, uint8_t *d_read_err, void *stream);
+
+/* Host form: h_occ in the same layout relative to h_offsets[0] (h_occ[h_offsets[i] - h_offsets[0] + p]); h_found, h_sum and
+ * h_read_err per read, each optional.  Runs chunk by chunk through the handle's staging, synchronously, like
+ * movi_sa_entries_host (8 bytes per base come down); a chunk is a stretch of reads of about 2^26 bases, or of "pipe_chunk_bases"
+ * where that option is set.  A k-mer that became an error slot makes the call return MOVI_ERR_INVARIANT after everything else
+ * was answered. */
+int movi_kmer_occ_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint32_t k,
+                       uint64_t *h_occ, uint32_t *h_found, uint64_t *h_sum, uint8_t *h_read_err, movi_query_stats_t *stats);
+
 /* ---- locate: suffix-array entries from a sampled suffix array ------------------- */
 
 /* `movi build-SA` and `movi query --sa-entries`: where in the indexed text a match lies.

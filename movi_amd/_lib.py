@@ -150,6 +150,10 @@ SYMBOLS = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "movi_kmer_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(QueryStatsC)]),
+    "movi_kmer_occ_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "movi_kmer_occ_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.POINTER(QueryStatsC)]),
     "movi_ssa_build": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "movi_ssa_save": (C.c_int, [C.c_void_p, C.c_char_p]),
     "movi_ssa_load": (C.c_int, [C.c_void_p, C.c_char_p]),

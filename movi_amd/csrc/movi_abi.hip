@@ -2583,6 +2583,8 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
     if (what & MOVI_PREPARE_COUNT) {
         const int rc = count_tables(ix, s, true);
         if (rc) return rc;
+        (void)preload_kmer_occ(ix->kmode, ix->dev.idx32 != 0);          // (movi_kmer_occ_device captured without a warm-up call)
+        (void)hipGetLastError();
     }
     if (what & MOVI_PREPARE_SA) {
         // the sampled suffix array and the locate rows were built when it was attached: only the kernels' code object is loaded here
@@ -2770,6 +2772,68 @@ int movi_kmer_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_o
                        [&](const uint8_t *db, const uint64_t *dof, uint64_t nr, uint64_t nb, void *d_out, uint32_t *d_n, uint8_t *d_err) {
                            return kmer_device(ix, db, dof, nr, nb, k, static_cast<movi_kmer_run_t *>(d_out), d_n, d_n + nr, d_err, nullptr, nullptr);
                        });
+}
+
+}  // extern "C"
+
+// -------------------------------------------------------------------------- k-mer occurrences
+
+namespace {
+
+int kmer_occ_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases, uint32_t k,
+                    uint64_t *d_occ, uint32_t *d_found, uint64_t *d_sum, uint8_t *d_read_err, hipStream_t s, DevStats *d_stats) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (k == 0) return fail(MOVI_ERR_ARG, "k must be at least 1");
+    if (n_reads == 0) return MOVI_OK;
+    if (!d_offsets || (n_bases && (!d_bases || !d_occ))) return fail(MOVI_ERR_ARG, "NULL device buffer");
+    if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
+    HIP_TRY(hipSetDevice(ix->device));
+    if (!d_stats) d_stats = ix->d_stats.get();
+    int rc = count_tables(ix, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(d_stats, 0, sizeof(DevStats), s));
+    HIP_TRY(launch_kmer_occ(ix->kmode, ix->dev, k, d_bases, d_offsets, n_reads, n_bases, d_occ, d_found, d_sum, d_read_err, d_stats,
+                            ix->cfg.num_cus, s, &ix->last_launch));
+    return MOVI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int movi_kmer_occ_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, uint64_t n_bases,
+                         uint32_t k, uint64_t *d_occ, uint32_t *d_found, uint64_t *d_sum, uint8_t *d_read_err, void *stream) {
+    return kmer_occ_device(ix, d_bases, d_offsets, n_reads, n_bases, k, d_occ, d_found, d_sum, d_read_err, static_cast<hipStream_t>(stream),
+                           nullptr);
+}
+
+int movi_kmer_occ_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint32_t k,
+                       uint64_t *h_occ, uint32_t *h_found, uint64_t *h_sum, uint8_t *h_read_err, movi_query_stats_t *stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (k == 0) return fail(MOVI_ERR_ARG, "k must be at least 1");
+    if (n_reads == 0) return MOVI_OK;
+    if (!h_offsets || (h_offsets[n_reads] != h_offsets[0] && (!h_bases || !h_occ))) return fail(MOVI_ERR_ARG, "NULL host buffer");
+    if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
+    HIP_TRY(hipSetDevice(ix->device));
+    uint64_t *d_occ = nullptr, *d_sum = nullptr;
+    uint32_t *d_found = nullptr;
+    auto launch = [&](ChunkCtx &c, const HostChunk &k_, const uint8_t *db, const uint64_t *dof, uint8_t *derr) -> int {
+        HIP_TRY(c.alloc(movi_index::kS, k_.nb * 8, &d_occ));
+        if (h_found) HIP_TRY(c.alloc(movi_index::kA, k_.nr * 4, &d_found));
+        if (h_sum) HIP_TRY(c.alloc(movi_index::kB, k_.nr * 8, &d_sum));
+        return kmer_occ_device(ix, db, dof, k_.nr, k_.nb, k, d_occ, h_found ? d_found : nullptr, h_sum ? d_sum : nullptr, derr, c.s, c.d_stats);
+    };
+    auto fetch = [&](ChunkCtx &c, const HostChunk &k_) -> int {
+        HIP_TRY(c.down(h_occ + (k_.b0 - h_offsets[0]), d_occ, k_.nb * 8));
+        if (h_found) HIP_TRY(c.down(h_found + k_.first, d_found, k_.nr * 4));
+        if (h_sum) HIP_TRY(c.down(h_sum + k_.first, d_sum, k_.nr * 8));
+        return MOVI_OK;
+    };
+    auto harvest = [](const uint8_t *, const HostChunk &, HostPool::Group *, bool) {};
+    AutoPin pins[2];                                         // (kKmerOcc: chunk by chunk, synchronously)
+    return run_host(ix, plan_reads_call(ix, HostQuery::kKmerOcc, h_bases, h_offsets, n_reads, 0, false, pins), h_bases, h_offsets, h_read_err,
+                    stats, launch, fetch, harvest);
 }
 
 }  // extern "C"

@@ -29,7 +29,9 @@ constexpr uint64_t kPipeTargetChunks = 8;
 constexpr uint64_t kPipeMaskChunks = 16;
 // Queries whose per-read results vary in length (MEMs, k-mer runs; run_compact) go through the handle's staging in chunks of about
 // kCompactChunkBases bases (at least kCompactChunkReads reads, at most kCompactMaxChunkBases: the device stages elem_bytes per base,
-// twice -- the kernel's output and its compacted copy).
+// twice -- the kernel's output and its compacted copy).  The k-mer occurrence query (8 bytes per base staged on the device, work handed
+// out per k-mer: no minimum of reads) goes through it in chunks of kKmerOccChunkBases bases, or of "pipe_chunk_bases" where that is set.
+constexpr uint64_t kKmerOccChunkBases = 1ull << 26;
 constexpr uint64_t kCompactChunkBases = 1ull << 25;
 constexpr uint64_t kCompactChunkReads = 1ull << 18;
 constexpr uint64_t kCompactMaxChunkBases = 1ull << 27;
@@ -100,7 +102,8 @@ enum class HostQuery {
     kSaEntries,      // 8 bytes per base come down, the locate walk is ~100 gathers per base: synchronous, nothing to overlap
     kPerRead,        // count, classify: per-read results, only the upload to hide
     kMultiClassify,  // per-read results, and the PML vector where the caller wants it (then synchronous); never page-locks by itself
-    kCompact         // MEMs, k-mer runs (run_compact): synchronous, chunks of their own size
+    kCompact,        // MEMs, k-mer runs (run_compact): synchronous, chunks of their own size
+    kKmerOcc         // 8 bytes per base come down and a lane owns k-mers, not reads: synchronous, chunks by bases alone
 };
 enum class HostRoute { kVector = 0, kMasks = 1, kMixed = 2 };
 
@@ -163,6 +166,7 @@ struct HostCall {
         small_bytes = facts.small_bytes;
         rule = CutRule();
         if (facts.query == HostQuery::kCompact) { rule.target = kCompactChunkBases; rule.min_reads = kCompactChunkReads; rule.max_bases = kCompactMaxChunkBases; }
+        if (facts.query == HostQuery::kKmerOcc) { rule.target = opt.pipe_chunk_bases ? opt.pipe_chunk_bases : kKmerOccChunkBases; rule.min_reads = 1; }
         if (!overlapped) return;
         // (calls whose results -- all or part of them -- come down as reset masks for the host's worker pool are cut twice as fine: the pool's
         // work arrives earlier and more evenly; 1 M x 150 bp: masks alone 22.9 -> 32.4 Gbases/s, both ways down 30 -> 33.9; finer still and

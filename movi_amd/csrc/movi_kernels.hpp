@@ -419,6 +419,14 @@ hipError_t launch_kmer(int mode, const DevIndex &ix, const KmerArgs &a, const ui
                        uint64_t n_reads, KmerRun *d_runs, uint32_t *d_n_runs, uint32_t *d_found, uint8_t *d_err,
                        DevStats *d_stats, const uint32_t *d_order, hipStream_t stream, LaunchInfo *info);
 
+// k-mer occurrences (movi_walk_kmer_occ.hip): d_occ[offsets[i] + p] = occurrences of the k-mer at p of read i, over all n_bases slots;
+// d_found / d_sum / d_err per read, each optional.  Mark, search and reduction, three kernels on `stream`; no scratch.
+constexpr int kKmerOccWaves = 16;    // kmer_occ_kernel: one-wavefront blocks per CU a launch fills at most (a lane then owns a list of slots)
+hipError_t launch_kmer_occ(int mode, const DevIndex &ix, uint32_t k, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
+                           uint64_t n_bases, uint64_t *d_occ, uint32_t *d_found, uint64_t *d_sum, uint8_t *d_err, DevStats *d_stats,
+                           int num_cus, hipStream_t stream, LaunchInfo *info);
+hipError_t preload_kmer_occ(int mode, bool idx32);   // load the translation unit's code object now (movi_index_prepare)
+
 // Locate (movi_walk_sa.hip; MoveStructure::get_SA_entries, src/move_structure.cpp:35-48; the layouts are stated in movi_sa.hpp).
 constexpr int kLocateWaves = 16;     // locate_kernel: one-wavefront blocks per CU a launch fills at most (a lane then owns a list of items)
 struct LocArgs {

@@ -7,6 +7,7 @@ Reference seam (file:line under /root/reference) -> here:
   MoveStructure::query_backward_search src/move_structure_search.cpp:340  -> MoveIndex.query_count
   MoveStructure::query_mems           src/mem_finder.cpp:7-145           -> MoveIndex.query_mems
   MoveStructure::query_all_kmers      src/sequitur.cpp:322-421           -> MoveIndex.query_kmers
+  (no reference seam: occurrences per k-mer, include/movi_hip.h)        -> MoveIndex.query_kmer_occ
   MoveStructure::get_SA_entries       src/move_structure.cpp:35-48       -> MoveIndex.locate / query_sa_entries
   MoveStructure::find_sampled_SA_entries src/move_structure_build.cpp:1174 -> MoveIndex.build_ssa (save_ssa / load_ssa: ssa.movi)
   MoveStructure::build (--preprocessed) src/move_structure_build.cpp:17-72 -> build_image
@@ -546,6 +547,35 @@ class MoveIndex:
             j += c
         return out
 
+    def query_kmer_occ_packed(self, bases, offs, k, want_err=False):
+        """movi_kmer_occ_host -> (occ, found, sum, QueryStats[, err, return code]); occ: one u64 per base, the k-mer at p of read i
+        at offs[i] - offs[0] + p, the read's last k - 1 slots 0 (an error slot has bit 63 set: MOVI_OCC_IS_ERROR)."""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        n = offs.size - 1
+        nb = int(offs[-1] - offs[0]) if n > 0 else 0
+        occ = np.zeros(max(nb, 1), np.uint64)
+        found = np.zeros(max(n, 1), np.uint32)
+        total = np.zeros(max(n, 1), np.uint64)
+        err = np.zeros(max(n, 1), np.uint8)
+        st = QueryStatsC()
+        rc = lib().movi_kmer_occ_host(self._h, bases.ctypes.data, offs.ctypes.data, n, int(k), occ.ctypes.data, found.ctypes.data,
+                                      total.ctypes.data, err.ctypes.data, C.byref(st))
+        if want_err:
+            return occ[:nb], found[:n], total[:n], QueryStats(st), err[:n], rc
+        check(rc)
+        return occ[:nb], found[:n], total[:n], QueryStats(st)
+
+    def query_kmer_occ(self, reads, k):
+        """`movi query --kmer-occ` per read: (found, sum, uint64 array of the max(0, len - k + 1) occurrence counts)."""
+        bases, offs = _pack_reads(reads)
+        occ, found, total, _ = self.query_kmer_occ_packed(bases, offs, k)
+        out = []
+        for i, r in enumerate(reads):
+            b = int(offs[i])
+            out.append((int(found[i]), int(total[i]), occ[b: b + max(0, len(r) - int(k) + 1)].copy()))
+        return out
+
     # -- locate: sampled suffix array ---------------------------------------------
     POS_OFFSET_BITS = 12          # MOVI_POS_PACK
     POS_NONE = 0xFFFFFFFFFFFFFFFF
@@ -727,6 +757,16 @@ class MoveIndex:
                                      C.c_void_p(d_err) if d_err else None,
                                      C.c_void_p(d_order) if d_order else None,
                                      C.c_void_p(stream) if stream else None))
+
+    def kmer_occ_device(self, d_bases, d_offs, n_reads, n_bases, k, d_occ, d_found=0, d_sum=0, d_err=0, stream=0):
+        """movi_kmer_occ_device: d_occ[offs[i] + p] = occurrences of the k-mer at p of read i (u64, all n_bases slots written);
+        d_found (u32), d_sum (u64), d_err (u8) per read, each optional."""
+        check(lib().movi_kmer_occ_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offs), n_reads, n_bases, int(k),
+                                         C.c_void_p(d_occ),
+                                         C.c_void_p(d_found) if d_found else None,
+                                         C.c_void_p(d_sum) if d_sum else None,
+                                         C.c_void_p(d_err) if d_err else None,
+                                         C.c_void_p(stream) if stream else None))
 
     def locate_device(self, d_pos, n_items, stream=0):
         """movi_locate_device: packed positions in, suffix-array entries out, in place."""

@@ -209,6 +209,8 @@ struct Job {
     std::vector<movi_mem_t> mems;                                     // ... and all of them, read by read (file order)
     std::vector<uint32_t> n_runs, kmers_found;                        // --kmer: runs and found k-mers per read ...
     std::vector<movi_kmer_run_t> runs;                                // ... and all the runs, read by read (file order)
+    std::vector<uint64_t> occ, occ_sum;                               // --kmer-occ: one count per base (a read's last k - 1: 0), the sums per read ...
+    std::vector<uint32_t> occ_found;                                  // ... and the found k-mers per read
     std::vector<movi_mc_read_t> mc;                                   // --multi-classify: best / second / counts per read ...
     std::vector<uint32_t> mc_counts;                                  // ... and, with --report-all, its counter row (num_species per read)
     std::vector<uint64_t> sa;                                         // --sa-entries: one suffix-array entry per base, emission order like pml
@@ -245,6 +247,9 @@ struct Job {
         n_mems.assign(o.mem ? n : 0, 0);
         n_runs.assign(o.kmer ? n : 0, 0);
         kmers_found.assign(o.kmer ? n : 0, 0);
+        if (o.kmer_occ) occ.resize(rs.bases.size());
+        occ_found.assign(o.kmer_occ ? n : 0, 0);
+        occ_sum.assign(o.kmer_occ ? n : 0, 0);
         err.assign(n, 0);
     }
 };
@@ -382,6 +387,7 @@ struct QueryRun {
     std::exception_ptr parse_error, write_error;
     std::mutex err_m;
     uint64_t reads_done = 0, bases_done = 0;
+    uint64_t occ_found_total = 0, occ_sum_total = 0;                   // --kmer-occ: found k-mers and the sum of their counts, all reads
     double gpu_seconds = 0, parse_seconds = 0, write_seconds = 0;
     std::vector<double> chunk_parse_s, chunk_gpu_s;                    // --verbose: the first chunks' stage times one by one
     std::vector<BatchReader::PhaseTimes> chunk_phases;                 // (cumulative parser phases after each chunk)
@@ -592,6 +598,8 @@ int run_shard(const QueryRun &q, movi_index_t *h, Job &job, size_t a, size_t b, 
         });
     case QueryKind::Count:
         return movi_count_host(h, bases, offs, n, job.matched.data() + a, job.counts.data() + a, err, nullptr);
+    case QueryKind::KmerOcc:                                          // (the counts lie relative to the shard's first base)
+        return movi_kmer_occ_host(h, bases, offs, n, o.k, job.occ.data() + offs[0], job.occ_found.data() + a, job.occ_sum.data() + a, err, nullptr);
     }
     return MOVI_ERR_ARG;
 }
@@ -818,6 +826,15 @@ void write_kmer_lines(QueryRun &q, const Job &job, const std::vector<uint32_t> &
     write_text(q, txt);
 }
 
+// one line per read (file order: no prefetch)
+void write_kmer_occ_lines(QueryRun &q, const Job &job, const std::vector<uint32_t> &order) {
+    std::string txt;
+    txt.reserve(job.rs.size() * 32 + job.rs.bases.size() * 2);
+    for (uint32_t i : order)
+        append_kmer_occ_line(txt, job.rs.id(i), job.rs.len(i), q.o.k, job.occ_found[i], job.occ_sum[i], job.occ.data() + job.rs.offsets[i]);
+    write_text(q, txt);
+}
+
 void write_job(QueryRun &q, Job &job) {
     const Options &o = q.o;
     const QueryPlan &plan = q.plan;
@@ -831,6 +848,7 @@ void write_job(QueryRun &q, Job &job) {
     case QueryKind::Mem: return write_mem_lines(q, job, order);
     case QueryKind::Kmer: return write_kmer_lines(q, job, order);
     case QueryKind::Count: return write_count_lines(q, job, order);
+    case QueryKind::KmerOcc: return write_kmer_occ_lines(q, job, order);
     default: break;                                                   // the PML / ZML forms
     }
     if (q.out.sa_file.is_open()) write_sa_records(q, job, order);
@@ -916,6 +934,8 @@ void gpu_stage(QueryRun &q) {
             job.mems.clear();
             for (auto &s : shards) job.mems.insert(job.mems.end(), s.mems.begin(), s.mems.end());
         }
+        if (o.kmer_occ)                                               // the summary's totals (--no-output still prints them)
+            for (size_t i = 0; i < n; i++) { q.occ_found_total += job.occ_found[i]; q.occ_sum_total += job.occ_sum[i]; }
         q.reads_done += n;
         q.bases_done += rs.bases.size();
         q.done_q.push(jp);
@@ -1014,6 +1034,11 @@ int run_query(const Options &o) {
     q.out.mls_file.close();
     if (q.out.sa_file.is_open()) q.out.sa_file.close();
     report_run(q);
+    if (o.kmer_occ) {                                                  // the two totals the reference's --kmer-count prints (include/sequitur.hpp:12-14)
+        std::ostream &sum_out = o.write_stdout ? std::cerr : std::cout;   // (--stdout: the lines own stdout)
+        sum_out << "Number of kmers found in the index:\t" << q.occ_found_total << "\n"
+                << "Sum of the counts of found k-mers:\t" << q.occ_sum_total << "\n";
+    }
     std::cout.flush();
     return 0;
 }

@@ -42,6 +42,7 @@ const Spec kSpecs[] = {
     // recognised but unsupported query types / features
     {"zml", 0, false},           {"mem", 0, false},         {"rpml", 0, false},
     {"kmer", 0, false},          {"kmer-count", 0, false},  {"sa-entries", 0, false},
+    {"kmer-occ", 0, false},      // occurrences per k-mer: this engine's own query (not the reference's --kmer-count)
     {"ftab-k", 0, true},         {"multi-ftab", 0, false},
     {"k-length", 'k', true},     {"min-mem-length", 'l', true},
 };
@@ -90,6 +91,7 @@ std::string usage() {
            "                      [--reverse] [--ignore-illegal-chars 1] [--gpus N] [--device D]\n"
            "       movi query -i DIR -r FILE|- --kmer [-k K] [--ftab-k K'] [-o PREFIX] [--stdout] [--no-output]\n"
            "                      [--reverse] [--ignore-illegal-chars 1] [--gpus N] [--device D]   (--kmer-count, --rpml: not supported)\n"
+           "       movi query -i DIR -r FILE|- --kmer-occ [-k K] [--ftab-k K'] ...   (occurrences of every k-mer in the text -> <prefix>.kmer_occ.<k>)\n"
            "       movi query -i DIR -r FILE|- --sa-entries [-o PREFIX] [--no-output] ...   (PML + <prefix>.sa_entries.bpf; after build-SA)\n"
            "       movi query -i DIR -r FILE|- --multi-classify -o REPORT|--stdout [--min-len N] [--report-all [--min-diff-frac F | --min-score-frac F]]\n"
            "                      [--no-output] [--reverse] [--gpus N] [--device D]   (after movi color; default colour mode only)\n"
@@ -171,11 +173,13 @@ Options parse_args(int argc, char **argv) {
         // clears the other query types (movi_options.hpp:108-110), so the last one applied wins
         // (the "only specify count or pml" check at :407-410 can never fire)
         // (set_kmer, :350, then set_mem, :352, come first: --kmer or --mem followed by a later one of the list is that other query)
+        // (--kmer-occ is applied where --kmer is and wins over it: `--kmer --kmer-occ` is the occurrence query)
         if (has("kmer")) { o.kmer = true; o.pml = false; o.count = false; o.zml = false; o.mem = false; }
-        if (has("mem")) { o.mem = true; o.pml = false; o.count = false; o.zml = false; o.kmer = false; }
-        if (has("count")) { o.count = true; o.pml = false; o.zml = false; o.mem = false; o.kmer = false; }
-        if (has("zml")) { o.zml = true; o.pml = false; o.count = false; o.mem = false; o.kmer = false; }
-        if (has("pml")) { o.pml = true; o.count = false; o.zml = false; o.mem = false; o.kmer = false; }
+        if (has("kmer-occ")) { o.kmer_occ = true; o.kmer = false; o.pml = false; o.count = false; o.zml = false; o.mem = false; }
+        if (has("mem")) { o.mem = true; o.pml = false; o.count = false; o.zml = false; o.kmer = false; o.kmer_occ = false; }
+        if (has("count")) { o.count = true; o.pml = false; o.zml = false; o.mem = false; o.kmer = false; o.kmer_occ = false; }
+        if (has("zml")) { o.zml = true; o.pml = false; o.count = false; o.mem = false; o.kmer = false; o.kmer_occ = false; }
+        if (has("pml")) { o.pml = true; o.count = false; o.zml = false; o.mem = false; o.kmer = false; o.kmer_occ = false; }
         if (has("k-length")) {
             const long v = to_int("k-length", val("k-length"));
             if (v < 0 || v > 0xFFFFFFFFl) throw UsageError("Argument '" + val("k-length") + "' failed to parse for option 'k-length'");
@@ -219,6 +223,12 @@ Options parse_args(int argc, char **argv) {
         if (o.gpus < 1) throw UsageError("--gpus must be >= 1");
         if (o.classify && o.count) throw UsageError("--classify needs PML or ZML queries");
         if (has("sample-rate")) throw UsageError("--sample-rate belongs to build-SA: a query takes the rate from ssa.movi");
+        if (o.kmer_occ) {
+            if (o.classify || o.logs || has("sa-entries") || has("multi-classify"))
+                throw UsageError("--kmer-occ cannot be combined with --classify, --filter, --logs, --sa-entries or --multi-classify");
+            if (o.k == 0) throw UsageError("-k / --k-length must be at least 1");
+            o.prefetch = false;                                   // file order, as --kmer
+        }
         o.sa_entries = has("sa-entries");
         if (o.sa_entries) {
             // (the reference opens an empty .sa_entries.bpf beside the other query types' files: only query_pml records entries)

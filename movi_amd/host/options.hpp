@@ -29,6 +29,7 @@ struct Options {
     bool zml = false;             // --zml: Ziv-Merhav cross parse lengths, same outputs as PML
     bool mem = false;             // --mem: maximal exact matches (src/mem_finder.cpp), one line per MEM
     bool kmer = false;            // --kmer: k-mer presence (src/sequitur.cpp:322-421), one line per read
+    bool kmer_occ = false;        // --kmer-occ: occurrences of every k-mer in the text (include/movi_hip.h: movi_kmer_occ_host), one line per read
     bool sa_entries = false;      // --sa-entries: one suffix-array entry per base beside the PML file (needs INDEX/ssa.movi: build-SA)
     bool multi_classify = false;  // --multi-classify: PML walk + document scoring, one report line per read (needs INDEX/doc_sets_flat.bin: movi color)
     uint32_t min_len = 1;         // --min-len (uint8_t, movi_options.hpp: min_match_len)
@@ -65,7 +66,7 @@ struct Options {
     bool write_output_allowed() const { return !no_output && !filter; }
     bool write_stdout_enabled() const { return write_stdout && !classify; }
     bool ml() const { return pml || zml; }                                // per-base matching lengths
-    std::string query_type() const { return kmer ? "kmers" : mem ? "mem" : count ? "count" : (zml ? "zml" : "pml"); }   // src/utils.cpp:47-67
+    std::string query_type() const { return kmer_occ ? "kmer_occ" : kmer ? "kmers" : mem ? "mem" : count ? "count" : (zml ? "zml" : "pml"); }   // src/utils.cpp:47-67
 };
 
 struct UsageError : std::runtime_error {

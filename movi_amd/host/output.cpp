@@ -442,6 +442,30 @@ void append_kmer_line(std::string &txt, std::string_view id, uint64_t query_leng
     txt.push_back('\n');
 }
 
+// `movi query --kmer-occ`: this engine's own file, so `all` is what it means (0 for a read shorter than k), not the wrapped value above.
+void append_kmer_occ_line(std::string &txt, std::string_view id, uint64_t query_length, uint32_t k, uint64_t found, uint64_t sum,
+                          const uint64_t *occ) {
+    char num[24];
+    auto put = [&](uint64_t v) {
+        const auto r = std::to_chars(num, num + sizeof(num), v);
+        txt.append(num, (size_t)(r.ptr - num));
+    };
+    const uint64_t all = query_length >= k ? query_length - k + 1ull : 0ull;
+    txt.append(id.data(), id.size());
+    txt.push_back('\t');
+    put(found);
+    txt.push_back('/');
+    put(all);
+    txt.push_back('\t');
+    put(sum);
+    txt.push_back('\t');
+    for (uint64_t p = 0; p < all; p++) {
+        if (p) txt.push_back(',');
+        put(occ[p]);
+    }
+    txt.push_back('\n');
+}
+
 void append_count_line(std::string &txt, std::string_view id, uint64_t query_length, uint64_t matched, uint64_t count) {
     char num[24];
     auto put = [&](uint64_t v) {

@@ -69,6 +69,10 @@ void append_count_line(std::string &txt, std::string_view id, uint64_t query_len
 void append_sa_record(std::string &out, std::string_view id, const uint64_t *entries, uint64_t count);
 void append_kmer_line(std::string &txt, std::string_view id, uint64_t query_length, uint32_t k, uint64_t found,
                       const movi_kmer_run_t *runs, uint64_t n_runs);
+// one line of `movi query --kmer-occ`: `id<TAB>found/all<TAB>sum<TAB>occ[0],occ[1],...,occ[all-1]<LF>`, all = max(0, len - k + 1) (the
+// list is empty when all = 0); occ: the read's slots of movi_kmer_occ_host, of which the first `all` are written
+void append_kmer_occ_line(std::string &txt, std::string_view id, uint64_t query_length, uint32_t k, uint64_t found, uint64_t sum,
+                          const uint64_t *occ);
 void append_mem_line(std::string &txt, std::string_view id, const movi_mem_t &m);   // one MEM line (output_mems, count as u16)   // the same line, appended
 
 // Movi Color.  DocInfo: MoveStructure::load_document_info (src/move_structure_io.cpp:643-687) -- DIR/ref.fa.doc_offsets (cumulative

@@ -20,10 +20,11 @@ enum class QueryKind {
     Mem,
     Kmer,
     Count,
+    KmerOcc,          // --kmer-occ: occurrences per k-mer (last: the arms above keep their numbers)
 };
 
 inline const char *query_kind_name(QueryKind k) {
-    static const char *const names[] = {"pml_verdict_bins", "pml_logs", "multi_classify", "sa_entries", "pml", "zml", "mem", "kmer", "count"};
+    static const char *const names[] = {"pml_verdict_bins", "pml_logs", "multi_classify", "sa_entries", "pml", "zml", "mem", "kmer", "count", "kmer_occ"};
     return names[(int)k];
 }
 
@@ -44,7 +45,7 @@ struct QueryPlan {
     bool mc_to_out_file;       // --multi-classify: the report is the -o file itself
     std::string bpf_suffix;    // prefix + this: the BPF file of a PML / ZML query
     std::string sa_suffix;     // prefix + this: the suffix-array entries beside it
-    std::string matches_suffix;// prefix + this: the text file of a count, MEM or k-mer query
+    std::string matches_suffix;// prefix + this: the text file of a count, MEM, k-mer or k-mer occurrence query
     std::string logs_stem;     // prefix + this + ".costs" / ".scans" / ".fastforwards"
 };
 
@@ -73,11 +74,12 @@ inline QueryPlan query_plan(const Options &o) {
            : o.pml ? QueryKind::Pml
            : o.zml ? QueryKind::Zml
            : o.mem ? QueryKind::Mem
-           : o.kmer ? QueryKind::Kmer : QueryKind::Count;
+           : o.kmer ? QueryKind::Kmer
+           : o.kmer_occ ? QueryKind::KmerOcc : QueryKind::Count;
     if (o.classify && !o.filter && !o.write_stdout) p.report_suffix = "." + o.query_type() + ".report";   // src/classifier.cpp:39-61
     p.mc_to_out_file = o.multi_classify && !o.write_stdout && out;
     if (p.open_files) {
-        if (o.kmer) p.matches_suffix = "." + o.query_type() + "." + std::to_string(o.k);   // <out_file or reads.<index type>>.kmers.<k> (src/utils.cpp:348-366)
+        if (o.kmer || o.kmer_occ) p.matches_suffix = "." + o.query_type() + "." + std::to_string(o.k);   // <out_file or reads.<index type>>.kmers.<k> (src/utils.cpp:348-366); --kmer-occ: .kmer_occ.<k>
         else if (o.mem) p.matches_suffix = ".mems";                                        // <out_file or reads.<index type>>.mems
         else if (o.ml()) {
             p.bpf_suffix = "." + o.query_type() + ".bpf";
