@@ -187,7 +187,7 @@ int movi_index_load_replicated(const char *index_dir_or_file, const int *devices
 #define MOVI_PREPARE_PML 1u
 #define MOVI_PREPARE_COUNT 2u
 #define MOVI_PREPARE_ZML 4u
-#define MOVI_PREPARE_SA 8u     /* locate: loads the kernels of movi_sa_entries_device / movi_locate_device.  The sampled suffix array and the
+#define MOVI_PREPARE_SA 8u     /* locate: loads the kernels of movi_sa_entries_device / movi_locate_device / movi_locate_matches_device.  The sampled suffix array and the
                                   locate rows are built when the array is attached (movi_ssa_build / movi_ssa_load), so a handle without
                                   one is MOVI_ERR_ARG here */
 int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *derived_bytes);
@@ -656,6 +656,66 @@ int movi_sa_entries_device(movi_index_t *ix, const uint8_t *d_bases, const uint6
 int movi_sa_entries_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, uint16_t *h_out_pml,
                          uint64_t *h_out_sa, uint8_t *h_read_err, movi_query_stats_t *stats);
 
+/* ---- locate count and MEM hits --------------------------------------------------- */
+
+/* `movi query --count --locate` and `movi query --mem --locate`: where in the indexed text a counted match or a MEM lies.
+ * Deviates from the reference: there is none -- the reference has no such mode, so the contract is stated on the text itself.
+ *
+ * Terms.  T is the indexed text of n = desc.length characters, terminator included: every record of the FASTA cleaned (anything but
+ * A, C, G, T becomes A) and followed by its reverse complement, with a '%' after each of them in an index built with --separators.
+ * A MATCH ITEM is (read, start, end) with 0 <= start < end <= len(read), and X = P[start .. end) of that read P.
+ *     occ(X)  = the number of t with T[t .. t + |X|) == X.  Occurrences across the record junctions of an index built without
+ *               --separators count, exactly as for the count query.  occ(X) = 0 if X holds an illegal base (not an error).
+ *     hits(X) = those t in BWT order, that is, by increasing rank of the suffix T[t ..].
+ * With a cap max_occ >= 1 the item reports listed = min(occ, max_occ) and the first `listed` elements of hits(X).
+ * Positions lie in [0, n): the "+ n" of get_SA_entries for walks that pass text position 0 (above) does not leak out.
+ * The answers depend neither on whether an interval table is used ("ftab_k"), nor on the row-index width ("idx64"), nor on the sample
+ * rate of the attached suffix array.
+ * (How they come about: the interval [s, e] the backward search over X ends on is the range of BWT positions whose suffix starts with
+ * X, so occ = e - s + 1 and hits(X) = SA[s], SA[s + 1], ...; a position's entry is SA[p] or SA[p] + n, so t = entry mod n.)
+ *
+ * Device form.  d_occ[i] = occ of item i in full 64 bits; d_first[0 .. n_items] = the exclusive prefix sum of `listed`, so
+ * d_first[n_items] = the total; the positions of item i are d_positions[d_first[i] .. d_first[i + 1]) as far as they lie below
+ * positions_cap.  Slots at or past min(total, positions_cap) are not touched, and a total above the cap is no error of the device
+ * call: the caller reads d_first[n_items].  Four steps on `stream`: the interval searches (one lane owns the items lane, lane + stride,
+ * ... and takes up its next item when a search ends, like movi_locate_device's lists), a device scan over the n_items + 1 values of
+ * `listed` (n_items < 2^31 - 1 per call, else MOVI_ERR_ARG: the scan is 32-bit-indexed), the expansion of the intervals into packed
+ * positions, and the locate walks in place on them, which store text positions.  (The walks are movi_locate_device's, in a kernel of
+ * this call's own: it reads the number of slots from d_first[n_items] on the device, where that one takes it from the host.)
+ * The scan's temporary storage, its input and the per-item intervals live in the caller's d_work, of at least
+ * movi_locate_matches_work_bytes(n_items) bytes (host only; about 33 bytes per item).
+ * The call is asynchronous on `stream`.  With a sampled suffix array attached and after
+ * movi_index_prepare(MOVI_PREPARE_COUNT | MOVI_PREPARE_SA) it allocates and builds nothing and may be captured into a graph without
+ * a warm-up call.  Too small a d_work, max_occ == 0, NULL required buffers (d_first and d_work always; d_items, d_occ, d_offsets and
+ * d_bases with n_items > 0; d_positions with positions_cap > 0) and no suffix array attached are each MOVI_ERR_ARG; the last names
+ * build-SA in its message.
+ * A bad item (read >= n_reads, start >= end, end past the read) gets occ = listed = 0 and 0xFF in d_item_err (optional); no byte
+ * outside the read is read.  An item whose search hits one of the reference's LF throws gets its kErr* code there and
+ * occ = listed = 0; a position whose expansion or locate walk breaks an invariant of the table becomes MOVI_POS_NONE, as in
+ * movi_locate_device.  Both are counted in movi_last_stats' `errors`.  A corrupt table ends the call, it does not hang it.
+ * movi_last_launch names the last kernel launched (the walk's; the search's when positions_cap is 0). */
+typedef struct movi_match { uint32_t read, start, end; } movi_match_t;   /* 12 bytes, end exclusive */
+
+int movi_locate_matches_work_bytes(uint64_t n_items, uint64_t *bytes);   /* host only */
+
+int movi_locate_matches_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
+                               const movi_match_t *d_items, uint64_t n_items, uint32_t max_occ, uint64_t *d_occ, uint64_t *d_first,
+                               uint64_t *d_positions, uint64_t positions_cap, uint8_t *d_item_err, void *d_work, uint64_t work_bytes,
+                               void *stream);
+
+/* Host form: h_occ[n_items], h_first[n_items + 1] and the positions of item 0, then item 1, ... in h_positions;
+ * *n_positions_total = h_first[n_items].  Items must be ordered by `read`, else MOVI_ERR_ARG, checked on the host before the device
+ * is touched.  Runs chunk by chunk through the handle's staging, synchronously, like movi_sa_entries_host; a chunk is a stretch of
+ * reads of about 2^26 bases ("pipe_chunk_bases" where that option is set) together with its items, and its reads go up with it --
+ * a caller that has just run the count or MEM query on the same reads uploads them a second time, which is accepted: from 10 positions
+ * per item on the locate walks are four fifths of the call and more (profiles/locate_matches.txt).  A positions_cap that is too small behaves like mems_cap of movi_mem_host: MOVI_ERR_ARG,
+ * with h_occ, h_first and the total still filled (h_positions is then incomplete).  Error items or MOVI_POS_NONE slots make the call
+ * return MOVI_ERR_INVARIANT, and bad items (0xFF in h_item_err, optional) MOVI_ERR_ARG, after everything else was answered. */
+int movi_locate_matches_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads,
+                             const movi_match_t *h_items, uint64_t n_items, uint32_t max_occ, uint64_t *h_occ, uint64_t *h_first,
+                             uint64_t *h_positions, uint64_t positions_cap, uint64_t *n_positions_total, uint8_t *h_item_err,
+                             movi_query_stats_t *stats);
+
 /* ---- Movi Color: multi-class classification, default colour mode ---------------- */
 
 /* `movi color`, `movi build --color` and `movi query --multi-classify`: which documents (species) a read comes from.
@@ -812,7 +872,9 @@ int movi_host_unregister(void *p);
  * "reserve_host_reads" (that staging reserved up front instead of inside the first big call: the reads of a synchronous *_host call of
  * up to this many bases, its u16 result vector, the per-read buffers of up to this many reads; movi_index_info "host_staging_bytes"
  * tells what is held), "pipe_chunk_bases"
- * (bases per chunk of the overlapped host path, 0 = its own policy: a test hook), "seg_len" (PML: batches whose mean
+ * (bases per chunk of the overlapped host path, 0 = its own policy: a test hook), "locate_matches_stages" (a measurement hook:
+ * movi_locate_matches_device stops after its searches and scan (1) or after the expansion (2: d_positions then holds packed
+ * positions); 3, the default, is the whole call), "seg_len" (PML: batches whose mean
  * read length is at least twice this many bases are walked segment-parallel -- every read cut into segments of about
  * seg_len bases walked by their own lanes, stitched where the walks fall into step, reads that do not walked again:
  * identical results; ZML parses likewise; default 2048, 0 = off, else a multiple of 32; batches too small to fill the GPU

@@ -163,6 +163,13 @@ SYMBOLS = {
                                          C.c_void_p, C.c_void_p, C.c_void_p]),
     "movi_sa_entries_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.POINTER(QueryStatsC)]),
+    "movi_locate_matches_work_bytes": (C.c_int, [C.c_uint64, C.POINTER(C.c_uint64)]),
+    "movi_locate_matches_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                             C.c_void_p]),
+    "movi_locate_matches_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p,
+                                           C.POINTER(QueryStatsC)]),
     "movi_color_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "movi_color_save": (C.c_int, [C.c_void_p, C.c_char_p]),
     "movi_color_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint32]),

@@ -211,6 +211,7 @@ struct movi_index {
     PipeSlot pipe[kPipeSlots];
     hipStream_t pipe_up = nullptr;   // every chunk's upload, in order (uploads on separate streams share the link and all arrive late)
     std::vector<hipEvent_t> pipe_ev; // chunk i of a call has arrived (calls whose reads go up ahead of the loop into scratch[kBases])
+    int locate_matches_stages = 3;   // measurement hook ("locate_matches_stages"): movi_locate_matches_device stops after the searches and the scan (1), after the expansion (2: d_positions holds packed positions), or runs whole (3)
     uint64_t pipe_chunk_bases = 0;   // test hook ("pipe_chunk_bases"): chunk size of the overlapped path, 0 = its policy
     LaunchInfo last_launch;          // what the last query call launched (movi_last_launch)
     bool host_autopin = true;        // big *_host calls on pageable buffers page-lock them for the call ("host_autopin")
@@ -1170,6 +1171,11 @@ int movi_set_option(movi_index_t *ix, const char *key, int64_t value) {
             HIP_TRY(grow(ix->scratch[movi_index::kErr], v));
             HIP_TRY(ix->h_rel.reserve((v + 1) * 8, (v + 1) * 8));   // (a reservation: exactly what was asked for)
         }
+        return MOVI_OK;
+    }
+    if (!strcmp(key, "locate_matches_stages")) {             // measurement hook (tools/locate_matches_bench.py): the call's steps timed apart
+        if (value < 1 || value > 3) return fail(MOVI_ERR_ARG, "locate_matches_stages must be 1 (search + scan), 2 (+ expansion) or 3 (the whole call)");
+        ix->locate_matches_stages = (int)value;
         return MOVI_OK;
     }
     if (!strcmp(key, "pipe_chunk_bases")) {                  // test hook: many small chunks through the overlapped host path
@@ -2589,6 +2595,7 @@ int movi_index_prepare(movi_index_t *ix, uint32_t what, void *stream, uint64_t *
     if (what & MOVI_PREPARE_SA) {
         // the sampled suffix array and the locate rows were built when it was attached: only the kernels' code object is loaded here
         (void)preload_sa(ix->kmode, ix->dev.idx32 != 0);
+        (void)preload_hits(ix->kmode, ix->dev.idx32 != 0);             // (movi_locate_matches_device captured without a warm-up call)
         (void)hipGetLastError();
     }
     if (what & MOVI_PREPARE_COLOR) {
@@ -3045,6 +3052,165 @@ int movi_sa_entries_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_
     AutoPin pins[2];                                         // (kSaEntries: chunk by chunk, synchronously)
     return run_host(ix, plan_reads_call(ix, HostQuery::kSaEntries, h_bases, h_offsets, n_reads, 0, h_out_pml != nullptr, pins), h_bases, h_offsets,
                     h_read_err, stats, launch, fetch, harvest);
+}
+
+}  // extern "C"
+
+// -------------------------------------------------------------------------- locate count and MEM hits
+
+static_assert(sizeof(movi_match_t) == sizeof(HitsItem) && sizeof(movi_match_t) == 12, "movi_match_t and HitsItem differ");
+
+namespace {
+
+// A host call's chunks: about kHitsChunkBases bases of reads ("pipe_chunk_bases" where that is set) and at most kHitsChunkItems items
+// (always whole reads: a read's items stay together); a chunk's positions are staged for kHitsChunkPositions of them and the chunk is
+// run again with room for its total where that is more.
+constexpr uint64_t kHitsChunkBases = 1ull << 26;
+constexpr uint64_t kHitsChunkItems = 1ull << 22;
+constexpr uint64_t kHitsChunkPositions = 1ull << 24;
+
+int locate_matches_device(movi_index *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, const movi_match_t *d_items,
+                          uint64_t n_items, uint32_t max_occ, uint64_t *d_occ, uint64_t *d_first, uint64_t *d_positions, uint64_t positions_cap,
+                          uint8_t *d_item_err, void *d_work, uint64_t work_bytes, hipStream_t s) {
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (max_occ == 0) return fail(MOVI_ERR_ARG, "max_occ must be at least 1");
+    if (!ix->sa_rate) return fail(MOVI_ERR_ARG, kNoSsa);
+    if (n_items >= kHitsMaxItems) return fail(MOVI_ERR_ARG, "2^31 - 1 items or more in one call (their prefix sum is one 32-bit-indexed device scan)");
+    if (n_reads > 0xFFFFFFFFull) return fail(MOVI_ERR_ARG, "more than 2^32 reads in one call");
+    if (!d_first || !d_work || (n_items && (!d_items || !d_occ || !d_offsets || (n_reads && !d_bases))) || (positions_cap && !d_positions))
+        return fail(MOVI_ERR_ARG, "NULL device buffer");
+    const uint64_t need = hits_work_layout(n_items).total;
+    if (work_bytes < need)
+        return fail(MOVI_ERR_ARG, "d_work holds " + std::to_string(work_bytes) + " bytes, " + std::to_string(n_items) + " items need " +
+                                      std::to_string(need) + " (movi_locate_matches_work_bytes)");
+    HIP_TRY(hipSetDevice(ix->device));
+    int rc = count_tables(ix, s);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(ix->d_stats.get(), 0, sizeof(DevStats), s));
+    HIP_TRY(launch_locate_matches(ix->kmode, ix->dev, loc_args(ix), d_bases, d_offsets, n_reads, reinterpret_cast<const HitsItem *>(d_items), n_items,
+                                  max_occ, d_occ, d_first, d_positions, positions_cap, d_item_err, d_work, work_bytes, ix->locate_matches_stages,
+                                  ix->d_stats.get(), ix->cfg.num_cus, s, &ix->last_launch));
+    return MOVI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int movi_locate_matches_work_bytes(uint64_t n_items, uint64_t *bytes) {
+    if (!bytes) return fail(MOVI_ERR_ARG, "NULL argument");
+    if (n_items >= kHitsMaxItems) return fail(MOVI_ERR_ARG, "2^31 - 1 items or more in one call (their prefix sum is one 32-bit-indexed device scan)");
+    *bytes = hits_work_layout(n_items).total;
+    return MOVI_OK;
+}
+
+int movi_locate_matches_device(movi_index_t *ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads, const movi_match_t *d_items,
+                               uint64_t n_items, uint32_t max_occ, uint64_t *d_occ, uint64_t *d_first, uint64_t *d_positions,
+                               uint64_t positions_cap, uint8_t *d_item_err, void *d_work, uint64_t work_bytes, void *stream) {
+    return locate_matches_device(ix, d_bases, d_offsets, n_reads, d_items, n_items, max_occ, d_occ, d_first, d_positions, positions_cap, d_item_err,
+                                 d_work, work_bytes, static_cast<hipStream_t>(stream));
+}
+
+int movi_locate_matches_host(movi_index_t *ix, const uint8_t *h_bases, const uint64_t *h_offsets, uint64_t n_reads, const movi_match_t *h_items,
+                             uint64_t n_items, uint32_t max_occ, uint64_t *h_occ, uint64_t *h_first, uint64_t *h_positions, uint64_t positions_cap,
+                             uint64_t *n_positions_total, uint8_t *h_item_err, movi_query_stats_t *stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_positions_total) *n_positions_total = 0;
+    if (!ix) return fail(MOVI_ERR_ARG, "index handle is NULL");
+    if (max_occ == 0) return fail(MOVI_ERR_ARG, "max_occ must be at least 1");
+    if (!h_first || (n_items && (!h_items || !h_occ)) || (n_reads && !h_offsets) || (positions_cap && !h_positions))
+        return fail(MOVI_ERR_ARG, "NULL host buffer");
+    for (uint64_t i = 1; i < n_items; i++)
+        if (h_items[i].read < h_items[i - 1].read)
+            return fail(MOVI_ERR_ARG, "the items are not ordered by read (item " + std::to_string(i) + ")");
+    if (n_reads) {
+        if (h_offsets[n_reads] != h_offsets[0] && !h_bases) return fail(MOVI_ERR_ARG, "NULL host buffer");
+        if (int rc0 = check_offsets(h_offsets, n_reads)) return rc0;
+    }
+    if (!ix->sa_rate) return fail(MOVI_ERR_ARG, kNoSsa);
+    h_first[0] = 0;
+    if (n_items == 0) return MOVI_OK;
+    HIP_TRY(hipSetDevice(ix->device));
+    DevBuf *d = ix->scratch;
+    const uint64_t n_text = ix->desc.length, per_item = std::min<uint64_t>(max_occ, n_text);
+    const uint64_t target = ix->pipe_chunk_bases ? ix->pipe_chunk_bases : kHitsChunkBases;
+    std::vector<uint64_t> rel;
+    std::vector<movi_match_t> items;
+    uint64_t total = 0, errors = 0, bad = 0, i0 = 0;
+    bool overflow = false;
+    // the items of reads at or past n_reads (bad items, the last of the ordered list) go with the last chunk, their read out of its range
+    for (uint64_t first = 0; i0 < n_items;) {
+        uint64_t last = n_reads, i1 = n_items;
+        if (first < n_reads) {
+            last = chunk_end(h_offsets, n_reads, first, target, 1, target);
+            auto read_lt = [](const movi_match_t &m, uint64_t r) { return (uint64_t)m.read < r; };
+            i1 = (uint64_t)(std::lower_bound(h_items + i0, h_items + n_items, last, read_lt) - h_items);
+            if (i1 - i0 > kHitsChunkItems) {                 // fewer reads: those that hold the first kHitsChunkItems items, at least one
+                last = std::max<uint64_t>(first + 1, h_items[i0 + kHitsChunkItems].read);
+                i1 = (uint64_t)(std::lower_bound(h_items + i0, h_items + n_items, last, read_lt) - h_items);
+            }
+            if (last == n_reads) i1 = n_items;
+        }
+        if (i1 == i0) { first = last; continue; }            // a stretch of reads without items
+        HostChunk c;
+        c.first = first; c.nr = last - first;
+        c.b0 = c.nr ? h_offsets[first] : 0; c.nb = c.nr ? h_offsets[last] - h_offsets[first] : 0;
+        const uint64_t ni = i1 - i0;
+        if (ni >= kHitsMaxItems) return fail(MOVI_ERR_ARG, "one read has 2^31 - 1 items or more");
+        rel.assign(c.nr + 1, 0);
+        if (c.nr) (void)fill_relative_offsets(rel.data(), h_offsets, c);
+        items.assign(h_items + i0, h_items + i1);
+        for (movi_match_t &m : items) m.read = (uint64_t)m.read < last ? (uint32_t)(m.read - first) : 0xFFFFFFFFu;
+        const HitsWorkLayout w = hits_work_layout(ni);
+        HIP_TRY(grow(d[movi_index::kBases], std::max<uint64_t>(c.nb, 1)));
+        HIP_TRY(grow(d[movi_index::kOffs], (c.nr + 1) * 8));
+        HIP_TRY(grow(d[movi_index::kErr], ni));
+        HIP_TRY(grow(d[movi_index::kMask], ni * sizeof(movi_match_t)));
+        HIP_TRY(grow(d[movi_index::kA], ni * 8));
+        HIP_TRY(grow(d[movi_index::kB], (ni + 1) * 8));
+        HIP_TRY(grow(d[movi_index::kTmp], w.total));
+        if (c.nb) HIP_TRY(hipMemcpy(d[movi_index::kBases].ptr(), h_bases + c.b0, c.nb, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d[movi_index::kOffs].ptr(), rel.data(), (c.nr + 1) * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d[movi_index::kMask].ptr(), items.data(), ni * sizeof(movi_match_t), hipMemcpyHostToDevice));
+        uint64_t cap = std::min(ni * per_item, kHitsChunkPositions), found = 0;
+        DevStats h{};
+        for (int pass = 0; pass < 2; pass++) {               // (a second pass only where the chunk's total is above the staging's first size)
+            HIP_TRY(grow(d[movi_index::kS], std::max<uint64_t>(cap, 1) * 8));
+            int rc = locate_matches_device(ix, d[movi_index::kBases].as<uint8_t>(), d[movi_index::kOffs].as<uint64_t>(), c.nr,
+                                           d[movi_index::kMask].as<movi_match_t>(), ni, max_occ, d[movi_index::kA].as<uint64_t>(),
+                                           d[movi_index::kB].as<uint64_t>(), d[movi_index::kS].as<uint64_t>(), cap, d[movi_index::kErr].as<uint8_t>(),
+                                           d[movi_index::kTmp].ptr(), w.total, nullptr);
+            if (rc) return rc;
+            HIP_TRY(hipMemcpy(&found, d[movi_index::kB].as<uint64_t>() + ni, 8, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&h, ix->d_stats.get(), sizeof(h), hipMemcpyDeviceToHost));
+            if (found <= cap || overflow || total + found > positions_cap) break;     // (positions that will not be delivered are not staged)
+            cap = found;
+        }
+        HIP_TRY(hipMemcpy(h_occ + i0, d[movi_index::kA].ptr(), ni * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(h_first + i0, d[movi_index::kB].ptr(), (ni + 1) * 8, hipMemcpyDeviceToHost));
+        for (uint64_t i = i0; i <= i1; i++) h_first[i] += total;       // (h_first[i1] is the next chunk's h_first[i0]: written again, the same)
+        items.clear();
+        {
+            std::vector<uint8_t> err(ni);
+            HIP_TRY(hipMemcpy(err.data(), d[movi_index::kErr].ptr(), ni, hipMemcpyDeviceToHost));
+            for (uint8_t e : err) bad += e == 0xFFu ? 1u : 0u;
+            if (h_item_err) memcpy(h_item_err + i0, err.data(), ni);
+        }
+        if (!overflow && total + found <= positions_cap) {
+            if (found) HIP_TRY(hipMemcpy(h_positions + total, d[movi_index::kS].ptr(), found * 8, hipMemcpyDeviceToHost));
+        } else overflow = true;
+        total += found;
+        errors += h.errors;
+        if (stats) add_stats(stats, c.nb, h);
+        i0 = i1;
+        first = last;
+    }
+    if (n_positions_total) *n_positions_total = total;
+    if (overflow) return fail(MOVI_ERR_ARG, std::to_string(total) + " positions listed, positions_cap is " + std::to_string(positions_cap));
+    if (errors)
+        return fail(MOVI_ERR_INVARIANT, std::to_string(errors) + " item(s) or position(s) hit a move-structure invariant violation (corrupt index?)");
+    if (bad) return fail(MOVI_ERR_ARG, std::to_string(bad) + " item(s) address no stretch of a read (0xFF in h_item_err)");
+    return MOVI_OK;
 }
 
 }  // extern "C"

@@ -453,6 +453,32 @@ hipError_t launch_sa_pos(const DevIndex &ix, const uint8_t *d_bases, const uint6
 hipError_t build_sampled_sa(int mode, const DevIndex &ix, const LocArgs &loc, uint64_t *d_samples, DevStats *d_stats, int num_cus,
                             hipStream_t stream, uint32_t *bad, LaunchInfo *info);
 hipError_t preload_sa(int mode, bool idx32);   // load the translation unit's code object now (movi_index_prepare)
+// Locate count and MEM hits (movi_walk_hits.hip): per match item (read, start, end) the occurrences of P[start .. end) in the text --
+// d_occ[i] --, the exclusive prefix sum of min(occ, max_occ) -- d_first[0 .. n_items] --, and the text positions of those hits in BWT
+// order in d_positions[d_first[i] .. d_first[i + 1]) as far as they lie below positions_cap.  Interval search, scan, expansion and
+// locate walk on `stream`; the intervals, the scan's input and its temporary storage live in d_work (hits_work_layout).  stages: 3 = the
+// whole call; 1 / 2 = stop after the scan / the expansion (a measurement hook: the steps timed apart).
+struct HitsItem { uint32_t read, start, end; };          // movi_match_t
+constexpr int kHitsWaves = 16;                           // hits_interval_kernel: one-wavefront blocks per CU a launch fills at most
+constexpr uint64_t kHitsMaxItems = 0x7FFFFFFFull;        // n_items + 1 values go through one 32-bit-indexed device scan
+constexpr uint64_t kHitsIntervalBytes = 24;
+struct HitsWorkLayout { uint64_t intervals, listed, scan_temp, total; };   // byte offsets into d_work, and its size
+// (the scan's temporary storage: a few words of look-back state per block of at least 256 values -- bounded here by half a byte per
+// value plus 32 KiB, several times what hipCUB asks for; the launcher checks hipCUB's own figure against it)
+inline HitsWorkLayout hits_work_layout(uint64_t n_items) {
+    auto up = [](uint64_t v) { return (v + 255u) & ~255ull; };
+    HitsWorkLayout w;
+    w.intervals = 0;
+    w.listed = up(n_items * kHitsIntervalBytes);
+    w.scan_temp = w.listed + up((n_items + 1) * 8);
+    w.total = w.scan_temp + up(n_items / 2 + (32u << 10));
+    return w;
+}
+hipError_t launch_locate_matches(int mode, const DevIndex &ix, const LocArgs &loc, const uint8_t *d_bases, const uint64_t *d_offsets,
+                                 uint64_t n_reads, const HitsItem *d_items, uint64_t n_items, uint32_t max_occ, uint64_t *d_occ,
+                                 uint64_t *d_first, uint64_t *d_positions, uint64_t positions_cap, uint8_t *d_item_err, void *d_work,
+                                 uint64_t work_bytes, int stages, DevStats *d_stats, int num_cus, hipStream_t stream, LaunchInfo *info);
+hipError_t preload_hits(int mode, bool idx32);   // load the translation unit's code object now (movi_index_prepare)
 // d_pos[m] = the packed position of BWT position m * loc.rate, m < n_samples (what build_sampled_sa starts its list from).
 hipError_t launch_sample_positions(int mode, const DevIndex &ix, const LocArgs &loc, uint64_t n_samples, uint64_t *d_pos, hipStream_t stream);
 

@@ -23,6 +23,7 @@ namespace movi {
 //   a.succ == 0   pos[item] = samples[s] + distance, NOT reduced modulo n: a walk that passes text position 0 stops at BWT position 0
 //                 (sample 0 = n - 1) and returns entry + n, as the reference does;
 //   a.succ == 1   one LF step first; pos[item] = s, a.aux[item] = distance.
+// (hits_walk_kernel, movi_walk_hits.hip, restates this loop with the item count read on the device: keep the two in step.)
 // An item that is kPosNone stays; one that is not a position of the table, or whose walk breaks an invariant of the table (the
 // reference's throws; more than n steps), becomes kPosNone and is counted in DevStats::errors.
 template <int MODE, typename IdxT>

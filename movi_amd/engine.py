@@ -9,6 +9,7 @@ Reference seam (file:line under /root/reference) -> here:
   MoveStructure::query_all_kmers      src/sequitur.cpp:322-421           -> MoveIndex.query_kmers
   (no reference seam: occurrences per k-mer, include/movi_hip.h)        -> MoveIndex.query_kmer_occ
   MoveStructure::get_SA_entries       src/move_structure.cpp:35-48       -> MoveIndex.locate / query_sa_entries
+  (no reference seam: text positions of count and MEM hits, movi_hip.h) -> MoveIndex.locate_matches
   MoveStructure::find_sampled_SA_entries src/move_structure_build.cpp:1174 -> MoveIndex.build_ssa (save_ssa / load_ssa: ssa.movi)
   MoveStructure::build (--preprocessed) src/move_structure_build.cpp:17-72 -> build_image
   prepare_ref + pfp-thresholds + build  src/movi_launcher.cpp:190-242    -> rlbwt_from_text / build_image_from_text
@@ -639,6 +640,56 @@ class MoveIndex:
         sa, _, _ = self.query_sa_entries_packed(bases, offs, want_pml=False)
         return [sa[int(offs[i]): int(offs[i + 1])] for i in range(len(reads))]
 
+    # -- locate count and MEM hits ------------------------------------------------
+    MATCH_DTYPE = np.dtype([("read", "<u4"), ("start", "<u4"), ("end", "<u4")])      # movi_match_t
+
+    @staticmethod
+    def locate_matches_work_bytes(n_items):
+        """movi_locate_matches_work_bytes: the bytes of d_work a device call over n_items items needs (host only)."""
+        b = C.c_uint64(0)
+        check(lib().movi_locate_matches_work_bytes(int(n_items), C.byref(b)))
+        return int(b.value)
+
+    def locate_matches_packed(self, bases, offs, items, max_occ, positions_cap=None, want_err=False):
+        """movi_locate_matches_host -> (occ, first, positions, QueryStats[, item err, total, return code]); items: MATCH_DTYPE (or an
+        (n, 3) integer array), ordered by read.  positions_cap None: room for a few positions per item, and a second call with room for
+        the total where that is more."""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offs = np.ascontiguousarray(offs, np.uint64)
+        items = np.asarray(items)
+        if items.dtype != self.MATCH_DTYPE:
+            items = np.ascontiguousarray(items, np.uint32).reshape(-1, 3).view(self.MATCH_DTYPE).reshape(-1)
+        items = np.ascontiguousarray(items)
+        n, ni = offs.size - 1, items.size
+        if positions_cap is None:                                 # a few positions per item first, then room for exactly the total
+            occ, first, pos, st, err, total, rc = self.locate_matches_packed(bases, offs, items, max_occ, ni * 4 + 1024, want_err=True)
+            if rc == -1 and total > pos.size:
+                return self.locate_matches_packed(bases, offs, items, max_occ, total, want_err)
+            if want_err:
+                return occ, first, pos, st, err, total, rc
+            check(rc)
+            return occ, first, pos[:total], st
+        occ = np.zeros(max(ni, 1), np.uint64)
+        first = np.zeros(ni + 1, np.uint64)
+        pos = np.zeros(max(int(positions_cap), 1), np.uint64)
+        err = np.zeros(max(ni, 1), np.uint8)
+        total = C.c_uint64(0)
+        st = QueryStatsC()
+        rc = lib().movi_locate_matches_host(self._h, bases.ctypes.data, offs.ctypes.data, n, items.ctypes.data, ni, int(max_occ),
+                                            occ.ctypes.data, first.ctypes.data, pos.ctypes.data, int(positions_cap), C.byref(total),
+                                            err.ctypes.data, C.byref(st))
+        if want_err:
+            return occ[:ni], first, pos[:int(positions_cap)], QueryStats(st), err[:ni], int(total.value), rc
+        check(rc)
+        return occ[:ni], first, pos[:int(total.value)], QueryStats(st)
+
+    def locate_matches(self, reads, items, max_occ=100):
+        """Per item (read, start, end), ordered by read: (occ, uint64 array of the first min(occ, max_occ) text positions of
+        reads[read][start:end] in BWT order).  What `movi query --count --locate` / `--mem --locate` print."""
+        bases, offs = _pack_reads(reads)
+        occ, first, pos, _ = self.locate_matches_packed(bases, offs, items, max_occ)
+        return [(int(occ[i]), pos[int(first[i]): int(first[i + 1])].copy()) for i in range(occ.size)]
+
     # -- Movi Color: colour tables and multi-class classification -------------------
     MC_DTYPE = np.dtype([("best", "<u2"), ("second", "<u2"), ("colors_count", "<u4"), ("sum_ml", "<u4"), ("best_count", "<u4"), ("second_count", "<u4"), ("reserved_", "<u4")])   # movi_mc_read_t
     DOC_NONE = 0xFFFF
@@ -767,6 +818,15 @@ class MoveIndex:
                                          C.c_void_p(d_sum) if d_sum else None,
                                          C.c_void_p(d_err) if d_err else None,
                                          C.c_void_p(stream) if stream else None))
+
+    def locate_matches_device(self, d_bases, d_offs, n_reads, d_items, n_items, max_occ, d_occ, d_first, d_positions, positions_cap,
+                              d_work, work_bytes, d_item_err=0, stream=0):
+        """movi_locate_matches_device: d_occ[n_items] (u64), d_first[n_items + 1] (u64: exclusive prefix sum of min(occ, max_occ)),
+        text positions of item i in d_positions[d_first[i] : d_first[i + 1]] below positions_cap; d_item_err (u8) optional."""
+        check(lib().movi_locate_matches_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offs), n_reads, C.c_void_p(d_items), n_items,
+                                               int(max_occ), C.c_void_p(d_occ), C.c_void_p(d_first), C.c_void_p(d_positions),
+                                               int(positions_cap), C.c_void_p(d_item_err) if d_item_err else None,
+                                               C.c_void_p(d_work), int(work_bytes), C.c_void_p(stream) if stream else None))
 
     def locate_device(self, d_pos, n_items, stream=0):
         """movi_locate_device: packed positions in, suffix-array entries out, in place."""

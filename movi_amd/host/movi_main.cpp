@@ -214,6 +214,8 @@ struct Job {
     std::vector<movi_mc_read_t> mc;                                   // --multi-classify: best / second / counts per read ...
     std::vector<uint32_t> mc_counts;                                  // ... and, with --report-all, its counter row (num_species per read)
     std::vector<uint64_t> sa;                                         // --sa-entries: one suffix-array entry per base, emission order like pml
+    std::vector<uint64_t> loc_occ, loc_first, loc_pos;                // --locate: per item (a read with matched > 0, in read order; a MEM) its occurrences, and
+                                                                      // the positions of item k in loc_pos[loc_first[k] .. loc_first[k + 1])
     std::vector<uint8_t> err;                                         // per-read error byte
     RawBytes original;                                                // reads as given (--filter after --ignore-illegal-chars 1)
     std::vector<uint32_t> bins_above, bins_below;                     // verdict-only classification
@@ -301,7 +303,7 @@ std::unique_ptr<BatchReader> open_reader(const std::string &path, std::istream &
 struct Outputs {
     // stream buffers first: they must outlive the streams that flush through them on destruction
     std::vector<char> out_buf2 = std::vector<char>(1u << 20);
-    std::ofstream report_file, matches_file, sa_file;
+    std::ofstream report_file, matches_file, sa_file, locs_file;
     std::unique_ptr<WorkerPool> bpf_pool;                             // the writer stage's helper threads (record order, BPF gather; built by the writer thread, outlives mls_file)
     BpfWriter mls_file;
     // --multi-classify writes one report, to the -o file itself (open_output_files, src/utils.cpp:323-326) or to --stdout; the PML
@@ -335,6 +337,7 @@ void open_outputs(const Options &o, const QueryPlan &plan, const std::string &in
     if (plan.mc_to_out_file) open_or_throw(f.mc_file, o.out_file);
     const std::string prefix = !o.out_file.empty() ? o.out_file : o.read_file + "." + index_type;
     if (!plan.matches_suffix.empty()) open_or_throw(f.matches_file, prefix + plan.matches_suffix);
+    if (!plan.locs_suffix.empty()) open_or_throw(f.locs_file, prefix + plan.locs_suffix);
     if (!plan.bpf_suffix.empty()) f.mls_file.open(prefix + plan.bpf_suffix, 16);
     if (!plan.sa_suffix.empty()) open_or_throw(f.sa_file, prefix + plan.sa_suffix, std::ios::out | std::ios::binary);
     // --logs (src/utils.cpp:376-382: opened with the other output files, written by output_logs :268-289 per read)
@@ -399,7 +402,7 @@ struct QueryRun {
 // What the query needs beside the index, and the devices it asks for: checked before anything is loaded.
 void check_inputs_and_devices(QueryRun &q) {
     const Options &o = q.o;
-    if (o.sa_entries && !std::ifstream(o.index_dir + "/ssa.movi").good())      // deserialize_sampled_SA, src/move_structure_io.cpp:727-730
+    if ((o.sa_entries || o.locate) && !std::ifstream(o.index_dir + "/ssa.movi").good())      // deserialize_sampled_SA, src/move_structure_io.cpp:727-730
         throw std::runtime_error("[deserialize sampled SA] Failed to open sampled SA entries file at " + o.index_dir + "/ssa.movi" +
                                  "\nBuild the sampled SA by running the build-SA command.");
     if (o.multi_classify) {
@@ -496,7 +499,7 @@ void load_handles(QueryRun &q) {
 void configure_handles(QueryRun &q) {
     const Options &o = q.o;
     const std::vector<movi_index_t *> &handles = q.handles;
-    if (o.sa_entries)                                                  // deserialize_sampled_SA, src/move_structure_io.cpp:724-744 (every GPU holds the samples beside its table)
+    if (o.sa_entries || o.locate)                                      // deserialize_sampled_SA, src/move_structure_io.cpp:724-744 (every GPU holds the samples beside its table)
         for (auto *hd : handles) check(movi_ssa_load(hd, (o.index_dir + "/ssa.movi").c_str()), "loading the sampled suffix array");
     if (o.multi_classify)                                              // deserialize_doc_sets_flat: every GPU holds the colour tables beside its table
         for (auto *hd : handles) {
@@ -547,6 +550,7 @@ void configure_handles(QueryRun &q) {
 struct ShardOut {                                                     // what a shard returns beside the Job's own arrays
     std::vector<movi_mem_t> mems;                                     // --mem / --kmer: the shard's results, sized by what it found
     std::vector<movi_kmer_run_t> runs;
+    std::vector<uint64_t> loc_occ, loc_first, loc_pos;                // --locate: the shard's items (loc_first: relative to the shard, one more than items)
 };
 
 // MEM and k-mer results: room for a few per read first; a shard that finds more is run again with room for exactly what it found.
@@ -566,8 +570,52 @@ int call_with_room(const Job &job, size_t a, size_t b, std::vector<T> &v, Call c
     return rc;
 }
 
-// Reads [a, b) of the job's chunk on one handle: the only place that names the engine's query entry points.
+// --locate: the shard's hits, after its ordinary query -- one item (i, len - matched, len) per read with matched > 0 of a count query,
+// one per MEM of a MEM query -- through movi_locate_matches_host, which uploads the shard's reads a second time (include/movi_hip.h).
+int locate_shard(const QueryRun &q, movi_index_t *h, const Job &job, size_t a, size_t b, ShardOut &out) {
+    std::vector<movi_match_t> items;
+    if (q.plan.kind == QueryKind::Count) {
+        for (size_t i = a; i < b; i++)
+            if (job.matched[i] > 0) {
+                const uint64_t len = job.rs.len(i);
+                items.push_back(movi_match_t{(uint32_t)(i - a), (uint32_t)(len - std::min<uint64_t>(job.matched[i], len)), (uint32_t)len});
+            }
+    } else {
+        size_t k = 0;
+        for (size_t i = a; i < b; i++)
+            for (uint32_t j = 0; j < job.n_mems[i]; j++, k++) items.push_back(movi_match_t{(uint32_t)(i - a), out.mems[k].start, out.mems[k].end});
+    }
+    const uint64_t ni = items.size();
+    out.loc_occ.assign(ni, 0);
+    out.loc_first.assign(ni + 1, 0);
+    // room for a few positions per item first; a shard that lists more is run again with room for exactly what it lists
+    uint64_t cap = std::min<uint64_t>(ni * q.o.max_occ, ni * 4 + 1024), total = 0;
+    out.loc_pos.resize(cap);
+    auto call = [&]() {
+        return movi_locate_matches_host(h, job.rs.bases.data(), job.rs.offsets.data() + a, b - a, items.data(), ni, q.o.max_occ, out.loc_occ.data(),
+                                        out.loc_first.data(), out.loc_pos.data(), cap, &total, nullptr, nullptr);
+    };
+    int rc = call();
+    if (rc == MOVI_ERR_ARG && total > cap) {
+        cap = total;
+        out.loc_pos.resize(cap);
+        rc = call();
+    }
+    out.loc_pos.resize(rc == MOVI_OK ? total : 0);
+    return rc;
+}
+
+int run_shard_query(const QueryRun &q, movi_index_t *h, Job &job, size_t a, size_t b, ShardOut &out);
+
+// Reads [a, b) of the job's chunk on one handle.
 int run_shard(const QueryRun &q, movi_index_t *h, Job &job, size_t a, size_t b, ShardOut &out) {
+    const int rc = run_shard_query(q, h, job, a, b, out);
+    if (rc != MOVI_OK || !q.plan.locate) return rc;
+    return locate_shard(q, h, job, a, b, out);
+}
+
+// The ordinary query of a shard: the only place that names the engine's query entry points (locate_shard's beside it).
+int run_shard_query(const QueryRun &q, movi_index_t *h, Job &job, size_t a, size_t b, ShardOut &out) {
     const Options &o = q.o;
     const uint8_t *bases = job.rs.bases.data();
     const uint64_t *offs = job.rs.offsets.data() + a;
@@ -795,11 +843,33 @@ void write_text(QueryRun &q, const std::string &txt) {
     out.write(txt.data(), (std::streamsize)txt.size());
 }
 
+// --locate: a chunk's .locs lines in one write -- to stdout in place of the ordinary lines, or to the file beside theirs
+void write_locs_text(QueryRun &q, const std::string &txt) {
+    if (txt.empty()) return;
+    std::ostream &out = q.o.write_stdout_enabled() ? static_cast<std::ostream &>(std::cout) : q.out.locs_file;
+    out.write(txt.data(), (std::streamsize)txt.size());
+}
+
 void write_count_lines(QueryRun &q, const Job &job, const std::vector<uint32_t> &order) {
     std::string txt;
-    txt.reserve(job.rs.size() * 32);
-    for (uint32_t i : order) append_count_line(txt, job.rs.id(i), job.rs.len(i), job.matched[i], job.counts[i]);
-    write_text(q, txt);
+    if (!(q.plan.locate && q.o.write_stdout_enabled())) {
+        txt.reserve(job.rs.size() * 32);
+        for (uint32_t i : order) append_count_line(txt, job.rs.id(i), job.rs.len(i), job.matched[i], job.counts[i]);
+        write_text(q, txt);
+    }
+    if (!q.plan.locate) return;
+    const size_t n = job.rs.size();
+    std::vector<uint64_t> item(n + 1, 0);                              // the item of read i, if it has one: the reads with matched > 0 before it
+    for (size_t i = 0; i < n; i++) item[i + 1] = item[i] + (job.matched[i] > 0 ? 1u : 0u);
+    txt.clear();
+    txt.reserve(n * 48 + job.loc_pos.size() * 10);
+    for (uint32_t i : order) {
+        const bool has = job.matched[i] > 0;
+        const uint64_t k = item[i], f = has ? job.loc_first[k] : 0;
+        append_count_locs_line(txt, job.rs.id(i), job.rs.len(i), job.matched[i], has ? job.loc_occ[k] : 0, job.loc_pos.data() + f,
+                               has ? job.loc_first[k + 1] - f : 0);
+    }
+    write_locs_text(q, txt);
 }
 
 // output_mems, src/utils.cpp:306-316 (file order: no prefetch)
@@ -809,9 +879,19 @@ void write_mem_lines(QueryRun &q, const Job &job, const std::vector<uint32_t> &o
     txt.reserve(n * 32);
     std::vector<uint64_t> first(n + 1, 0);
     for (size_t i = 0; i < n; i++) first[i + 1] = first[i] + job.n_mems[i];
+    if (!(q.plan.locate && q.o.write_stdout_enabled())) {
+        for (uint32_t i : order)
+            for (uint64_t k = first[i]; k < first[i + 1]; k++) append_mem_line(txt, job.rs.id(i), job.mems[k]);
+        write_text(q, txt);
+    }
+    if (!q.plan.locate) return;
+    txt.clear();
+    txt.reserve(job.mems.size() * 48 + job.loc_pos.size() * 10);
     for (uint32_t i : order)
-        for (uint64_t k = first[i]; k < first[i + 1]; k++) append_mem_line(txt, job.rs.id(i), job.mems[k]);
-    write_text(q, txt);
+        for (uint64_t k = first[i]; k < first[i + 1]; k++)
+            append_mem_locs_line(txt, job.rs.id(i), job.mems[k].start, job.mems[k].end, job.loc_occ[k], job.loc_pos.data() + job.loc_first[k],
+                                 job.loc_first[k + 1] - job.loc_first[k]);
+    write_locs_text(q, txt);
 }
 
 // output_kmers, src/utils.cpp:258-266 (file order: no prefetch)
@@ -934,6 +1014,16 @@ void gpu_stage(QueryRun &q) {
             job.mems.clear();
             for (auto &s : shards) job.mems.insert(job.mems.end(), s.mems.begin(), s.mems.end());
         }
+        if (q.plan.locate) {                                          // the shards' items in read order, their firsts made the chunk's
+            job.loc_occ.clear(); job.loc_pos.clear();
+            job.loc_first.assign(1, 0);
+            for (auto &s : shards) {
+                const uint64_t base = job.loc_pos.size();
+                job.loc_occ.insert(job.loc_occ.end(), s.loc_occ.begin(), s.loc_occ.end());
+                for (size_t k = 1; k < s.loc_first.size(); k++) job.loc_first.push_back(base + s.loc_first[k]);
+                job.loc_pos.insert(job.loc_pos.end(), s.loc_pos.begin(), s.loc_pos.end());
+            }
+        }
         if (o.kmer_occ)                                               // the summary's totals (--no-output still prints them)
             for (size_t i = 0; i < n; i++) { q.occ_found_total += job.occ_found[i]; q.occ_sum_total += job.occ_sum[i]; }
         q.reads_done += n;
@@ -1033,6 +1123,7 @@ int run_query(const Options &o) {
     if (q.parse_error) std::rethrow_exception(q.parse_error);
     q.out.mls_file.close();
     if (q.out.sa_file.is_open()) q.out.sa_file.close();
+    if (q.out.locs_file.is_open()) q.out.locs_file.close();
     report_run(q);
     if (o.kmer_occ) {                                                  // the two totals the reference's --kmer-count prints (include/sequitur.hpp:12-14)
         std::ostream &sum_out = o.write_stdout ? std::cerr : std::cout;   // (--stdout: the lines own stdout)

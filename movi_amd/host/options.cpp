@@ -1,5 +1,6 @@
 #include "options.hpp"
 
+#include <cerrno>
 #include <cstdlib>
 #include <map>
 #include <set>
@@ -43,6 +44,7 @@ const Spec kSpecs[] = {
     {"zml", 0, false},           {"mem", 0, false},         {"rpml", 0, false},
     {"kmer", 0, false},          {"kmer-count", 0, false},  {"sa-entries", 0, false},
     {"kmer-occ", 0, false},      // occurrences per k-mer: this engine's own query (not the reference's --kmer-count)
+    {"locate", 0, false},        {"max-occ", 0, true},      // text positions of count / MEM hits: this engine's own (include/movi_hip.h)
     {"ftab-k", 0, true},         {"multi-ftab", 0, false},
     {"k-length", 'k', true},     {"min-mem-length", 'l', true},
 };
@@ -92,6 +94,8 @@ std::string usage() {
            "       movi query -i DIR -r FILE|- --kmer [-k K] [--ftab-k K'] [-o PREFIX] [--stdout] [--no-output]\n"
            "                      [--reverse] [--ignore-illegal-chars 1] [--gpus N] [--device D]   (--kmer-count, --rpml: not supported)\n"
            "       movi query -i DIR -r FILE|- --kmer-occ [-k K] [--ftab-k K'] ...   (occurrences of every k-mer in the text -> <prefix>.kmer_occ.<k>)\n"
+           "       movi query -i DIR -r FILE|- --count|--mem ... --locate [--max-occ N]   (text positions of the hits -> <prefix>.matches.locs /\n"
+           "                      <prefix>.mems.locs, at most N per match, default 100; after build-SA)\n"
            "       movi query -i DIR -r FILE|- --sa-entries [-o PREFIX] [--no-output] ...   (PML + <prefix>.sa_entries.bpf; after build-SA)\n"
            "       movi query -i DIR -r FILE|- --multi-classify -o REPORT|--stdout [--min-len N] [--report-all [--min-diff-frac F | --min-score-frac F]]\n"
            "                      [--no-output] [--reverse] [--gpus N] [--device D]   (after movi color; default colour mode only)\n"
@@ -228,6 +232,21 @@ Options parse_args(int argc, char **argv) {
                 throw UsageError("--kmer-occ cannot be combined with --classify, --filter, --logs, --sa-entries or --multi-classify");
             if (o.k == 0) throw UsageError("-k / --k-length must be at least 1");
             o.prefetch = false;                                   // file order, as --kmer
+        }
+        o.locate = has("locate");
+        if (o.locate) {
+            if (!o.count && !o.mem) throw UsageError("--locate reports the text positions of count or MEM hits: it needs --count or --mem");
+            if (o.classify || o.logs) throw UsageError("--locate cannot be combined with --classify, --filter or --logs");
+        }
+        if (has("max-occ")) {
+            if (!o.locate) throw UsageError("--max-occ belongs to --locate");
+            const std::string &mv = val("max-occ");
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long v = std::strtoull(mv.c_str(), &end, 10);
+            if (mv.empty() || mv[0] < '0' || mv[0] > '9' || (end && *end) || errno || v < 1 || v > 0xFFFFFFFFull)
+                throw UsageError("--max-occ must be between 1 and 4294967295");
+            o.max_occ = (uint32_t)v;
         }
         o.sa_entries = has("sa-entries");
         if (o.sa_entries) {

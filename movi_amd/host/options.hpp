@@ -30,6 +30,8 @@ struct Options {
     bool mem = false;             // --mem: maximal exact matches (src/mem_finder.cpp), one line per MEM
     bool kmer = false;            // --kmer: k-mer presence (src/sequitur.cpp:322-421), one line per read
     bool kmer_occ = false;        // --kmer-occ: occurrences of every k-mer in the text (include/movi_hip.h: movi_kmer_occ_host), one line per read
+    bool locate = false;          // --locate: text positions of the count / MEM hits beside the ordinary file (needs INDEX/ssa.movi: build-SA)
+    uint32_t max_occ = 100;       // --max-occ: positions listed per match at most (1 .. 2^32 - 1)
     bool sa_entries = false;      // --sa-entries: one suffix-array entry per base beside the PML file (needs INDEX/ssa.movi: build-SA)
     bool multi_classify = false;  // --multi-classify: PML walk + document scoring, one report line per read (needs INDEX/doc_sets_flat.bin: movi color)
     uint32_t min_len = 1;         // --min-len (uint8_t, movi_options.hpp: min_match_len)

@@ -466,6 +466,58 @@ void append_kmer_occ_line(std::string &txt, std::string_view id, uint64_t query_
     txt.push_back('\n');
 }
 
+// `movi query --count --locate` / `--mem --locate`: this engine's own files (include/movi_hip.h: movi_locate_matches_host).
+namespace {
+void append_locs_tail(std::string &txt, uint64_t occ, const uint64_t *pos, uint64_t listed) {
+    char num[24];
+    auto put = [&](uint64_t v) {
+        const auto r = std::to_chars(num, num + sizeof(num), v);
+        txt.append(num, (size_t)(r.ptr - num));
+    };
+    put(occ);
+    txt.push_back('\t');
+    put(listed);
+    txt.push_back('\t');
+    for (uint64_t k = 0; k < listed; k++) {
+        if (k) txt.push_back(',');
+        put(pos[k]);
+    }
+    txt.push_back('\n');
+}
+}  // namespace
+
+void append_count_locs_line(std::string &txt, std::string_view id, uint64_t query_length, uint64_t matched, uint64_t occ,
+                            const uint64_t *pos, uint64_t listed) {
+    char num[24];
+    auto put = [&](uint64_t v) {
+        const auto r = std::to_chars(num, num + sizeof(num), v);
+        txt.append(num, (size_t)(r.ptr - num));
+    };
+    txt.append(id.data(), id.size());
+    txt.push_back('\t');
+    put(matched);
+    txt.push_back('/');
+    put(query_length);
+    txt.push_back('\t');
+    append_locs_tail(txt, occ, pos, listed);
+}
+
+void append_mem_locs_line(std::string &txt, std::string_view id, uint64_t start, uint64_t end, uint64_t occ, const uint64_t *pos,
+                          uint64_t listed) {
+    char num[24];
+    auto put = [&](uint64_t v) {
+        const auto r = std::to_chars(num, num + sizeof(num), v);
+        txt.append(num, (size_t)(r.ptr - num));
+    };
+    txt.append(id.data(), id.size());
+    txt.push_back('\t');
+    put(start);
+    txt.push_back('\t');
+    put(end);
+    txt.push_back('\t');
+    append_locs_tail(txt, occ, pos, listed);
+}
+
 void append_count_line(std::string &txt, std::string_view id, uint64_t query_length, uint64_t matched, uint64_t count) {
     char num[24];
     auto put = [&](uint64_t v) {

@@ -73,6 +73,13 @@ void append_kmer_line(std::string &txt, std::string_view id, uint64_t query_leng
 // list is empty when all = 0); occ: the read's slots of movi_kmer_occ_host, of which the first `all` are written
 void append_kmer_occ_line(std::string &txt, std::string_view id, uint64_t query_length, uint32_t k, uint64_t found, uint64_t sum,
                           const uint64_t *occ);
+// one line of `movi query --count --locate` (<prefix>.matches.locs): `id<TAB>matched/len<TAB>occ<TAB>listed<TAB>p,p,...<LF>` -- occ in full
+// 64 bits, `listed` text positions in BWT order, the last field empty when listed = 0 (a read with matched = 0: occ = listed = 0) --
+// and of `movi query --mem --locate` (<prefix>.mems.locs): `id<TAB>start<TAB>end<TAB>occ<TAB>listed<TAB>p,p,...<LF>`
+void append_count_locs_line(std::string &txt, std::string_view id, uint64_t query_length, uint64_t matched, uint64_t occ,
+                            const uint64_t *pos, uint64_t listed);
+void append_mem_locs_line(std::string &txt, std::string_view id, uint64_t start, uint64_t end, uint64_t occ, const uint64_t *pos,
+                          uint64_t listed);
 void append_mem_line(std::string &txt, std::string_view id, const movi_mem_t &m);   // one MEM line (output_mems, count as u16)   // the same line, appended
 
 // Movi Color.  DocInfo: MoveStructure::load_document_info (src/move_structure_io.cpp:643-687) -- DIR/ref.fa.doc_offsets (cumulative

@@ -47,6 +47,8 @@ struct QueryPlan {
     std::string sa_suffix;     // prefix + this: the suffix-array entries beside it
     std::string matches_suffix;// prefix + this: the text file of a count, MEM, k-mer or k-mer occurrence query
     std::string logs_stem;     // prefix + this + ".costs" / ".scans" / ".fastforwards"
+    bool locate;               // --locate on a count or MEM query: the shard also locates its hits (movi_locate_matches_host)
+    std::string locs_suffix;   // prefix + this: their text positions, one line per line of the matches file ("" = none, or they go to stdout)
 };
 
 inline QueryPlan query_plan(const Options &o) {
@@ -87,6 +89,11 @@ inline QueryPlan query_plan(const Options &o) {
         } else p.matches_suffix = "." + o.query_type() + ".matches";
     }
     if (p.logs) p.logs_stem = "." + o.query_type();
+    p.locate = o.locate && (o.count || o.mem);
+    if (p.locate) {
+        p.prepare |= (int)MOVI_PREPARE_SA;                                                 // (kind Count / Mem: MOVI_PREPARE_COUNT so far)
+        if (p.open_files) p.locs_suffix = p.matches_suffix + ".locs";
+    }
     return p;
 }
 
