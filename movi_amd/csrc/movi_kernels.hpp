@@ -420,15 +420,17 @@ hipError_t launch_kmer(int mode, const DevIndex &ix, const KmerArgs &a, const ui
                        DevStats *d_stats, const uint32_t *d_order, hipStream_t stream, LaunchInfo *info);
 
 // k-mer occurrences (movi_walk_kmer_occ.hip): d_occ[offsets[i] + p] = occurrences of the k-mer at p of read i, over all n_bases slots;
-// d_found / d_sum / d_err per read, each optional.  Mark, search and reduction, three kernels on `stream`; no scratch.
+// d_found / d_sum / d_err per read, each optional.  Mark, search (search_lists, movi_search.hpp) and reduction, three kernels on
+// `stream`; no scratch.
 constexpr int kKmerOccWaves = 16;    // kmer_occ_kernel: one-wavefront blocks per CU a launch fills at most (a lane then owns a list of slots)
 hipError_t launch_kmer_occ(int mode, const DevIndex &ix, uint32_t k, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
                            uint64_t n_bases, uint64_t *d_occ, uint32_t *d_found, uint64_t *d_sum, uint8_t *d_err, DevStats *d_stats,
                            int num_cus, hipStream_t stream, LaunchInfo *info);
 hipError_t preload_kmer_occ(int mode, bool idx32);   // load the translation unit's code object now (movi_index_prepare)
 
-// Locate (movi_walk_sa.hip; MoveStructure::get_SA_entries, src/move_structure.cpp:35-48; the layouts are stated in movi_sa.hpp).
-constexpr int kLocateWaves = 16;     // locate_kernel: one-wavefront blocks per CU a launch fills at most (a lane then owns a list of items)
+// Locate (movi_walk_sa.hip; MoveStructure::get_SA_entries, src/move_structure.cpp:35-48; the layouts and the walk, locate_walk, are
+// stated in movi_sa.hpp, the lanes' item lists in movi_lists.hpp).
+constexpr int kLocateWaves = 16;     // locate_kernel, hits_walk_kernel, color_walk_kernel: one-wavefront blocks per CU a launch fills at most (a lane then owns a list of items)
 struct LocArgs {
     const uint4 *rows = nullptr;        // the locate rows: 16 bytes per row
     const uint64_t *samples = nullptr;  // n / rate + 1 entries (not read in successor mode)
@@ -455,8 +457,8 @@ hipError_t build_sampled_sa(int mode, const DevIndex &ix, const LocArgs &loc, ui
 hipError_t preload_sa(int mode, bool idx32);   // load the translation unit's code object now (movi_index_prepare)
 // Locate count and MEM hits (movi_walk_hits.hip): per match item (read, start, end) the occurrences of P[start .. end) in the text --
 // d_occ[i] --, the exclusive prefix sum of min(occ, max_occ) -- d_first[0 .. n_items] --, and the text positions of those hits in BWT
-// order in d_positions[d_first[i] .. d_first[i + 1]) as far as they lie below positions_cap.  Interval search, scan, expansion and
-// locate walk on `stream`; the intervals, the scan's input and its temporary storage live in d_work (hits_work_layout).  stages: 3 = the
+// order in d_positions[d_first[i] .. d_first[i + 1]) as far as they lie below positions_cap.  Interval search (search_lists,
+// movi_search.hpp), scan, expansion and locate walk (locate_walk, movi_sa.hpp) on `stream`; the intervals, the scan's input and its temporary storage live in d_work (hits_work_layout).  stages: 3 = the
 // whole call; 1 / 2 = stop after the scan / the expansion (a measurement hook: the steps timed apart).
 struct HitsItem { uint32_t read, start, end; };          // movi_match_t
 constexpr int kHitsWaves = 16;                           // hits_interval_kernel: one-wavefront blocks per CU a launch fills at most

@@ -5,9 +5,10 @@
 //     all_p[i] % rate in the low 24 (all_p[i] = BWT position of the row's first character; rate <= 2^24).  "Is all_p[idx] + offset a
 //     multiple of rate" is then 32-bit arithmetic on the one 16-byte gather a step makes anyway, and the sample's index at the end of a
 //     walk is quotient + (remainder + offset) / rate;
-//   * loc_lf_step: LF_move + fast_forward (src/move_structure.cpp:59-87) on those rows.
+//   * loc_lf_step: LF_move + fast_forward (src/move_structure.cpp:59-87) on those rows;
+//   * locate_walk: the loop over loc_lf_step that locate_kernel and hits_walk_kernel (movi_walk_hits.hip) share.
 #pragma once
-#include "movi_device.hpp"
+#include "movi_lists.hpp"
 
 namespace movi {
 
@@ -73,21 +74,62 @@ __device__ __forceinline__ uint32_t loc_lf_step(const uint4 *__restrict__ rows, 
     return errc;
 }
 
-// The lane's counters to DevStats (may be null), one atomic per wavefront and counter; errs = items of the lane that failed.
-__device__ __forceinline__ void flush_lane_stats_sa(DevStats *stats, uint32_t ff_total, uint32_t errs, uint64_t lane_steps, uint64_t wave_steps) {
-    const uint32_t erw = wave_sum(errs);
-    unsigned long long ffw = ff_total, lsw = lane_steps;              // summed in 64 bits: 64 lanes of long walks pass 2^32
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        ffw += __shfl_xor(ffw, s, 64);
-        lsw += __shfl_xor(lsw, s, 64);
+// The locate walks of the items [0, n_items) of `pos`, in place: the loop of locate_kernel (movi_walk_sa.hip) and hits_walk_kernel
+// (movi_walk_hits.hip), on the lanes' lists (movi_lists.hpp).  Walk lengths are roughly geometric with mean `rate`; every iteration of
+// a lane is one dependent gather, a 16-byte locate row.  A walk ends on the first position that is a multiple of the rate -- in
+// successor mode (a.succ) not on the one it starts from -- : on_hit(item, s, dist) stores the answer for sample s reached after dist
+// steps and returns false where it had to refuse it; on_fail(item) stores the failure of a walk that broke an invariant of the table
+// (the reference's throws; more than n steps: an error, not a hang).  An item that is kPosNone stays; one that is not a position of
+// the table becomes kPosNone.  Every refusal and failure is counted in DevStats::errors.
+template <int MODE, typename IdxT, typename OnHit, typename OnFail>
+__device__ __forceinline__ void locate_walk(const DevIndex &ix, const LocArgs &a, uint64_t *__restrict__ pos, uint64_t n_items, DevStats *stats,
+                                            OnHit on_hit, OnFail on_fail) {
+    LaneList ls(n_items);
+    IdxT kidx = 0;
+    uint32_t off = 0, ff_total = 0, errs = 0;
+    uint64_t dist = 0, lane_steps = 0, wave_steps = 0;      // (64 bits: a rate above n on a large table makes walks of n steps)
+    uint4 v = make_uint4(0, 0, 0, 0);
+    const uint32_t rate = a.rate;
+    while (ls.any()) {
+        wave_steps += 1;
+        if (ls.state == 1u) {                             // the lane's next item
+            const uint64_t p = pos[ls.item];
+            const uint64_t row = p >> kPosOffBits;
+            if (p != kPosNone && row < ix.r) {
+                kidx = (IdxT)row;
+                off = (uint32_t)p & ((1u << kPosOffBits) - 1u);
+                v = loc_load(a.rows, row);
+                dist = 0;
+                ls.state = 2u;
+            } else {
+                if (p != kPosNone) { errs += 1; pos[ls.item] = kPosNone; }
+                ls.next();
+            }
+        }
+        uint32_t t = 0;
+        bool hit = false;
+        if (ls.state == 2u) {
+            t = loc_rem(v) + off;                         // < 2^24 + 2^12
+            hit = (t % rate == 0u) && !(a.succ != 0u && dist == 0);
+        }
+        if (hit) {
+            if (!on_hit(ls.item, loc_quot(v) + t / rate, dist)) errs += 1;
+            ls.next();
+        }
+        const bool walk = ls.state == 2u;                 // (a lane that took up an item above steps in this same iteration)
+        uint64_t idx = kidx;
+        const uint32_t e = loc_lf_step<MODE>(a.rows, ix.r, walk, idx, off, v, ff_total, [&]() {
+            lane_steps += walk ? 1u : 0u;
+            dist += walk ? 1u : 0u;
+        });
+        kidx = (IdxT)idx;
+        if (walk && (e != 0u || dist > a.n)) {            // a corrupt table
+            errs += 1;
+            on_fail(ls.item);
+            ls.next();
+        }
     }
-    if ((threadIdx.x & 63) == 0 && stats) {
-        if (ffw) atomicAdd(&stats->fast_forwards, ffw);
-        if (erw) atomicAdd(&stats->errors, (unsigned long long)erw);
-        atomicAdd(&stats->lane_steps, lsw);
-        atomicAdd(&stats->wave_steps, (unsigned long long)wave_steps);
-    }
+    flush_list_stats(stats, ff_total, 0u, errs, lane_steps, wave_steps);
 }
 
 }  // namespace movi

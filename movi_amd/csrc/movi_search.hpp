@@ -4,9 +4,12 @@
 //     checkpoints behind MoveInterval::count (row_start);
 //   * the entry of the interval table (DevIndex::ftab): FtabEntry, ftab_encode, ftab_decode -- its bit layout is stated there only;
 //   * for the lane-per-read queries (MEM, k-mers): the prologue (read_lane), the interval step (search_step), the counters' way
-//     out (flush_lane_stats) and the launch (launch_lane_per_read).
+//     out (flush_lane_stats) and the launch (launch_lane_per_read);
+//   * for the queries whose lanes own lists of patterns (k-mer occurrences, the hits' intervals): the loop (search_lists) and the
+//     interval's size (interval_count);
+//   * the launch of a MODE x IdxT kernel family: family_kernel, launch_lane_per_read, launch_lane_lists, preload_family.
 #pragma once
-#include "movi_device.hpp"
+#include "movi_lists.hpp"
 
 namespace movi {
 
@@ -134,6 +137,19 @@ __device__ __forceinline__ uint64_t row_start(const DevIndex &ix, uint64_t k) {
     uint64_t p = ix.row_start_ckpt[k >> kPrefixShift];
     for (; j < k; ++j) p += row_n<MODE>(load_row<MODE>(ix.rows, j));
     return p;
+}
+
+// MoveInterval::count (include/move_intervals.hpp:47-58) of the non-empty interval from (rs, os) to (re, oe), rws = row rs: inside one
+// row from the offsets, inside a checkpoint block's reach from the rows between the ends, else from the checkpoints.
+template <int MODE>
+__device__ __forceinline__ uint64_t interval_count(const DevIndex &ix, uint64_t rs, uint32_t os, uint2 rws, uint64_t re, uint32_t oe) {
+    if (rs == re) return (uint64_t)oe - os + 1;
+    if (re - rs < (1ull << kPrefixShift)) {
+        uint64_t v = (uint64_t)row_n<MODE>(rws) - os + oe + 1;
+        for (uint64_t j = rs + 1; j < re; ++j) v += row_n<MODE>(load_row<MODE>(ix.rows, j));
+        return v;
+    }
+    return (row_start<MODE>(ix, re) + oe) - (row_start<MODE>(ix, rs) + os) + 1;
 }
 
 // ---- entry of the interval table (DevIndex::ftab): the interval after the K bases of its index, and what reaching it cost.
@@ -271,8 +287,69 @@ __device__ __forceinline__ void flush_lane_stats(DevStats *stats, uint32_t ff_to
     }
 }
 
-// Launch of a kernel family F -- F::kernel<MODE, IdxT>() = the __global__ function (DevIndex, args...) -- one lane per read in blocks of
-// one wavefront, MODE in {6, 3} x IdxT in {uint32_t, uint64_t (DevIndex::idx32 == 0)}; noted and reported as "<name><MODE, IdxT>".
+// The searches of a launch whose lanes own lists of patterns (movi_lists.hpp), one pattern per item, searched leftwards from its last
+// base by search_step -- the interval table's lookup first where K <= lim -- until it dies, hits one of the reference's LF throws or
+// all its lim bases are taken.
+//   take(item, last, lim)                  false: the item holds no pattern (one iteration); else the address of the pattern's last
+//                                          base and its length;
+//   done(item, st, rs, os, rws, re, oe)    the search is over: st.err != 0, st.taken == 0 (the pattern does not occur) or else the
+//                                          interval of the whole pattern.  Returns false where the item failed (DevStats::errors).
+// IdxT: the type the lane's interval rows are kept in between iterations (uint32_t when DevIndex::idx32).
+template <int MODE, typename IdxT, typename Take, typename Done>
+__device__ __forceinline__ void search_lists(const DevIndex &ix, uint64_t n_items, DevStats *stats, Take take, Done done) {
+    __shared__ uint8_t s_code[256];
+    for (int i = threadIdx.x; i < 256; i += blockDim.x) s_code[i] = ix.code_of[i];
+    __syncthreads();
+    LaneList ls(n_items);
+    uint32_t l = 0, lim = 0;                              // bases of the pattern taken (the interval is non-empty after each), its length
+    const uint8_t *last = nullptr;                        // the pattern's last base
+    uint32_t ff_total = 0, scan_total = 0, errs = 0;
+    uint64_t lane_steps = 0, wave_steps = 0;
+    IdxT krs = 0, kre = 0;
+    uint32_t os = 0, oe = 0;
+    uint2 rws = make_uint2(0, 0), rwe = make_uint2(0, 0);
+    while (ls.any()) {
+        wave_steps += 1;
+        if (ls.state == 1u) {                             // the lane's next item
+            if (take(ls.item, last, lim)) { l = 0; ls.state = 2u; }
+            else ls.next();
+        }
+        const bool live = ls.state == 2u;                 // (a lane that took up an item above steps in this same iteration)
+        lane_steps += live ? 1u : 0u;
+        // ---- one step leftwards on the pattern's next base: last[-l - i], i < lim - l
+        uint64_t rs = krs, re = kre;
+        const uint8_t *R = last - l;
+        auto base_at = [&](uint32_t i) { return (uint32_t)s_code[*(R - i)]; };
+        auto keep = [](uint64_t, uint64_t, uint32_t, uint32_t) {};
+        const SearchStep st = search_step<MODE>(ix, live, lim, l, base_at, keep, rs, os, rws, re, oe, rwe, ff_total, scan_total);
+        krs = (IdxT)rs; kre = (IdxT)re;
+        if (live && (st.err != 0u || st.taken == 0u || l == lim)) {
+            if (!done(ls.item, st, rs, os, rws, re, oe)) errs += 1;
+            ls.next();
+        }
+    }
+    flush_list_stats(stats, ff_total, scan_total, errs, lane_steps, wave_steps);
+}
+
+// ---- the launch of a kernel family F: F::kernel<MODE, IdxT>() = the __global__ function (DevIndex, args...), MODE in {6, 3} x IdxT
+// in {uint32_t, uint64_t (DevIndex::idx32 == 0)}, in blocks of one wavefront; noted and reported as "<name><MODE, IdxT>".
+template <typename F>
+auto family_kernel(int mode, bool idx32) {                // mode: 6 or 3
+    return mode == 6 ? (idx32 ? F::template kernel<6, uint32_t>() : F::template kernel<6, uint64_t>())
+                     : (idx32 ? F::template kernel<3, uint32_t>() : F::template kernel<3, uint64_t>());
+}
+inline void note_family_launch(const char *name, int variant, int mode, const DevIndex &ix, int waves, LaunchInfo *info) {
+    char nm[96];
+    snprintf(nm, sizeof(nm), "%s<%d, %s>", name, mode, ix.idx32 ? "unsigned int" : "unsigned long");
+    note_walk_launch(nm);
+    if (info) {
+        *info = LaunchInfo();
+        snprintf(info->kernel, sizeof(info->kernel), "%s", nm);
+        info->variant = variant; info->block_threads = 64; info->idx64 = ix.idx32 ? 0 : 1; info->waves_per_cu = waves;
+    }
+}
+
+// One lane per read.
 template <typename F, typename... Args>
 hipError_t launch_lane_per_read(const char *name, int variant, int mode, const DevIndex &ix, uint64_t n_reads, hipStream_t stream,
                                 LaunchInfo *info, Args... args) {
@@ -280,18 +357,30 @@ hipError_t launch_lane_per_read(const char *name, int variant, int mode, const D
     if (mode != 6 && mode != 3) return hipErrorInvalidValue;
     const uint64_t blocks = (n_reads + 63) / 64;
     if (blocks > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    char nm[96];
-    snprintf(nm, sizeof(nm), "%s<%d, %s>", name, mode, ix.idx32 ? "unsigned int" : "unsigned long");
-    note_walk_launch(nm);
-    if (info) {
-        *info = LaunchInfo();
-        snprintf(info->kernel, sizeof(info->kernel), "%s", nm);
-        info->variant = variant; info->block_threads = 64; info->idx64 = ix.idx32 ? 0 : 1;
-    }
-    auto kernel = mode == 6 ? (ix.idx32 ? F::template kernel<6, uint32_t>() : F::template kernel<6, uint64_t>())
-                            : (ix.idx32 ? F::template kernel<3, uint32_t>() : F::template kernel<3, uint64_t>());
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64), 0, stream, ix, args...);
+    note_family_launch(name, variant, mode, ix, 0, info);
+    hipLaunchKernelGGL(family_kernel<F>(mode, ix.idx32 != 0u), dim3((unsigned)blocks), dim3(64), 0, stream, ix, args...);
     return hipGetLastError();
+}
+
+// A list of the n_items items per lane (movi_lists.hpp): at most `waves` one-wavefront blocks per CU, so that a lane's list holds many
+// items wherever there are many.  n_items: the host's count, or its upper bound where only the device knows the count
+// (hits_walk_kernel); 0 is noted and reported, not launched (the k-mer occurrences of reads without bases).
+template <typename F, typename... Args>
+hipError_t launch_lane_lists(const char *name, int variant, int mode, const DevIndex &ix, uint64_t n_items, int waves, int num_cus,
+                             hipStream_t stream, LaunchInfo *info, Args... args) {
+    if (mode != 6 && mode != 3) return hipErrorInvalidValue;
+    note_family_launch(name, variant, mode, ix, waves, info);
+    if (n_items == 0) return hipSuccess;
+    const uint64_t want = (n_items + 63) / 64, cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * (uint64_t)waves;
+    hipLaunchKernelGGL(family_kernel<F>(mode, ix.idx32 != 0u), dim3((unsigned)(want < cap ? want : cap)), dim3(64), 0, stream, ix, args...);
+    return hipGetLastError();
+}
+
+// Loads the family's code object now (movi_index_prepare: a first call may then be captured).
+template <typename F>
+hipError_t preload_family(int mode, bool idx32) {
+    hipFuncAttributes at;
+    return hipFuncGetAttributes(&at, (const void *)family_kernel<F>(mode, idx32));
 }
 
 }  // namespace movi

@@ -9,6 +9,7 @@
 //                      where the reference has it: after the LF step, before the base is compared.
 // The contract is stated in include/movi_hip.h (movi_color_build, movi_multi_classify_device); the tables in movi_color.hpp.
 // (Named into the movi_walk*.hip family: the sanitizer build of tests/fuzz/fuzz_parse.sh compiles the library from that glob.)
+#include "movi_search.hpp"
 #include "movi_color.hpp"
 
 #include <chrono>
@@ -22,8 +23,8 @@ namespace movi {
 // The samples sorted by their text position cut the text into stretches: item i (sample tj[i], text position tv[i]) owns the positions
 // tv[i], tv[i] - 1, ..., tv[i - 1] + 1 -- len = tv[i] - tv[i - 1] of them, tv[-1] = -1 -- and must then stand on sample tj[i - 1] (the
 // lowest one walks through text position 0 to BWT position 0, sample 0).  A chunk of items is a stretch of the text, so its keys are
-// indexed by text position and every slot has exactly one writer.  Strided item lists, one-wavefront blocks and the ballot loop are
-// locate_kernel's.  bad[0] counts what a consistent table and array cannot produce: a walk that meets a sample too early, too late
+// indexed by text position and every slot has exactly one writer.  The lanes own lists of items (LaneList, movi_lists.hpp) and step by
+// loc_lf_step, as locate_walk's do.  bad[0] counts what a consistent table and array cannot produce: a walk that meets a sample too early, too late
 // or meets the wrong one, a position outside the table, a BWT position passed twice (the bitmap `visited`).
 struct ColWalkArgs {
     const uint64_t *P;         // packed position of every sample
@@ -38,18 +39,16 @@ struct ColWalkArgs {
 
 template <int MODE, typename IdxT>
 __global__ __launch_bounds__(64) void color_walk_kernel(DevIndex ix, LocArgs a, ColWalkArgs c, uint64_t n_items, DevStats *stats) {
-    const uint64_t stride = (uint64_t)gridDim.x * 64u;
-    uint64_t item = (uint64_t)blockIdx.x * 64u + threadIdx.x;
-    uint32_t state = item < n_items ? 1u : 0u;            // 0 = list done, 1 = take up `item`, 2 = walking
+    LaneList ls(n_items);
     IdxT kidx = 0;
     uint32_t off = 0, ff_total = 0, errs = 0, doc = 0;
     uint64_t dist = 0, len = 0, t = 0, expect = 0, doc_lo = 0, lane_steps = 0, wave_steps = 0;
     uint4 v = make_uint4(0, 0, 0, 0);
     const uint32_t rate = a.rate;
-    while (wave_any(state != 0u)) {
+    while (ls.any()) {
         wave_steps += 1;
-        if (state == 1u) {                                // the lane's next item
-            const uint64_t i = c.i0 + item, j = c.tj[i];
+        if (ls.state == 1u) {                             // the lane's next item
+            const uint64_t i = c.i0 + ls.item, j = c.tj[i];
             t = c.tv[i];
             len = i ? t - c.tv[i - 1] : t + 1;
             expect = i ? c.tj[i - 1] : 0;
@@ -70,23 +69,21 @@ __global__ __launch_bounds__(64) void color_walk_kernel(DevIndex ix, LocArgs a, 
                 }
                 doc = lo;
                 doc_lo = doc ? c.doc_ends[doc - 1] : 0;
-                state = 2u;
+                ls.state = 2u;
             } else {
                 errs += 1;
-                item += stride;
-                state = item < n_items ? 1u : 0u;
+                ls.next();
             }
         }
-        if (state == 2u) {
+        if (ls.state == 2u) {
             const uint32_t tp = loc_rem(v) + off;         // < 2^24 + 2^12
             const bool hit = (tp % rate == 0u) && dist != 0;
             if (hit || dist >= len) {                     // the walk is over: on the expected sample after len steps, or an error
                 if (!(hit && dist == len && loc_quot(v) + tp / rate == expect)) errs += 1;
-                item += stride;
-                state = item < n_items ? 1u : 0u;
+                ls.next();
             }
         }
-        const bool walk = state == 2u;                    // (a lane that took up an item above steps in this same iteration)
+        const bool walk = ls.state == 2u;                 // (a lane that took up an item above steps in this same iteration)
         uint64_t idx = kidx;
         const uint64_t bwt = loc_quot(v) * rate + loc_rem(v) + off, row_now = kidx, tt = t - dist;
         const uint32_t e = loc_lf_step<MODE>(a.rows, ix.r, walk, idx, off, v, ff_total, [&]() {
@@ -105,12 +102,11 @@ __global__ __launch_bounds__(64) void color_walk_kernel(DevIndex ix, LocArgs a, 
         kidx = (IdxT)idx;
         if (walk && e != 0u) {                            // a corrupt table: an error, not a hang
             errs += 1;
-            item += stride;
-            state = item < n_items ? 1u : 0u;
+            ls.next();
         }
     }
     if (errs) atomicAdd(c.bad, errs);
-    flush_lane_stats_sa(stats, ff_total, 0u, lane_steps, wave_steps);
+    flush_list_stats(stats, ff_total, 0u, 0u, lane_steps, wave_steps);
 }
 
 namespace {
@@ -122,34 +118,9 @@ __global__ __launch_bounds__(256) void iota_kernel(uint64_t *out, uint64_t n) {
 
 unsigned blocks256(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
-template <int MODE, typename IdxT>
-void launch_color_walk_t(unsigned blocks, hipStream_t stream, const DevIndex &ix, const LocArgs &a, const ColWalkArgs &c, uint64_t n_items, DevStats *d_stats) {
-    hipLaunchKernelGGL((color_walk_kernel<MODE, IdxT>), dim3(blocks), dim3(64), 0, stream, ix, a, c, n_items, d_stats);
-}
-
-hipError_t launch_color_walk(int mode, const DevIndex &ix, const LocArgs &a, const ColWalkArgs &c, uint64_t n_items, DevStats *d_stats,
-                             int num_cus, hipStream_t stream, LaunchInfo *info) {
-    if (n_items == 0) return hipSuccess;
-    const uint64_t want = (n_items + 63) / 64, cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * kLocateWaves;
-    const unsigned blocks = (unsigned)(want < cap ? want : cap);
-    char nm[96];
-    snprintf(nm, sizeof(nm), "color_walk_kernel<%d, %s>", mode, ix.idx32 ? "unsigned int" : "unsigned long");
-    note_walk_launch(nm);
-    if (info) {
-        *info = LaunchInfo();
-        snprintf(info->kernel, sizeof(info->kernel), "%s", nm);
-        info->variant = 0; info->block_threads = 64; info->idx64 = ix.idx32 ? 0 : 1;
-        info->waves_per_cu = kLocateWaves;
-    }
-    if (mode == 6) {
-        if (ix.idx32) launch_color_walk_t<6, uint32_t>(blocks, stream, ix, a, c, n_items, d_stats);
-        else launch_color_walk_t<6, uint64_t>(blocks, stream, ix, a, c, n_items, d_stats);
-    } else {
-        if (ix.idx32) launch_color_walk_t<3, uint32_t>(blocks, stream, ix, a, c, n_items, d_stats);
-        else launch_color_walk_t<3, uint64_t>(blocks, stream, ix, a, c, n_items, d_stats);
-    }
-    return hipGetLastError();
-}
+struct ColorWalkFamily {
+    template <int MODE, typename IdxT> static auto kernel() { return &color_walk_kernel<MODE, IdxT>; }
+};
 
 double seconds_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -246,7 +217,8 @@ hipError_t build_color_keys(int mode, const DevIndex &ix, const LocArgs &loc, co
         if (acc + n_keys > cap) { e = hipErrorOutOfMemory; break; }
         ColWalkArgs c{d_P, d_tv, d_tj, i0, tlo, n_keys, d_ends, d_ids, n_docs, doc_bits + 1, d_a + acc, d_visited, d_bad};
         auto tw = std::chrono::steady_clock::now();
-        e = launch_color_walk(mode, ix, loc, c, i1 - i0, nullptr, num_cus, stream, info);
+        e = launch_lane_lists<ColorWalkFamily>("color_walk_kernel", 0, mode, ix, i1 - i0, kLocateWaves, num_cus, stream, info, loc, c, i1 - i0,
+                                               (DevStats *)nullptr);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         seconds[0] += seconds_since(tw);
         auto ts = std::chrono::steady_clock::now();

@@ -9,19 +9,23 @@
 // (it stops at BWT position 0, whose sample is n - 1): t = entry mod n, and no other shift is needed.
 //
 // Four steps on the caller's stream:
-//   hits_interval_kernel   the searches.  Blocks of one wavefront; a lane owns the items lane, lane + stride, ... (locate_kernel's
-//                          lists, movi_walk_sa.hip) and takes up its next item in the iteration after a search ends, because item
-//                          lengths differ widely.  search_step (movi_search.hpp) over P[end - 1] down to P[start] with
-//                          lim = end - start, so the interval table serves the first K bases.  Stores per item the interval's two
-//                          packed ends and the BWT position of its start (HitsInterval, in the caller's work area), occ, and
-//                          listed = min(occ, max_occ) for the scan;
+//   hits_interval_kernel   the searches.  Blocks of one wavefront; a lane owns the items lane, lane + stride, ... and takes up its
+//                          next item in the iteration after a search ends, because item lengths differ widely: search_lists
+//                          (movi_search.hpp) over P[end - 1] down to P[start] with lim = end - start, so the interval table serves
+//                          the first K bases.  Stores per item the interval's two packed ends and the BWT position of its start
+//                          (HitsInterval, in the caller's work area), occ (interval_count), and listed = min(occ, max_occ) for
+//                          the scan;
 //   the scan               hipcub::DeviceScan::ExclusiveSum over the n_items + 1 values of `listed` (the last one 0) into d_first,
 //                          64-bit values, its temporary storage from the work area.  n_items + 1 < 2^31: one 32-bit-indexed scan;
 //   hits_expand_kernel     slot j < min(total, cap): its item by an upper bound over d_first, its BWT position = the interval's start
 //                          + (j - first[item]), its row from the item's first row and the 32-row checkpoints, then
 //                          pos_pack(row, offset).  Neighbouring lanes hold neighbouring slots: the stores are coalesced;
-//   hits_walk_kernel       the locate walks in place on those slots -- locate_kernel's loop over loc_lf_step (movi_sa.hpp), with the
-//                          slot count read on the device -- and entry -> t = entry mod n; kPosNone stays.
+//   hits_walk_kernel       the locate walks in place on those slots: locate_walk (movi_sa.hpp), the loop locate_kernel
+//                          (movi_walk_sa.hip) runs, with two differences.  The number of slots is min(d_first[n_items], cap), read
+//                          on the device -- locate_kernel takes its count from the host, which does not know the total without
+//                          waiting for the stream, and a launch over the caller's whole cap would walk, and overwrite, slots past
+//                          the total.  And the entry is stored as a text position, t = entry mod n; a sample that does not give
+//                          one (a corrupt array) becomes kPosNone and is counted in DevStats::errors.  kPosNone stays.
 // The grids of the last two are sized from positions_cap and the kernels read the total from d_first[n_items]: nothing comes back
 // to the host, so the call can be captured, and no slot at or past min(total, cap) is read or written.
 // (Named into the movi_walk*.hip family: the sanitizer build of tests/fuzz/fuzz_parse.sh compiles the library from that glob.)
@@ -38,91 +42,49 @@ struct HitsInterval {
 };
 static_assert(sizeof(HitsInterval) == kHitsIntervalBytes, "HitsInterval and hits_work_layout differ");
 
-// IdxT: the type the lane's interval rows are kept in between iterations (uint32_t when DevIndex::idx32).
+// search_lists over the items: a bad item (outside its read, or empty) is answered in `take`; a search that ends on the whole of X
+// stores the interval and its size, interval_count.  A corrupt table never yields a count beyond the text.
 template <int MODE, typename IdxT>
 __global__ __launch_bounds__(64) void hits_interval_kernel(DevIndex ix, const uint8_t *__restrict__ bases, const uint64_t *__restrict__ offs,
                                                            uint64_t n_reads, const HitsItem *__restrict__ items, uint64_t n_items,
                                                            uint32_t max_occ, uint64_t n_text, HitsInterval *__restrict__ iv, uint64_t *__restrict__ occ,
                                                            uint64_t *__restrict__ listed, uint8_t *__restrict__ item_err, DevStats *stats) {
-    __shared__ uint8_t s_code[256];
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) s_code[i] = ix.code_of[i];
-    __syncthreads();
-    const uint64_t stride = (uint64_t)gridDim.x * 64u;
-    uint64_t g = (uint64_t)blockIdx.x * 64u + threadIdx.x;
-    if (g == 0) listed[n_items] = 0;                      // the scan's last input: d_first[n_items] = the total
-    uint32_t state = g < n_items ? 1u : 0u;               // 0 = list done, 1 = take up item g, 2 = searching
-    uint32_t l = 0, lim = 0;                              // bases of X taken (the interval is non-empty after each), |X|
-    uint64_t last = 0;                                    // index of X's last base in `bases`
-    uint32_t ff_total = 0, scan_total = 0, errs = 0;
-    uint64_t lane_steps = 0, wave_steps = 0;
-    IdxT krs = 0, kre = 0;
-    uint32_t os = 0, oe = 0;
-    uint2 rws = make_uint2(0, 0), rwe = make_uint2(0, 0);
-    while (wave_any(state != 0u)) {
-        wave_steps += 1;
-        if (state == 1u) {                                // the lane's next item
+    if (blockIdx.x == 0 && threadIdx.x == 0) listed[n_items] = 0;      // the scan's last input: d_first[n_items] = the total
+    search_lists<MODE, IdxT>(ix, n_items, stats,
+        [&](uint64_t g, const uint8_t *&last, uint32_t &lim) {
             const HitsItem it = items[g];
             bool ok = it.read < n_reads && it.start < it.end;
             if (ok) {
                 const uint64_t beg = offs[it.read], fin = offs[(uint64_t)it.read + 1];
                 ok = fin >= beg && it.end <= fin - beg;   // (no base outside the read is read)
-                last = beg + it.end - 1u;
+                last = bases + (beg + it.end - 1u);
+                lim = it.end - it.start;
             }
-            if (ok) { l = 0; lim = it.end - it.start; state = 2u; }
-            else {                                        // a bad item
+            if (!ok) {                                    // a bad item
                 occ[g] = 0; listed[g] = 0;
                 if (item_err) item_err[g] = 0xFFu;
-                g += stride;
-                state = g < n_items ? 1u : 0u;
             }
-        }
-        const bool live = state == 2u;                    // (a lane that took up an item above steps in this same iteration)
-        lane_steps += live ? 1u : 0u;
-        // ---- one step leftwards on X's next base: bases[last - l - i], i < lim - l
-        uint64_t rs = krs, re = kre;
-        const uint8_t *R = bases + (live ? last - l : 0u);
-        auto base_at = [&](uint32_t i) { return (uint32_t)s_code[*(R - i)]; };
-        auto keep = [](uint64_t, uint64_t, uint32_t, uint32_t) {};
-        const SearchStep st = search_step<MODE>(ix, live, lim, l, base_at, keep, rs, os, rws, re, oe, rwe, ff_total, scan_total);
-        krs = (IdxT)rs; kre = (IdxT)re;
-        if (live && (st.err != 0u || st.taken == 0u || l == lim)) {
+            return ok;
+        },
+        [&](uint64_t g, const SearchStep &st, uint64_t rs, uint32_t os, uint2 rws, uint64_t re, uint32_t oe) {
             uint64_t v = 0;
             uint32_t code = st.err;
             HitsInterval h{0, 0, 0};
-            if (!code && st.taken != 0u) {                // MoveInterval::count (include/move_intervals.hpp:47-58), from the checkpoints
+            if (!code && st.taken != 0u) {
                 if (rs >= ix.r || re >= ix.r || rs > re) code = kErrIdRange;
                 else {
-                    const uint64_t p0 = row_start<MODE>(ix, rs) + os, p1 = row_start<MODE>(ix, re) + oe;
-                    if (p1 < p0 || p1 >= n_text) code = kErrIdRange;     // (a corrupt table: never a count beyond the text)
-                    else {
-                        v = p1 - p0 + 1;
-                        h.s_pack = pos_pack(rs, os); h.e_pack = pos_pack(re, oe); h.p0 = p0;
-                    }
+                    const uint64_t p0 = row_start<MODE>(ix, rs) + os;
+                    v = interval_count<MODE>(ix, rs, os, rws, re, oe);
+                    if (p0 >= n_text || v - 1 >= n_text - p0) { code = kErrIdRange; v = 0; }
+                    else { h.s_pack = pos_pack(rs, os); h.e_pack = pos_pack(re, oe); h.p0 = p0; }
                 }
             }
-            if (code) errs += 1;
             iv[g] = h;
             occ[g] = v;
             listed[g] = v < (uint64_t)max_occ ? v : (uint64_t)max_occ;
             if (item_err) item_err[g] = (uint8_t)code;
-            g += stride;
-            state = g < n_items ? 1u : 0u;
-        }
-    }
-    const uint32_t scw = wave_sum(scan_total), erw = wave_sum(errs);
-    unsigned long long ffw = ff_total, lsw = lane_steps;    // summed in 64 bits: a lane's list holds many searches
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        ffw += __shfl_xor(ffw, s, 64);
-        lsw += __shfl_xor(lsw, s, 64);
-    }
-    if ((threadIdx.x & 63) == 0 && stats) {
-        if (ffw) atomicAdd(&stats->fast_forwards, ffw);
-        if (scw) atomicAdd(&stats->scans, (unsigned long long)scw);
-        if (erw) atomicAdd(&stats->errors, (unsigned long long)erw);
-        atomicAdd(&stats->lane_steps, lsw);
-        atomicAdd(&stats->wave_steps, (unsigned long long)wave_steps);
-    }
+            return code == 0u;
+        });
 }
 
 // Slot j of the position list -> the packed position of its BWT position.  A grid-stride loop over [0, min(total, cap)).
@@ -169,89 +131,33 @@ __global__ __launch_bounds__(256) void hits_expand_kernel(DevIndex ix, const Hit
     if (errs && stats) atomicAdd(&stats->errors, (unsigned long long)errs);
 }
 
-// The locate walks of slots [0, min(total, cap)), in place, and the way back to text coordinates.  KEEP IN STEP WITH locate_kernel
-// (movi_walk_sa.hip), whose state machine this restates: a change to one of the two loops belongs in the other.  This is locate_kernel's loop
-// (movi_walk_sa.hip: a lane owns the slots lane, lane + stride, ... and takes up its next slot when a walk ends; loc_lf_step on the
-// locate rows) with two differences.  The number of slots is read from d_first[n_items] on the device -- locate_kernel takes it from the
-// host, which does not know the total without waiting for the stream, and a launch over the caller's whole cap would walk, and
-// overwrite, slots past the total.  And the entry is stored as a text position: get_SA_entries' "+ n" of the walks that passed text
-// position 0 is taken back.  A slot that is kPosNone stays; one whose walk breaks an invariant of the table becomes kPosNone and is
-// counted in DevStats::errors.
+// locate_walk (movi_sa.hpp) in place on the slots [0, min(total, cap)): see the head of this file for what differs from locate_kernel.
 template <int MODE, typename IdxT>
 __global__ __launch_bounds__(64) void hits_walk_kernel(DevIndex ix, LocArgs a, const uint64_t *__restrict__ first, uint64_t n_first,
                                                        uint64_t cap, uint64_t *__restrict__ pos, DevStats *stats) {
-    const uint64_t total = first[n_first], n_items = total < cap ? total : cap;
-    const uint64_t stride = (uint64_t)gridDim.x * 64u;
-    uint64_t item = (uint64_t)blockIdx.x * 64u + threadIdx.x;
-    uint32_t state = item < n_items ? 1u : 0u;            // 0 = list done, 1 = take up `item`, 2 = walking
-    IdxT kidx = 0;
-    uint32_t off = 0, ff_total = 0, errs = 0;
-    uint64_t dist = 0, lane_steps = 0, wave_steps = 0;
-    uint4 v = make_uint4(0, 0, 0, 0);
-    const uint32_t rate = a.rate;
-    while (wave_any(state != 0u)) {
-        wave_steps += 1;
-        if (state == 1u) {                                // the lane's next slot
-            const uint64_t p = pos[item];
-            const uint64_t row = p >> kPosOffBits;
-            if (p != kPosNone && row < ix.r) {
-                kidx = (IdxT)row;
-                off = (uint32_t)p & ((1u << kPosOffBits) - 1u);
-                v = loc_load(a.rows, row);
-                dist = 0;
-                state = 2u;
-            } else {
-                if (p != kPosNone) { errs += 1; pos[item] = kPosNone; }
-                item += stride;
-                state = item < n_items ? 1u : 0u;
-            }
-        }
-        uint32_t t = 0;
-        bool hit = false;
-        if (state == 2u) {
-            t = loc_rem(v) + off;                         // < 2^24 + 2^12
-            hit = t % rate == 0u;
-        }
-        if (hit) {
-            const uint64_t s = loc_quot(v) + t / rate;
+    const uint64_t total = first[n_first];
+    a.succ = 0u;                                          // (no successor mode here)
+    locate_walk<MODE, IdxT>(ix, a, pos, total < cap ? total : cap, stats,
+        [&](uint64_t item, uint64_t s, uint64_t dist) {
             uint64_t e = kPosNone;
             if (s < a.n_entries) {
                 e = a.samples[s] + dist;                  // get_SA_entries: SA[p], or SA[p] + n
                 if (e >= a.n) e -= a.n;
                 if (e >= a.n) e = kPosNone;               // (a corrupt sample)
             }
-            if (e == kPosNone) errs += 1;
             pos[item] = e;
-            item += stride;
-            state = item < n_items ? 1u : 0u;
-        }
-        const bool walk = state == 2u;                    // (a lane that took up a slot above steps in this same iteration)
-        uint64_t idx = kidx;
-        const uint32_t err = loc_lf_step<MODE>(a.rows, ix.r, walk, idx, off, v, ff_total, [&]() {
-            lane_steps += walk ? 1u : 0u;
-            dist += walk ? 1u : 0u;
-        });
-        kidx = (IdxT)idx;
-        if (walk && (err != 0u || dist > a.n)) {          // a corrupt table: an error, not a hang
-            errs += 1;
-            pos[item] = kPosNone;
-            item += stride;
-            state = item < n_items ? 1u : 0u;
-        }
-    }
-    flush_lane_stats_sa(stats, ff_total, errs, lane_steps, wave_steps);
+            return e != kPosNone;
+        },
+        [&](uint64_t item) { pos[item] = kPosNone; });
 }
 
 namespace {
-
-template <int MODE, typename IdxT>
-void launch_interval_t(unsigned blocks, hipStream_t stream, const DevIndex &ix, const uint8_t *d_bases, const uint64_t *d_offsets, uint64_t n_reads,
-                       const HitsItem *d_items, uint64_t n_items, uint32_t max_occ, uint64_t n_text, HitsInterval *d_iv, uint64_t *d_occ,
-                       uint64_t *d_listed, uint8_t *d_item_err, DevStats *d_stats) {
-    hipLaunchKernelGGL((hits_interval_kernel<MODE, IdxT>), dim3(blocks), dim3(64), 0, stream, ix, d_bases, d_offsets, n_reads, d_items, n_items,
-                       max_occ, n_text, d_iv, d_occ, d_listed, d_item_err, d_stats);
-}
-
+struct HitsIntervalFamily {
+    template <int MODE, typename IdxT> static auto kernel() { return &hits_interval_kernel<MODE, IdxT>; }
+};
+struct HitsWalkFamily {
+    template <int MODE, typename IdxT> static auto kernel() { return &hits_walk_kernel<MODE, IdxT>; }
+};
 }  // namespace
 
 hipError_t launch_locate_matches(int mode, const DevIndex &ix, const LocArgs &loc, const uint8_t *d_bases, const uint64_t *d_offsets,
@@ -265,49 +171,24 @@ hipError_t launch_locate_matches(int mode, const DevIndex &ix, const LocArgs &lo
     uint64_t *d_listed = reinterpret_cast<uint64_t *>(static_cast<uint8_t *>(d_work) + w.listed);
     void *d_temp = static_cast<uint8_t *>(d_work) + w.scan_temp;
     if (n_items == 0) return hipMemsetAsync(d_first, 0, 8, stream);      // d_first[0] = the total = 0
-    const unsigned cus = (unsigned)(num_cus > 0 ? num_cus : 256);
-    char nm[96];
-    snprintf(nm, sizeof(nm), "hits_interval_kernel<%d, %s>", mode, ix.idx32 ? "unsigned int" : "unsigned long");
-    note_walk_launch(nm);
-    {
-        // one-wavefront blocks; at most kHitsWaves per CU, so that a lane's list holds many items wherever there are many
-        const uint64_t want = (n_items + 63) / 64, cap = (uint64_t)cus * kHitsWaves;
-        const unsigned blocks = (unsigned)(want < cap ? want : cap);
-        if (mode == 6) {
-            if (ix.idx32) launch_interval_t<6, uint32_t>(blocks, stream, ix, d_bases, d_offsets, n_reads, d_items, n_items, max_occ, loc.n, d_iv, d_occ, d_listed, d_item_err, d_stats);
-            else launch_interval_t<6, uint64_t>(blocks, stream, ix, d_bases, d_offsets, n_reads, d_items, n_items, max_occ, loc.n, d_iv, d_occ, d_listed, d_item_err, d_stats);
-        } else {
-            if (ix.idx32) launch_interval_t<3, uint32_t>(blocks, stream, ix, d_bases, d_offsets, n_reads, d_items, n_items, max_occ, loc.n, d_iv, d_occ, d_listed, d_item_err, d_stats);
-            else launch_interval_t<3, uint64_t>(blocks, stream, ix, d_bases, d_offsets, n_reads, d_items, n_items, max_occ, loc.n, d_iv, d_occ, d_listed, d_item_err, d_stats);
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    {
-        size_t need = 0;
-        hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_listed, d_first, (int)(n_items + 1), stream);
-        if (e != hipSuccess) return e;
-        if (need > w.total - w.scan_temp) return hipErrorInvalidValue;   // (hits_work_layout's room for it is an upper bound: never met)
-        size_t have = (size_t)(w.total - w.scan_temp);
-        e = hipcub::DeviceScan::ExclusiveSum(d_temp, have, d_listed, d_first, (int)(n_items + 1), stream);
-        if (e != hipSuccess) return e;
-    }
-    if (positions_cap == 0 || stages < 2) {
-        if (info) {
-            *info = LaunchInfo();
-            snprintf(info->kernel, sizeof(info->kernel), "%s", nm);
-            info->variant = 0; info->block_threads = 64; info->idx64 = ix.idx32 ? 0 : 1; info->waves_per_cu = kHitsWaves;
-        }
-        return hipSuccess;
-    }
+    hipError_t e = launch_lane_lists<HitsIntervalFamily>("hits_interval_kernel", 0, mode, ix, n_items, kHitsWaves, num_cus, stream, info, d_bases,
+                                                         d_offsets, n_reads, d_items, n_items, max_occ, loc.n, d_iv, d_occ, d_listed, d_item_err,
+                                                         d_stats);
+    if (e != hipSuccess) return e;
+    size_t need = 0, have = (size_t)(w.total - w.scan_temp);
+    e = hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_listed, d_first, (int)(n_items + 1), stream);
+    if (e == hipSuccess && need > have) e = hipErrorInvalidValue;            // (hits_work_layout's room for it is an upper bound: never met)
+    if (e == hipSuccess) e = hipcub::DeviceScan::ExclusiveSum(d_temp, have, d_listed, d_first, (int)(n_items + 1), stream);
+    if (e != hipSuccess || positions_cap == 0 || stages < 2) return e;       // (info: the interval kernel's)
     // the total stays on the device: the grids come from the cap, the kernels stop at min(total, cap)
-    const uint64_t want = (positions_cap + 255) / 256, gcap = (uint64_t)cus * 8u;
+    const uint64_t want = (positions_cap + 255) / 256, gcap = (uint64_t)(num_cus > 0 ? num_cus : 256) * 8u;
     const unsigned blocks = (unsigned)(want < gcap ? want : gcap);
+    char nm[96];
     snprintf(nm, sizeof(nm), "hits_expand_kernel<%d>", mode);
     note_walk_launch(nm);
     if (mode == 6) hipLaunchKernelGGL(hits_expand_kernel<6>, dim3(blocks), dim3(256), 0, stream, ix, d_iv, d_first, n_items, positions_cap, d_positions, d_stats);
     else hipLaunchKernelGGL(hits_expand_kernel<3>, dim3(blocks), dim3(256), 0, stream, ix, d_iv, d_first, n_items, positions_cap, d_positions, d_stats);
-    hipError_t e = hipGetLastError();
+    e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (stages < 3) {
         if (info) {
@@ -318,37 +199,16 @@ hipError_t launch_locate_matches(int mode, const DevIndex &ix, const LocArgs &lo
         return hipSuccess;
     }
     if (loc.rate == 0u || !loc.rows || !loc.samples) return hipErrorInvalidValue;
-    {
-        // one-wavefront blocks; at most kLocateWaves per CU, as launch_locate
-        const uint64_t wwant = (positions_cap + 63) / 64, wcap = (uint64_t)cus * kLocateWaves;
-        const unsigned wblocks = (unsigned)(wwant < wcap ? wwant : wcap);
-        snprintf(nm, sizeof(nm), "hits_walk_kernel<%d, %s>", mode, ix.idx32 ? "unsigned int" : "unsigned long");
-        note_walk_launch(nm);
-        if (info) {
-            *info = LaunchInfo();
-            snprintf(info->kernel, sizeof(info->kernel), "%s", nm);
-            info->variant = 0; info->block_threads = 64; info->idx64 = ix.idx32 ? 0 : 1; info->waves_per_cu = kLocateWaves;
-        }
-        if (mode == 6) {
-            if (ix.idx32) hipLaunchKernelGGL((hits_walk_kernel<6, uint32_t>), dim3(wblocks), dim3(64), 0, stream, ix, loc, d_first, n_items, positions_cap, d_positions, d_stats);
-            else hipLaunchKernelGGL((hits_walk_kernel<6, uint64_t>), dim3(wblocks), dim3(64), 0, stream, ix, loc, d_first, n_items, positions_cap, d_positions, d_stats);
-        } else {
-            if (ix.idx32) hipLaunchKernelGGL((hits_walk_kernel<3, uint32_t>), dim3(wblocks), dim3(64), 0, stream, ix, loc, d_first, n_items, positions_cap, d_positions, d_stats);
-            else hipLaunchKernelGGL((hits_walk_kernel<3, uint64_t>), dim3(wblocks), dim3(64), 0, stream, ix, loc, d_first, n_items, positions_cap, d_positions, d_stats);
-        }
-    }
-    return hipGetLastError();
+    // as launch_locate, over the cap
+    return launch_lane_lists<HitsWalkFamily>("hits_walk_kernel", 0, mode, ix, positions_cap, kLocateWaves, num_cus, stream, info, loc, d_first,
+                                             n_items, positions_cap, d_positions, d_stats);
 }
 
 hipError_t preload_hits(int mode, bool idx32) {
     hipFuncAttributes at;
-    const void *f = mode == 6 ? (idx32 ? (const void *)hits_interval_kernel<6, uint32_t> : (const void *)hits_interval_kernel<6, uint64_t>)
-                              : (idx32 ? (const void *)hits_interval_kernel<3, uint32_t> : (const void *)hits_interval_kernel<3, uint64_t>);
-    hipError_t e = hipFuncGetAttributes(&at, f);
+    hipError_t e = preload_family<HitsIntervalFamily>(mode, idx32);
     if (e == hipSuccess) e = hipFuncGetAttributes(&at, mode == 6 ? (const void *)hits_expand_kernel<6> : (const void *)hits_expand_kernel<3>);
-    if (e == hipSuccess)
-        e = hipFuncGetAttributes(&at, mode == 6 ? (idx32 ? (const void *)hits_walk_kernel<6, uint32_t> : (const void *)hits_walk_kernel<6, uint64_t>)
-                                                : (idx32 ? (const void *)hits_walk_kernel<3, uint32_t> : (const void *)hits_walk_kernel<3, uint64_t>));
+    if (e == hipSuccess) e = preload_family<HitsWalkFamily>(mode, idx32);
     return e;
 }
 

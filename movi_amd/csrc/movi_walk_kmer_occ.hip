@@ -6,12 +6,12 @@
 //   kmer_occ_mark_kernel     one lane per read: a *pending mark* (kOccPending) into the slot of every k-mer whose k bases are legal,
 //                            0 into the read's other slots (a k-mer with an illegal base, the last k - 1 slots);
 //   kmer_occ_kernel          the searches.  Blocks of one wavefront; a lane owns the slots lane, lane + stride, ... of all n_bases slots
-//                            (locate_kernel's lists, movi_walk_sa.hip) and takes up its next slot in the iteration after a search
-//                            ends, so the wavefronts stay full although a search that dies early is over in one step and a found
-//                            k-mer takes 1 + (k - K) of them.  A slot that holds no mark costs one iteration; a marked slot g is a
-//                            backward search over bases[g + k - 1] down to bases[g]: search_step (movi_search.hpp) with lim = k --
-//                            the interval table's lookup first where K <= k --, which ends dead (0) or at l == k (the interval's
-//                            count, MoveInterval::count).  No read ids anywhere: the marks carry everything;
+//                            and takes up its next slot in the iteration after a search ends (search_lists, movi_search.hpp), so
+//                            the wavefronts stay full although a search that dies early is over in one step and a found k-mer
+//                            takes 1 + (k - K) of them.  A slot that holds no mark costs one iteration; a marked slot g is a
+//                            backward search over bases[g + k - 1] down to bases[g] with lim = k -- the interval table's lookup
+//                            first where K <= k --, which ends dead (0) or at l == k (the interval's count, interval_count).  No
+//                            read ids anywhere: the marks carry everything;
 //   kmer_occ_reduce_kernel   one wavefront per read: found, sum and the error code from the read's slots.
 // A k-mer whose search hits one of the reference's LF throws becomes an error slot (kOccErr | code; MOVI_OCC_IS_ERROR).
 // (Named into the movi_walk*.hip family: the sanitizer build of tests/fuzz/fuzz_parse.sh compiles the library from that glob.)
@@ -50,67 +50,24 @@ __global__ __launch_bounds__(64) void kmer_occ_mark_kernel(DevIndex ix, uint32_t
 
 }  // namespace
 
-// IdxT: the type the lane's interval rows are kept in between iterations (uint32_t when DevIndex::idx32).
 template <int MODE, typename IdxT>
 __global__ __launch_bounds__(64) void kmer_occ_kernel(DevIndex ix, uint32_t k, const uint8_t *__restrict__ bases, uint64_t n_slots,
                                                       uint64_t *__restrict__ occ, DevStats *stats) {
-    __shared__ uint8_t s_code[256];
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) s_code[i] = ix.code_of[i];
-    __syncthreads();
-    const uint64_t stride = (uint64_t)gridDim.x * 64u;
-    uint64_t g = (uint64_t)blockIdx.x * 64u + threadIdx.x;
-    uint32_t state = g < n_slots ? 1u : 0u;               // 0 = list done, 1 = take up slot g, 2 = searching
-    uint32_t l = 0;                                       // bases of the k-mer taken (the interval is non-empty after each)
-    uint32_t ff_total = 0, scan_total = 0, errs = 0;
-    uint64_t lane_steps = 0, wave_steps = 0;
-    IdxT krs = 0, kre = 0;
-    uint32_t os = 0, oe = 0;
-    uint2 rws = make_uint2(0, 0), rwe = make_uint2(0, 0);
-    while (wave_any(state != 0u)) {
-        wave_steps += 1;
-        if (state == 1u) {                                // the lane's next slot
+    search_lists<MODE, IdxT>(ix, n_slots, stats,
+        [&](uint64_t g, const uint8_t *&last, uint32_t &lim) {
             // (a mark outside [0, n_slots - k] is none of the mark kernel's: never searched, so no base outside the batch is read)
-            if (occ[g] == kOccPending && k <= n_slots && g <= n_slots - k) { l = 0; state = 2u; }
-            else { g += stride; state = g < n_slots ? 1u : 0u; }
-        }
-        const bool live = state == 2u;                    // (a lane that took up a slot above steps in this same iteration)
-        lane_steps += live ? 1u : 0u;
-        // ---- one step leftwards on the k-mer's next base: bases[g + k - 1 - l - i], i < k - l
-        uint64_t rs = krs, re = kre;
-        const uint8_t *R = bases + g + (k - 1u - l);
-        auto base_at = [&](uint32_t i) { return (uint32_t)s_code[*(R - i)]; };
-        auto keep = [](uint64_t, uint64_t, uint32_t, uint32_t) {};
-        const SearchStep st = search_step<MODE>(ix, live, k, l, base_at, keep, rs, os, rws, re, oe, rwe, ff_total, scan_total);
-        krs = (IdxT)rs; kre = (IdxT)re;
-        if (live && (st.err != 0u || st.taken == 0u || l == k)) {
+            if (!(occ[g] == kOccPending && k <= n_slots && g <= n_slots - k)) return false;
+            last = bases + g + (k - 1u);
+            lim = k;
+            return true;
+        },
+        [&](uint64_t g, const SearchStep &st, uint64_t rs, uint32_t os, uint2 rws, uint64_t re, uint32_t oe) {
             uint64_t v = 0;
-            if (st.err) { v = kOccErr | st.err; errs += 1; }
-            else if (st.taken != 0u) {                    // MoveInterval::count (include/move_intervals.hpp:47-58)
-                if (rs == re) v = (uint64_t)oe - os + 1;
-                else if (re - rs < (1ull << kPrefixShift)) {          // inside a checkpoint block's reach: the rows between the ends
-                    v = (uint64_t)row_n<MODE>(rws) - os + oe + 1;
-                    for (uint64_t j = rs + 1; j < re; ++j) v += row_n<MODE>(load_row<MODE>(ix.rows, j));
-                } else v = (row_start<MODE>(ix, re) + oe) - (row_start<MODE>(ix, rs) + os) + 1;
-            }
+            if (st.err) v = kOccErr | st.err;
+            else if (st.taken != 0u) v = interval_count<MODE>(ix, rs, os, rws, re, oe);
             occ[g] = v;
-            g += stride;
-            state = g < n_slots ? 1u : 0u;
-        }
-    }
-    const uint32_t scw = wave_sum(scan_total), erw = wave_sum(errs);
-    unsigned long long ffw = ff_total, lsw = lane_steps;    // summed in 64 bits: a lane's list holds many searches
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        ffw += __shfl_xor(ffw, s, 64);
-        lsw += __shfl_xor(lsw, s, 64);
-    }
-    if ((threadIdx.x & 63) == 0 && stats) {
-        if (ffw) atomicAdd(&stats->fast_forwards, ffw);
-        if (scw) atomicAdd(&stats->scans, (unsigned long long)scw);
-        if (erw) atomicAdd(&stats->errors, (unsigned long long)erw);
-        atomicAdd(&stats->lane_steps, lsw);
-        atomicAdd(&stats->wave_steps, (unsigned long long)wave_steps);
-    }
+            return st.err == 0u;
+        });
 }
 
 namespace {
@@ -148,11 +105,9 @@ __global__ __launch_bounds__(256) void kmer_occ_reduce_kernel(const uint64_t *__
     if (err) err[rid] = (uint8_t)code;
 }
 
-template <int MODE, typename IdxT>
-void launch_occ_t(unsigned blocks, hipStream_t stream, const DevIndex &ix, uint32_t k, const uint8_t *d_bases, uint64_t n_slots,
-                  uint64_t *d_occ, DevStats *d_stats) {
-    hipLaunchKernelGGL((kmer_occ_kernel<MODE, IdxT>), dim3(blocks), dim3(64), 0, stream, ix, k, d_bases, n_slots, d_occ, d_stats);
-}
+struct KmerOccFamily {
+    template <int MODE, typename IdxT> static auto kernel() { return &kmer_occ_kernel<MODE, IdxT>; }
+};
 
 }  // namespace
 
@@ -162,33 +117,15 @@ hipError_t launch_kmer_occ(int mode, const DevIndex &ix, uint32_t k, const uint8
     if (n_reads == 0) return hipSuccess;
     if ((mode != 6 && mode != 3) || k == 0u) return hipErrorInvalidValue;
     if ((n_reads + 63) / 64 > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    char nm[96];
-    snprintf(nm, sizeof(nm), "kmer_occ_kernel<%d, %s>", mode, ix.idx32 ? "unsigned int" : "unsigned long");
-    note_walk_launch(nm);
-    if (info) {
-        *info = LaunchInfo();
-        snprintf(info->kernel, sizeof(info->kernel), "%s", nm);
-        info->variant = 0; info->block_threads = 64; info->idx64 = ix.idx32 ? 0 : 1;
-        info->waves_per_cu = kKmerOccWaves;
-    }
     if (n_bases != 0) {
         hipLaunchKernelGGL(kmer_occ_mark_kernel, dim3((unsigned)((n_reads + 63) / 64)), dim3(64), 0, stream, ix, k, d_bases, d_offsets, n_reads,
                            n_bases, d_occ);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        // one-wavefront blocks; at most kKmerOccWaves per CU, so that a lane's list holds many k-mers wherever there are many
-        const uint64_t want = (n_bases + 63) / 64, cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * kKmerOccWaves;
-        const unsigned blocks = (unsigned)(want < cap ? want : cap);
-        if (mode == 6) {
-            if (ix.idx32) launch_occ_t<6, uint32_t>(blocks, stream, ix, k, d_bases, n_bases, d_occ, d_stats);
-            else launch_occ_t<6, uint64_t>(blocks, stream, ix, k, d_bases, n_bases, d_occ, d_stats);
-        } else {
-            if (ix.idx32) launch_occ_t<3, uint32_t>(blocks, stream, ix, k, d_bases, n_bases, d_occ, d_stats);
-            else launch_occ_t<3, uint64_t>(blocks, stream, ix, k, d_bases, n_bases, d_occ, d_stats);
-        }
-        e = hipGetLastError();
-        if (e != hipSuccess) return e;
     }
+    hipError_t e = launch_lane_lists<KmerOccFamily>("kmer_occ_kernel", 0, mode, ix, n_bases, kKmerOccWaves, num_cus, stream, info, k, d_bases,
+                                                    n_bases, d_occ, d_stats);
+    if (e != hipSuccess) return e;
     if (d_found || d_sum || d_err) {
         hipLaunchKernelGGL(kmer_occ_reduce_kernel, dim3((unsigned)((n_reads + 3) / 4)), dim3(256), 0, stream, d_occ, d_offsets, n_reads, n_bases,
                            d_found, d_sum, d_err);
@@ -197,11 +134,6 @@ hipError_t launch_kmer_occ(int mode, const DevIndex &ix, uint32_t k, const uint8
     return hipSuccess;
 }
 
-hipError_t preload_kmer_occ(int mode, bool idx32) {
-    hipFuncAttributes at;
-    const void *f = mode == 6 ? (idx32 ? (const void *)kmer_occ_kernel<6, uint32_t> : (const void *)kmer_occ_kernel<6, uint64_t>)
-                              : (idx32 ? (const void *)kmer_occ_kernel<3, uint32_t> : (const void *)kmer_occ_kernel<3, uint64_t>);
-    return hipFuncGetAttributes(&at, f);
-}
+hipError_t preload_kmer_occ(int mode, bool idx32) { return preload_family<KmerOccFamily>(mode, idx32); }
 
 }  // namespace movi

@@ -9,6 +9,7 @@
 // The contract is stated in include/movi_hip.h (movi_locate_device, movi_sa_entries_device, movi_ssa_build); the locate rows and the
 // packed positions in movi_sa.hpp.
 // (Named into the movi_walk*.hip family: the sanitizer build of tests/fuzz/fuzz_parse.sh compiles the library from that glob.)
+#include "movi_search.hpp"
 #include "movi_sa.hpp"
 
 #include <hipcub/hipcub.hpp>
@@ -16,106 +17,39 @@
 namespace movi {
 
 // ------------------------------------------------------------------------------------------------ locate
-// Walk lengths are roughly geometric with mean `rate`, so a lane per item would leave most lanes of a wavefront idle behind its
-// longest walk.  Here a lane owns the items lane, lane + stride, ... (stride = the launch's lanes) and takes up its next item in the
-// iteration after a walk ends: no cross-lane traffic, and all lanes stay busy until the lists run out.  Every iteration of a lane is
-// one dependent gather: a 16-byte locate row.
+// locate_walk (movi_sa.hpp) over the n_items positions of `pos`, the count known to the host.
 //   a.succ == 0   pos[item] = samples[s] + distance, NOT reduced modulo n: a walk that passes text position 0 stops at BWT position 0
 //                 (sample 0 = n - 1) and returns entry + n, as the reference does;
-//   a.succ == 1   one LF step first; pos[item] = s, a.aux[item] = distance.
-// (hits_walk_kernel, movi_walk_hits.hip, restates this loop with the item count read on the device: keep the two in step.)
+//   a.succ == 1   one LF step first; pos[item] = s, a.aux[item] = distance (0 where the walk failed).
 // An item that is kPosNone stays; one that is not a position of the table, or whose walk breaks an invariant of the table (the
 // reference's throws; more than n steps), becomes kPosNone and is counted in DevStats::errors.
 template <int MODE, typename IdxT>
 __global__ __launch_bounds__(64) void locate_kernel(DevIndex ix, LocArgs a, uint64_t *__restrict__ pos, uint64_t n_items, DevStats *stats) {
-    const uint64_t stride = (uint64_t)gridDim.x * 64u;
-    uint64_t item = (uint64_t)blockIdx.x * 64u + threadIdx.x;
-    uint32_t state = item < n_items ? 1u : 0u;            // 0 = list done, 1 = take up `item`, 2 = walking
-    IdxT kidx = 0;
-    uint32_t off = 0, ff_total = 0, errs = 0;
-    uint64_t dist = 0, lane_steps = 0, wave_steps = 0;      // (64 bits: a rate above n on a large table makes walks of n steps)
-    uint4 v = make_uint4(0, 0, 0, 0);
-    const uint32_t rate = a.rate;
-    while (wave_any(state != 0u)) {
-        wave_steps += 1;
-        if (state == 1u) {                                // the lane's next item
-            const uint64_t p = pos[item];
-            const uint64_t row = p >> kPosOffBits;
-            if (p != kPosNone && row < ix.r) {
-                kidx = (IdxT)row;
-                off = (uint32_t)p & ((1u << kPosOffBits) - 1u);
-                v = loc_load(a.rows, row);
-                dist = 0;
-                state = 2u;
-            } else {
-                if (p != kPosNone) { errs += 1; pos[item] = kPosNone; }
-                item += stride;
-                state = item < n_items ? 1u : 0u;
-            }
-        }
-        uint32_t t = 0;
-        bool hit = false;
-        if (state == 2u) {
-            t = loc_rem(v) + off;                         // < 2^24 + 2^12
-            hit = (t % rate == 0u) && !(a.succ != 0u && dist == 0);
-        }
-        if (hit) {
-            const uint64_t s = loc_quot(v) + t / rate;
-            if (s >= a.n_entries) { errs += 1; pos[item] = kPosNone; }
-            else if (a.succ) { pos[item] = s; a.aux[item] = dist; }
+    locate_walk<MODE, IdxT>(ix, a, pos, n_items, stats,
+        [&](uint64_t item, uint64_t s, uint64_t dist) {
+            if (s >= a.n_entries) { pos[item] = kPosNone; return false; }
+            if (a.succ) { pos[item] = s; a.aux[item] = dist; }
             else pos[item] = a.samples[s] + dist;
-            item += stride;
-            state = item < n_items ? 1u : 0u;
-        }
-        const bool walk = state == 2u;                    // (a lane that took up an item above steps in this same iteration)
-        uint64_t idx = kidx;
-        const uint32_t e = loc_lf_step<MODE>(a.rows, ix.r, walk, idx, off, v, ff_total, [&]() {
-            lane_steps += walk ? 1u : 0u;
-            dist += walk ? 1u : 0u;
-        });
-        kidx = (IdxT)idx;
-        if (walk && (e != 0u || dist > a.n)) {            // a corrupt table: an error, not a hang
-            errs += 1;
+            return true;
+        },
+        [&](uint64_t item) {
             pos[item] = kPosNone;
             if (a.succ) a.aux[item] = 0;
-            item += stride;
-            state = item < n_items ? 1u : 0u;
-        }
-    }
-    flush_lane_stats_sa(stats, ff_total, errs, lane_steps, wave_steps);
+        });
 }
 
 namespace {
-template <int MODE, typename IdxT>
-void launch_locate_t(unsigned blocks, hipStream_t stream, const DevIndex &ix, const LocArgs &a, uint64_t *d_pos, uint64_t n_items, DevStats *d_stats) {
-    hipLaunchKernelGGL((locate_kernel<MODE, IdxT>), dim3(blocks), dim3(64), 0, stream, ix, a, d_pos, n_items, d_stats);
-}
+struct LocateFamily {
+    template <int MODE, typename IdxT> static auto kernel() { return &locate_kernel<MODE, IdxT>; }
+};
 }  // namespace
 
 hipError_t launch_locate(int mode, const DevIndex &ix, const LocArgs &a, uint64_t *d_pos, uint64_t n_items, DevStats *d_stats,
                          int num_cus, hipStream_t stream, LaunchInfo *info) {
     if (n_items == 0) return hipSuccess;
     if ((mode != 6 && mode != 3) || a.rate == 0u || !a.rows) return hipErrorInvalidValue;
-    // one-wavefront blocks; at most kLocateWaves per CU, so that a lane's list holds many walks wherever there are many items
-    const uint64_t want = (n_items + 63) / 64, cap = (uint64_t)(num_cus > 0 ? num_cus : 256) * kLocateWaves;
-    const unsigned blocks = (unsigned)(want < cap ? want : cap);
-    char nm[96];
-    snprintf(nm, sizeof(nm), "locate_kernel<%d, %s>", mode, ix.idx32 ? "unsigned int" : "unsigned long");
-    note_walk_launch(nm);
-    if (info) {
-        *info = LaunchInfo();
-        snprintf(info->kernel, sizeof(info->kernel), "%s", nm);
-        info->variant = a.succ ? 1 : 0; info->block_threads = 64; info->idx64 = ix.idx32 ? 0 : 1;
-        info->waves_per_cu = kLocateWaves;
-    }
-    if (mode == 6) {
-        if (ix.idx32) launch_locate_t<6, uint32_t>(blocks, stream, ix, a, d_pos, n_items, d_stats);
-        else launch_locate_t<6, uint64_t>(blocks, stream, ix, a, d_pos, n_items, d_stats);
-    } else {
-        if (ix.idx32) launch_locate_t<3, uint32_t>(blocks, stream, ix, a, d_pos, n_items, d_stats);
-        else launch_locate_t<3, uint64_t>(blocks, stream, ix, a, d_pos, n_items, d_stats);
-    }
-    return hipGetLastError();
+    return launch_lane_lists<LocateFamily>("locate_kernel", a.succ ? 1 : 0, mode, ix, n_items, kLocateWaves, num_cus, stream, info, a, d_pos,
+                                           n_items, d_stats);
 }
 
 // ------------------------------------------------------------------------------------------------ the position walk
@@ -194,9 +128,7 @@ hipError_t launch_sa_pos(const DevIndex &ix, const uint8_t *d_bases, const uint6
 
 hipError_t preload_sa(int mode, bool idx32) {
     hipFuncAttributes at;
-    const void *loc = mode == 6 ? (idx32 ? (const void *)locate_kernel<6, uint32_t> : (const void *)locate_kernel<6, uint64_t>)
-                                : (idx32 ? (const void *)locate_kernel<3, uint32_t> : (const void *)locate_kernel<3, uint64_t>);
-    hipError_t e = hipFuncGetAttributes(&at, loc);
+    hipError_t e = preload_family<LocateFamily>(mode, idx32);
     if (e == hipSuccess && mode == 6)
         e = hipFuncGetAttributes(&at, idx32 ? (const void *)sa_pos_kernel<uint32_t> : (const void *)sa_pos_kernel<uint64_t>);
     return e;

@@ -240,6 +240,43 @@ def test_positions_cap_below_the_total(ref_text):
     gpu.close()
 
 
+@pytest.mark.parametrize("mode", [6, 3])
+def test_walk_is_locate_mod_n(built_lib, mode):
+    """hits_walk_kernel and locate_kernel are one loop (locate_walk, movi_sa.hpp): the slots of the whole call are movi_locate_device's
+    entries of the packed positions the expansion left (stages = 2), reduced modulo n, slot for slot, and no slot at or past the total
+    is touched.  The first 3000 bases of ref.fasta, 300 items, max_occ = 4; rates 7 and n + 13, so that walks pass text position 0."""
+    import torch
+    import movi_amd
+    from oracle import build_index as B
+    ref = _ref()
+    gpu = movi_amd.MoveIndex.from_image(B.build_index_from_seqs([ref[:3000]], mode))
+    n = int(gpu.desc.length)
+    rng = np.random.default_rng(4242)
+    reads = [ref[a:a + 50] for a in rng.integers(0, 2950, 60).tolist()]
+    items = [(i, s, s + L) for i in range(len(reads)) for s, L in ((0, 2), (3, 4), (10, 6), (20, 12), (5, 45))]
+    assert len(items) == 300
+    wrapped = 0
+    for rate in (7, n + 13):
+        gpu.build_ssa(rate)
+        gpu.set_option("locate_matches_stages", 2)
+        _, first2, packed, _ = device_locate(gpu, reads, items, 4)
+        gpu.set_option("locate_matches_stages", 3)
+        occ, first, pos, err = device_locate(gpu, reads, items, 4)
+        assert gpu.last_launch()["kernel"].startswith("hits_walk_kernel<%d, " % mode) and gpu.last_stats().errors == 0
+        total = int(first[-1])
+        assert (first2 == first).all() and (err == 0).all() and (occ > 4).any() and (occ < 4).any()
+        assert 300 < total < pos.size and (packed[total:] == FILL).all() and (pos[total:] == FILL).all()
+        d = torch.from_numpy(packed[:total].view(np.int64).copy()).to(torch.device("cuda", 0))
+        gpu.locate_device(d.data_ptr(), total)
+        torch.cuda.synchronize()
+        assert gpu.last_launch()["kernel"].startswith("locate_kernel<%d, " % mode) and gpu.last_stats().errors == 0
+        entries = d.cpu().numpy().view(np.uint64)
+        assert (entries % np.uint64(n) == pos[:total]).all(), (mode, rate)
+        wrapped += int((entries >= np.uint64(n)).sum())
+    assert wrapped > 0                                        # some walk passed text position 0: its entry is SA + n
+    gpu.close()
+
+
 def built_hits_kernels(tmp_dir):
     """Demangled names of the hits_*_kernel instantiations in the library's gfx950 code object."""
     import movi_amd
